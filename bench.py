@@ -23,9 +23,15 @@ What one run proves about itself (all in the one JSON line rank 0 prints):
                 Python, like any caller's loop; --rollout-entry
                 enqueues a block's K steps with ONE call of the engine's open-loop rollout entry instead (include/bbai.h bbai_rollout,
                 the same launches) -- measured equal on every config, 65 536-env steps included: the GPU sets the pace.
-  * timing      W warmup steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides; a rank's
-                clock stops when its own device is idle, the block is the max over ranks (the closing barrier itself is
-                reported as timing.barrier_ms, not timed); repeated until >= --min-seconds of timed work.  Blocks alternate between PLAIN (nothing but
+  * timing      W warmup steps and K-step probe blocks up to 4 look-ahead periods after the reset (the engine is still settling
+                before that; a fixed count: timing.settle_steps, the probes' times in timing.probe_block_ms, outside the result),
+                then ONE timed block of EXACTLY K steps: --steps is the number of timed steps and `ms_per_step` is that block's
+                milliseconds / K.
+                Blocks are bracketed by barrier + synchronize on both sides; a rank's clock stops when its own device is idle,
+                the block is the max over ranks (the closing barrier itself is reported as timing.barrier_ms, not timed).  The
+                kernel times of `roofline` then come from a few untimed profiled steps behind the timed block.  --min-seconds
+                S > 0 instead repeats K-step blocks behind ONE probe block until >= S seconds of timed work (`timing.timed_steps`
+                says how many):  blocks alternate between PLAIN (nothing but
                 the steps and the parity tap) and PROFILED (every kernel launch bracketed by a HIP event pair on its
                 launch stream).  `value` / `ms_per_step` = the MEAN over the plain blocks (all their steps / all their seconds:
                 what a long rollout sustains -- reset storms, when a million envs time out on the same tick, are in it); the
@@ -70,6 +76,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E peak (MI355X_MICROARCH.md)
 HEADLINE_ENVS = 1048576     # BASELINE.json: "1M parallel envs"
+DUMP_ENVS = 1024            # --dump-outputs: envs of the whole job whose outputs are written ...
+DUMP_MAX_BYTES = 64 << 20   # ... and never more bytes than this in all
 
 # BASELINE.json configs: level, obs mode and the TOTAL env count the config is quoted on.  C4 / C5 are quoted on
 # 8 GPUs (131072 envs each); the "-shard" names run that per-GPU shard size on however many GPUs are used (profiling
@@ -143,7 +151,8 @@ def parse_args(argv=None):
     ap.add_argument("--action-seed", type=int, default=1234)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
                     help="a BASELINE.json config by name (overrides --level/--envs/--no-pixel); default = C5")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the K-step block until this much timed work")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): ONE timed block of exactly --steps steps; > 0: repeat the K-step block until this much timed work")
     ap.add_argument("--max-blocks", type=int, default=64)
     ap.add_argument("--parity-envs", type=int, default=1024, help="envs of every shard, scattered over it, checked against the oracle (0 = off)")
     ap.add_argument("--parity-pixel-envs", type=int, default=64)
@@ -169,6 +178,9 @@ def parse_args(argv=None):
     ap.add_argument("--rollout-entry", action="store_true", help="one bbai_rollout call per block instead of one bbai_step / bbai_render / bbai_tap_ids call per step from Python (the same launches)")
     ap.add_argument("--full-out", default=None, help="where the FULL record goes (default <repo>/gpurun_out/bench_full.json); stdout carries the compact judged line only")
     ap.add_argument("--dump-digest", default=None, help="write per-env output digests of this rank to <prefix>.rank<r>.npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step handed out (obs image, direction, reward, "
+                         "done) for a fixed, seeded sample of envs as DIR/<name>.npy (float32 / float64, < %d MB)" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -298,7 +310,7 @@ def compact_line(out, full_path=None):
     line["parity"] = par
     line["timing"] = {"blocks": t.get("blocks"), "ms_median": (bm.get("median") / K) if bm.get("median") else None,
                       "ms_max": (bm.get("max") / K) if bm.get("max") else None, "mean_over_median": t.get("mean_over_median"),
-                      "timed_seconds": t.get("timed_seconds"), "profiled_ms_per_step": t.get("profiled_ms_per_step"),
+                      "timed_seconds": t.get("timed_seconds"), "timed_steps": t.get("timed_steps"), "profiled_ms_per_step": t.get("profiled_ms_per_step"),
                       "loop": ("rollout" if str(t.get("loop", "")).startswith("one bbai_rollout") else "step")}
     line["kernel_avg_ms"] = r.get("kernel_avg_ms")
     rc = out.get("rccl") or {}
@@ -370,12 +382,48 @@ class Ctx(object):
     pass
 
 
-def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, PP, parity_budget, after_seed=None, digest=None, profile_tail=False):
+def dump_outputs(ctx, env, first, E, path):
+    """--dump-outputs: what the last timed step handed its caller -- obs["image"] (the pixels in pixel mode), obs["direction"],
+    reward (float32, as step() returns it), reward64 (the reference's float64) and done -- for a fixed sample of every shard's envs
+    (shard.scattered_ids: the same envs on every run of the same arguments), the engine's uint8 outputs widened exactly to float32.
+    env_ids.npy holds the global index of every row.  Rank 0 writes every rank's rows.  Outside the timed region."""
+    torch, np, ranks = ctx.torch, ctx.np, ctx.ranks
+    img = env.pixels if env.pixel else env.image
+    row_bytes = 4 * (img[0].numel() + 3) + 8 * 2
+    n = max(1, min(E, DUMP_ENVS // ranks.world, DUMP_MAX_BYTES // (row_bytes * ranks.world)))
+    ids = ctx.shard.scattered_ids(E, n, salt=first)
+    sel = torch.as_tensor(ids, dtype=torch.int64, device=env.device)
+    torch.cuda.synchronize()
+    mine = {"env_ids": np.asarray(ids, dtype=np.float64) + first,
+            "image": img[sel].cpu().numpy().astype(np.float32),
+            "direction": env.direction[sel].cpu().numpy().astype(np.float32),
+            "reward": env.reward[sel].cpu().numpy().astype(np.float32),
+            "reward64": env.reward64[sel].cpu().numpy().astype(np.float64),
+            "done": env.done[sel].cpu().numpy().astype(np.float32)}
+    parts = ranks.gather_objects(mine)
+    if ranks.rank != 0:
+        return None
+    os.makedirs(path, exist_ok=True)
+    files, total = {}, 0
+    for k in mine:
+        a = np.concatenate([p[k] for p in parts])
+        np.save(os.path.join(path, k + ".npy"), a)
+        files[k] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        total += a.nbytes
+    assert total <= DUMP_MAX_BYTES, total
+    return {"dir": os.path.abspath(path), "envs": files["env_ids"]["shape"][0], "bytes": total, "files": files}
+
+
+def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, PP, parity_budget, after_seed=None, digest=None, profile_tail=False,
+            after_timed=None):
     """One workload through the measured loop (babyai_amd/shard.py timed_blocks): create + seed + reset the shard (timed:
-    `setup_ms`), W warmup steps and ONE K-step probe block, then as many further K-step blocks as make `min_seconds`,
+    `setup_ms`), W warmup steps and K-step probe blocks outside the result (the engine is still settling after the reset: one
+    block with min_seconds, else as many as reach 4 look-ahead periods), then as many further K-step blocks as make `min_seconds`,
     alternately plain and profiled (profile_tail: all the plain blocks first, as ONE contiguous rollout whose mean is what a long run
     sustains -- reset storms land where they land, not in the blocks that happen to be profiled -- and a quarter as many profiled blocks
-    behind them), with the outputs of P scattered envs (pixels of PP) tapped at every step.  Returns a
+    behind them), with the outputs of P scattered envs (pixels of PP) tapped at every step.  min_seconds 0: ONE plain K-step block,
+    right behind the probes in the same loop, is the timed region, and a few untimed steps are profiled behind it.  `after_timed(env, first)` runs right after the last timed step,
+    before anything else steps the env.  Returns a
     dict with the block times, the per-kernel HIP-event times, the device logs for the oracle replay and the counters; the
     env is closed."""
     import time
@@ -433,8 +481,14 @@ def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, 
         env.tap(lg["image"][obs_row], lg["direction"][obs_row], lg["reward64"][row], lg["done"][row],
                 lg["pixels"][obs_row] if "pixels" in lg else None, ids=lg["ids"])
 
-    # phase 1: reset, W warmup steps and ONE K-step block; its time decides how many further blocks make min_seconds
-    S1 = W + K
+    # phase 1: reset, W warmup steps and ONE K-step block; its time decides how many further blocks make min_seconds.  Without
+    # min_seconds phase 1 runs K-step probe blocks until 4 look-ahead periods have passed since the reset: the engine is still
+    # settling before that (BossLevel pixels, 1 048 576 envs, period 16: 2.6 ms per step over steps 5-25, 1.60 over steps 25-65); the
+    # first block behind a pause (phase 2's set-up) is ~2 % slow as well.  A FIXED step count keeps the timed steps -- and what they
+    # compute -- the same on every run of the same arguments
+    n_probe = 1 if min_seconds > 0 else max(1, -(-(4 * period - W) // K))
+    n_timed1 = 0 if min_seconds > 0 else 1      # without min_seconds the timed block closes phase 1: no pause between it and the probes
+    S1 = W + (n_probe + n_timed1) * K
     actions1 = actions_torch(args.action_seed, 0, S1, first, E, dev)        # resident before the timed region
     ids1, PP1 = tap_ids(P, PP)
     log1 = make_log(S1, True, ids1, PP1)
@@ -476,13 +530,23 @@ def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, 
         env.rollout(actions1[t0:t0 + k], tap=log1, obs_row0=t0 + 1, row0=t0, step_tap=step_tap and log1 is not None)
 
     torch.cuda.synchronize()
-    blocks = shard.timed_blocks(env, actions1, W, K, 1, ranks, after1, run_steps=run1 if fast else None, step_fn=step1 if (step_tap and log1 is not None) else None)
-    want = int(min(max_blocks, max(0, -(-min_seconds // blocks[0]))))
-    want = int(ranks.max(want))
-    if want == 1:
-        want = 2                                      # one plain and one profiled block at least
+    local1, barrier1, resets1 = [], [], []
+
+    def before1(i):
+        if i == n_probe:
+            resets1.append(env.reset_count())
+    blocks = shard.timed_blocks(env, actions1, W, K, n_probe + n_timed1, ranks, after1, before_block=before1, local_out=local1, barrier_out=barrier1,
+                                run_steps=run1 if fast else None, step_fn=step1 if (step_tap and log1 is not None) else None)
+    probe = blocks[:n_probe]
+    if min_seconds > 0:
+        want = int(min(max_blocks, max(0, -(-min_seconds // blocks[0]))))
+        want = int(ranks.max(want))
+        if want == 1:
+            want = 2                                  # one plain and one profiled block at least
+    else:
+        want = 0                                      # the timed region was phase 1's last block: ONE plain block of exactly K steps
     n_plain, n_prof = (want + 1) // 2, want // 2      # alternating: plain (even) and profiled (odd) blocks
-    if profile_tail and want:
+    if profile_tail and want and min_seconds > 0:
         n_plain, n_prof = want, max(2, want // 4)
         want = n_plain + n_prof
     is_prof = (lambda i: i >= n_plain) if profile_tail else (lambda i: i % 2 == 1)
@@ -536,8 +600,12 @@ def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, 
         profiled = [b for i, b in enumerate(all_blocks) if is_prof(i)]
         local_blocks = [b for i, b in enumerate(local_blocks) if not is_prof(i)]
         del actions2
+    elif n_timed1:
+        blocks, local_blocks, barrier_s, resets0 = blocks[n_probe:], local1[n_probe:], barrier1[n_probe:], resets1[0]
     resets = ranks.sum(env.reset_count() - resets0)
-    if not want:                    # single-block run: nothing was bracketed; time a few untimed steps
+    if after_timed is not None:
+        after_timed(env, first)
+    if not profiled:                # no profiled block: bracket a few untimed steps behind the timed ones
         env.profile(True)
         for t in range(4):
             env.step(actions1[t])
@@ -547,7 +615,7 @@ def measure(ctx, level, pixel, E, total_envs, K, W, min_seconds, max_blocks, P, 
     env.profile(False)
     gate_timeouts = int(ranks.sum(env.gate_timeouts()))      # (synchronises; outside the timed blocks) a window gate that gave up = a void run
     m = {"level": level, "pixel": pixel, "E": E, "total_envs": total_envs, "first": first, "K": K, "W": W, "S1": S1, "S2": S2, "want": want,
-         "blocks": blocks, "profiled": profiled, "local_blocks": local_blocks, "barrier_s": barrier_s,
+         "blocks": blocks, "profiled": profiled, "local_blocks": local_blocks, "barrier_s": barrier_s, "probe": probe, "settle": W + n_probe * K,
          "kernel_ms": {k: v[0] for k, v in prof.items() if v[0] is not None},
          "kernel_launches": {k: v[1] for k, v in prof.items() if v[0] is not None},
          "resets": resets, "setup_ms": setup_ms, "gate_timeouts": gate_timeouts,
@@ -743,8 +811,14 @@ def main():
     if world > 1 and P:
         P = max(min(128, E), P // world)      # every rank's host cores are shared by all ranks of the node
     digest = shard.EnvDigest(E, dev, 147) if args.dump_digest else None
+    dumped = {}
+
+    def after_timed(env, first):
+        if args.dump_outputs:
+            dumped["record"] = dump_outputs(ctx, env, first, E, args.dump_outputs)
+
     m = measure(ctx, level, pixel, E, total_envs, K, W, args.min_seconds, args.max_blocks, P, args.parity_pixel_envs, args.parity_budget,
-                after_seed=after_seed, digest=digest, profile_tail=args.profile_tail)
+                after_seed=after_seed, digest=digest, profile_tail=args.profile_tail, after_timed=after_timed)
     env = m["env"]
     achievable = state["achievable"]
     blocks, profiled, local_blocks = m["blocks"], m["profiled"], m["local_blocks"]
@@ -773,7 +847,7 @@ def main():
                      per_rank_ms_per_step_min=min(per_rank_ms) if all(v is not None for v in per_rank_ms) else None,
                      per_rank_ms_per_step_max=max(per_rank_ms) if all(v is not None for v in per_rank_ms) else None,
                      launched_by="bench.py itself" if os.environ.get("BBAI_BENCH_SELF_LAUNCHED") else ("external launcher" if world > 1 else "single process")),
-        "timing": {"blocks": len(blocks), "steps_per_block": K,
+        "timing": {"blocks": len(blocks), "steps_per_block": K, "timed_steps": K * (len(blocks) + len(profiled)),
                    "block_ms": {"min": bs[0] * 1e3, "median": med * 1e3, "mean": st["mean"] * 1e3, "p90": st["p90"] * 1e3, "max": bs[-1] * 1e3},
                    "block_ms_list": [round(b * 1e3, 4) for b in blocks],
                    "timed_seconds": sum(blocks) + sum(profiled),
@@ -790,7 +864,10 @@ def main():
                    "profiled_ms_per_step": prof_med / K * 1e3 if profiled else None,
                    "event_pairs_cost_us_per_step": (prof_med - med) / K * 1e6 if profiled else None,
                    "note": "plain and profiled blocks alternate; kernel_avg_ms are the profiled blocks' launches and add up to (at most) "
-                           "profiled_ms_per_step"},
+                           "profiled_ms_per_step" if profiled else
+                           "one timed block of exactly `steps` steps behind the warmup and the probe blocks; kernel_avg_ms are 4 untimed "
+                           "profiled steps behind it",
+                   "settle_steps": m["settle"], "probe_block_ms": [round(b * 1e3, 4) for b in m["probe"]]},
         "setup_ms": m["setup_ms"],
         "state_layout": m["state_layout"], "lookahead_period": m["lookahead_period"],
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -803,6 +880,7 @@ def main():
                      "kernel_avg_ms": kernel_ms, "kernel_launches": kernel_launches, "measured_on": "rank 0"},
         "parity": None, "cpu_baseline": None, "configs": None, "gate_timeouts": m["gate_timeouts"],
         "build": {"commit": git_head(), "csrc_sha": csrc_sha()},
+        "dump_outputs": dumped.get("record"),
     }
     # the OPTIONAL gather of the encoded observations to rank 0 (north_star: "only an optional xGMI gather of obs to
     # rank 0"): timed on its own, after the timed region -- it is not part of a step and not part of `value`
@@ -860,7 +938,7 @@ def main():
             par["envs_all_ranks"] = len(ids2) * world
             par["env_selection"] = "scattered over each shard: both ends, wave / block boundaries, pseudo-random spread (shard.scattered_ids)"
             par["env_ids_rank0"] = {"min": min(ids2), "max": max(ids2), "count": len(ids2), "shard_envs": E}
-            par["steps_checked"] = "all %d steps of the run (warmup, probe block and the %d timed blocks)" % (S, want)
+            par["steps_checked"] = "all %d steps of the run (warmup, probe blocks and the %d timed blocks)" % (S, len(blocks) + len(profiled))
             out["parity"] = par
         if broken:
             exit_code = 4

@@ -136,49 +136,30 @@ def test_lane_group_width_does_not_matter(level, lanes):
         _one_lane()
 
 
-@pytest.mark.timeout(900)
-@pytest.mark.parametrize("level,n_envs,steps", [("BossLevel", 24, 300), ("SynthSeq", 16, 200), ("KeyCorridorS6R3", 8, 250)])
-def test_bot_differential_against_live_reference(level, n_envs, steps):
-    """Fresh seeds (not in the fixtures), the reference's Bot running live next to the host build (build container only)."""
-    from oracle import refenv
-    if not refenv.have_reference():
-        pytest.skip("reference tree not present")
-    import signal
-    refenv.import_reference()
-    from babyai.bot import Bot
-    from babyai.levels import level_dict
+DIFFERENTIAL = [("BossLevel", 24, 300), ("SynthSeq", 16, 200), ("KeyCorridorS6R3", 8, 250)]
+SWITCH_ON = ["GoToLocal", "PickupLoc", "GoTo", "Unlock"]
 
-    class Timeout(BaseException):
-        pass
 
-    def on_alarm(signum, frame):
-        raise Timeout()
+def _reference(key):
+    """The reference's answers to one of these protocols (tests/refpin_util.Replay over tools/gen_golden_refpin.py's record)."""
+    import refpin_util as rp
+    return rp.Replay(rp.load_json("bot_reference.json.gz")[key])
 
+
+def _differential(ref, level, n_envs, steps):
+    """Seeds not in the fixtures above, the reference's Bot next to the host build, 8 % random actions in between."""
     rng = np.random.RandomState(len(level))
     checked = 0
     for i in range(n_envs):
         seed = 880000 + 37 * i
-        ref = level_dict[level]()
-        if hasattr(ref, "locked_room"):
-            ref.locked_room = None
-        ref.seed(seed)
-        ref.reset()
+        ref.make(level, seed, "seed")
         env = HostEnv(make_cfg(level), seed)
         env.reset()
-        rbot, hbot = Bot(ref), HostBot(env)
+        ref.new_bot()
+        hbot = HostBot(env)
         first, last = True, None
         for t in range(steps):
-            try:
-                signal.signal(signal.SIGALRM, on_alarm)
-                signal.setitimer(signal.ITIMER_REAL, 3.0)
-                try:
-                    want = int(rbot.replan(last))
-                finally:
-                    signal.setitimer(signal.ITIMER_REAL, 0)
-            except BaseException as exc:
-                if isinstance(exc, KeyboardInterrupt):
-                    raise
-                want = None
+            want = ref.replan(last, 3.0)
             got = hbot.decide(first, last)
             first = False
             assert got == want, (level, seed, t, got, want)
@@ -187,23 +168,29 @@ def test_bot_differential_against_live_reference(level, n_envs, steps):
                 break
             a = want if rng.rand() > 0.08 else int(rng.randint(0, 7))
             last = a
-            _, r, d, _ = ref.step(a)
+            r, d = ref.step(a)
             _, hr, hd = env.step(a)
             assert bool(d) == bool(hd) and np.float32(r) == hr
             if d:
                 ref.reset()
                 env.reset()
-                rbot, hbot = Bot(ref), HostBot(env)
+                ref.new_bot()
+                hbot = HostBot(env)
                 first, last = True, None
     assert checked > n_envs * steps // 2
 
 
-def test_stack_capacity_is_the_one_documented_divergence():
-    """MiniBossLevel, `Level(seed=520)`: the reference bot enters an unproductive loop that grows its subgoal stack by
-    about four entries every five steps and keeps acting until max_steps (episode failed, reward 0).  With the default
-    48-entry stack the port reports 'gave up' (reason = capacity) at step 63, where the reference's stack reaches 52;
-    with a deeper stack (BBAI_BOT_STACK / stack_cap) it follows the reference to the end of the episode.
-    Either way the episode fails; demonstrations (first SOLVED episode per stream) are unaffected."""
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("level,n_envs,steps", DIFFERENTIAL)
+def test_bot_differential_against_live_reference(level, n_envs, steps):
+    """Fresh seeds (not in the fixtures of the tests above): what the reference's Bot decided, live, when
+    tools/gen_golden_refpin.py ran this protocol, against the host build."""
+    ref = _reference("differential/%s" % level)
+    _differential(ref, level, n_envs, steps)
+    assert ref.finished()
+
+
+def _stack_capacity(ref):
     level, seed = "MiniBossLevel", 520
     env = HostEnv(make_cfg(level), seed)
     env.reset()
@@ -211,14 +198,8 @@ def test_stack_capacity_is_the_one_documented_divergence():
     deep_env = HostEnv(make_cfg(level), seed)
     deep_env.reset()
     deep = HostBot(deep_env, stack_cap=1024)
-    ref = rbot = None
-    from oracle import refenv
-    if refenv.have_reference():
-        refenv.import_reference()
-        from babyai.bot import Bot
-        from babyai.levels import level_dict
-        ref = level_dict[level](seed=seed)
-        rbot = Bot(ref)
+    ref.make(level, seed, "ctor")
+    ref.new_bot()
     first, t, done, reward, deepest = True, 0, False, 0.0, 0
     while not done:
         b = deep.decide(first, None)
@@ -229,32 +210,32 @@ def test_stack_capacity_is_the_one_documented_divergence():
             assert (a == b) if t < 63 else (a is None and bot.dead_reason == 2), t
             if t < 63:
                 env.step(a)
-        if rbot is not None:
-            assert int(rbot.replan()) == b and len(rbot.stack) == deep.stack_depth, t
-            ref.step(b)
+        want, depth = ref.replan(), ref.stack_depth()
+        assert want == b and depth == deep.stack_depth, t
+        ref.step(b)
         first = False
         _, reward, done = deep_env.step(b)
         t += 1
     assert reward == 0 and t == deep_env.max_steps and deepest > 48
 
 
-@pytest.mark.parametrize("level", ["GoToLocal", "PickupLoc", "GoTo", "Unlock"])
-def test_expert_switched_on_mid_episode(level):
-    """`Bot(env)` constructed in the middle of an episode (after random steps) vs the port, which starts a fresh plan by
-    itself when it was not consulted on the previous step.  Only turn/forward noise before the switch, so that no
-    described object has moved (see bot_decide)."""
-    from oracle import refenv
-    if not refenv.have_reference():
-        pytest.skip("reference tree not present")
-    refenv.import_reference()
-    from babyai.bot import Bot
-    from babyai.levels import level_dict
+def test_stack_capacity_is_the_one_documented_divergence():
+    """MiniBossLevel, `Level(seed=520)`: the reference bot enters an unproductive loop that grows its subgoal stack by
+    about four entries every five steps and keeps acting until max_steps (episode failed, reward 0).  With the default
+    48-entry stack the port reports 'gave up' (reason = capacity) at step 63, where the reference's stack reaches 52;
+    with a deeper stack (BBAI_BOT_STACK / stack_cap) it follows the reference to the end of the episode.
+    Either way the episode fails; demonstrations (first SOLVED episode per stream) are unaffected.  The reference's decisions and
+    stack depths: tools/gen_golden_refpin.py's record."""
+    ref = _reference("stack_capacity")
+    _stack_capacity(ref)
+    assert ref.finished()
+
+
+def _switch_on(ref, level):
     rng = np.random.RandomState(3)
     for k in range(6):
         seed = 990000 + k
-        ref = level_dict[level]()
-        ref.seed(seed)
-        ref.reset()
+        ref.make(level, seed, "seed_keep")
         env = HostEnv(make_cfg(level), seed)
         env.reset()
         hbot = HostBot(env)
@@ -262,24 +243,34 @@ def test_expert_switched_on_mid_episode(level):
             done = False
             for t in range(int(rng.randint(3, 12))):
                 a = int(rng.choice([0, 1, 2]))
-                _, _, d, _ = ref.step(a)
+                _, d = ref.step(a)
                 env.step(a)
                 if d:
                     done = True
                     break
             if done:
                 break
-            rbot = Bot(ref)
+            ref.new_bot()
             last = None
             for t in range(40):
-                want = int(rbot.replan(last))
+                want = ref.replan(last)
                 got = hbot.decide(False, last)               # no `first` flag: the port notices by itself
                 assert got == want, (level, seed, t)
                 last = want
-                _, _, d, _ = ref.step(want)
+                _, d = ref.step(want)
                 env.step(want)
                 if d or t == 12:
                     done = d
                     break
             if done:
                 break
+
+
+@pytest.mark.parametrize("level", SWITCH_ON)
+def test_expert_switched_on_mid_episode(level):
+    """`Bot(env)` constructed in the middle of an episode (after random steps) vs the port, which starts a fresh plan by
+    itself when it was not consulted on the previous step.  Only turn/forward noise before the switch, so that no
+    described object has moved (see bot_decide).  The reference's side: tools/gen_golden_refpin.py's record."""
+    ref = _reference("switch_on/%s" % level)
+    _switch_on(ref, level)
+    assert ref.finished()

@@ -1,55 +1,44 @@
-"""Build-container only: the stand-alone oracle stepped side by side with the REFERENCE ITSELF
-(/root/reference/babyai imported unmodified on the restated gym_minigrid shim).  Skipped where the
-reference tree does not exist (the GPU box) -- the committed golden traces carry the pin there."""
-import random
+"""The stand-alone oracle against the REFERENCE ITSELF (babyai imported unmodified on the restated gym_minigrid shim), through
+records of the reference taken by tools/gen_golden_refpin.py (tests/golden/refpin/): the oracle replays the same seeds and the
+same actions and must produce the same missions, time limits, grids, observations, rewards and dones.  Only
+test_c1_digest_from_the_reference_itself still imports the reference: it re-derives a committed constant, where the tree exists."""
+import types
 
 import numpy as np
 import pytest
 
 from oracle import refenv
 from oracle import levels as olevels
-
-pytestmark = pytest.mark.skipif(not refenv.have_reference(), reason="/root/reference not present")
+import refpin_util as rp
 
 
 @pytest.fixture(scope="module")
-def level_dict():
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        refenv.import_reference()
-        from babyai.levels import level_dict
-    return level_dict
+def levels_record():
+    return rp.load_json("levels.json")
+
+
+@pytest.fixture(scope="module")
+def episodes_record():
+    return rp.load_json("random_episodes.json")
 
 
 @pytest.mark.parametrize("name", sorted(olevels.SPECS))
-def test_oracle_vs_reference(level_dict, name):
-    for seed in (2, 9):
-        ref = level_dict[name]()
-        if hasattr(ref, "locked_room"):
-            ref.locked_room = None          # see tools/gen_golden.py: constructor entropy leak
-        ref.seed(seed)
+def test_oracle_vs_reference(episodes_record, name):
+    def env_for_seed(seed):
         ora = olevels.make_env(name)
         ora.seed(seed)
-        rng = random.Random(seed)
-        for ep in range(2):
-            a, b = ref.reset(), ora.reset()
-            assert a["mission"] == b["mission"] and ref.max_steps == ora.max_steps
-            assert np.array_equal(a["image"], b["image"])
-            assert ref.grid == ora.grid
-            for t in range(250):
-                act = rng.randint(0, 6)
-                (a, ra, da, _), (b, rb, db, _) = ref.step(act), ora.step(act)
-                assert np.array_equal(a["image"], b["image"]) and a["direction"] == b["direction"]
-                assert ra == rb and da == db
-                if da:
-                    break
+        return ora
+
+    got, want = rp.random_episodes(env_for_seed), episodes_record[name]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w, (name, w["seed"], w["ep"])
 
 
-def test_reference_constructor_args_match_table(level_dict):
-    """The level table restates the reference constructors: compare against live reference objects."""
+def test_reference_constructor_args_match_table(levels_record):
+    """The level table restates the reference constructors: compare against the attributes of reference objects."""
     for name, (fam, kw) in olevels.SPECS.items():
-        ref = level_dict[name](seed=1)
+        ref = types.SimpleNamespace(**levels_record["attrs"][name])
         if fam == "fixed":
             assert (ref.room_size, ref.num_rows, ref.num_cols) == (kw.get("room_size", 9), kw.get("num_rows", 1), kw.get("num_cols", 1))
             continue
@@ -79,23 +68,29 @@ def test_reference_constructor_args_match_table(level_dict):
             assert ref.num_objs == kw.get("num_dists", 8)
 
 
-def test_reference_own_smoke_test_passes_on_shim(level_dict):
-    """A trimmed run of the reference's only test of this path (babyai/levels/levelgen.py:496-541):
-    surface/mission agreement and same-seed determinism for every registered level."""
-    for name, level in level_dict.items():
-        m0, m1 = level(seed=0), level(seed=0)
+def test_reference_own_smoke_test_passes_on_shim(levels_record):
+    """A trimmed run of the reference's only test of this path (babyai/levels/levelgen.py:496-541) -- surface/mission agreement
+    and same-seed determinism for every registered level -- on the oracle, whose seed-0 levels and first missions must be the
+    reference's."""
+    for name, rec in levels_record["seed0"].items():
+        m0, m1 = olevels.make_env(name, seed=0), olevels.make_env(name, seed=0)
         assert isinstance(m0.surface, str) and len(m0.surface) > 0
         assert m0.unwrapped.grid == m1.unwrapped.grid and m0.surface == m1.surface
+        grid = rp.Digest()
+        grid.add(m0.unwrapped.grid.encode(), np.uint8)
+        assert (m0.surface, grid.hexdigest()) == (rec["surface"], rec["grid"]), name
         obs = m0.reset()
-        assert obs["mission"] == m0.surface
+        assert obs["mission"] == m0.surface == rec["reset_mission"], name
 
 
-def test_level_table_covers_every_registered_level(level_dict):
+def test_level_table_covers_every_registered_level(levels_record):
     """All 105 ids the reference registers (levelgen.py:467-493) are in the engine's and the oracle's tables."""
     from babyai_amd.levels import LEVELS
-    assert set(level_dict.keys()) == set(LEVELS) == set(olevels.SPECS)
+    assert len(levels_record["registered"]) == 105
+    assert set(levels_record["registered"]) == set(LEVELS) == set(olevels.SPECS)
 
 
+@pytest.mark.skipif(not refenv.have_reference(), reason="reference tree not present (tests/test_oracle_golden.py pins the oracle to the same digest)")
 def test_c1_digest_from_the_reference_itself():
     from oracle import cpu_baseline
     from test_oracle_golden import C1_DIGEST

@@ -1,67 +1,44 @@
-"""babyai_amd.rollout.DeviceRollout vs the reference's own BaseAlgo.collect_experiences
-(babyai/rl/algos/base.py:131-260), run UNMODIFIED on the shim over reference envs in ParallelEnv workers.
-Needs /root/reference (build container only)."""
+"""babyai_amd.rollout.DeviceRollout vs the reference's own BaseAlgo.collect_experiences (babyai/rl/algos/base.py:131-260), run
+UNMODIFIED on the shim over reference envs in ParallelEnv workers: the experiences the reference collected are recorded by
+tools/gen_golden_refpin.py (tests/golden/refpin/rollout.npz) and the device rollout must reproduce them over oracle envs."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import refenv
-from rollout_util import OracleTensorEnv, ToyACModel, pad_tokens
+from rollout_util import OracleTensorEnv, ToyACModel
+import refpin_util as rp
 
-pytestmark = pytest.mark.skipif(not refenv.have_reference(), reason="reference tree not present")
-
-FIELDS = ("memory", "mask", "action", "value", "reward", "advantage", "returnn", "log_prob")
+FIELDS = rp.ROLLOUT_FIELDS
 
 
-def _reference_algo(level, seeds, T, scale):
-    refenv.import_reference()
-    import gym
-    from babyai.rl.algos.base import BaseAlgo
-    from babyai.rl.utils import DictList
-
-    class Algo(BaseAlgo):
-        def update_parameters(self):
-            pass
-
-    def preprocess(obss, device=None):
-        return DictList({"image": torch.tensor(np.array([o["image"] for o in obss]), dtype=torch.float),
-                         "instr": torch.tensor(pad_tokens([o["mission"] for o in obss]))})
-
-    envs = []
-    for s in seeds:
-        e = gym.make("BabyAI-%s-v0" % level)
-        e.seed(int(s))
-        envs.append(e)
-    return Algo(envs, ToyACModel(), T, 0.99, 7e-4, 0.95, 0.01, 0.5, 0.5, 1, preprocess,
-                lambda _0, _1, reward, _2: scale * reward, None)
+@pytest.fixture(scope="module")
+def rollout_record():
+    with np.load(rp.golden_path("rollout.npz")) as f:
+        return {k: f[k] for k in f.files}
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("level,scale", [("GoToObjS4", 16.0), ("GoToLocalS5N2", 16.0), ("GoToObjS4", 20.0)])
-def test_device_rollout_equals_reference_collect_experiences(level, scale):
+@pytest.mark.parametrize("level,scale", rp.ROLLOUT_CASES)
+def test_device_rollout_equals_reference_collect_experiences(rollout_record, level, scale):
     from babyai_amd.rollout import DeviceRollout
-    seeds = [500 + i for i in range(5)]
-    T = 24
-    algo = _reference_algo(level, seeds, T, scale)
-    roll = DeviceRollout(OracleTensorEnv(level, seeds), ToyACModel(), T, 0.99, 0.95, reward_scale=scale)
+    roll = DeviceRollout(OracleTensorEnv(level, rp.ROLLOUT_SEEDS), ToyACModel(), rp.ROLLOUT_T, 0.99, 0.95, reward_scale=scale)
     total_done = 0
-    for it in range(3):                                    # state carries across rollouts (memory, masks, log tails)
-        exps_ref, log_ref = algo.collect_experiences()
+    for it in range(rp.ROLLOUT_ITERS):                     # state carries across rollouts (memory, masks, log tails)
         exps, log = roll.collect_experiences()
-        exact = True               # rewards are shaped from the float64 reward, like the reference: exact for any scale
+
+        def ref(k):
+            return rollout_record[rp.rollout_key(level, scale, it, k)]
+        # rewards are shaped from the float64 reward, like the reference: exact for any scale
         for f in FIELDS:
-            a, b = getattr(exps_ref, f), getattr(exps, f)
+            a, b = torch.from_numpy(ref(f)), getattr(exps, f)
             assert a.shape == b.shape and a.dtype == b.dtype, f
-            if exact:
-                assert torch.equal(a, b), (level, it, f)
-            else:
-                assert torch.allclose(a, b, rtol=1e-6, atol=1e-6), (level, it, f)
-        assert torch.equal(exps_ref.obs.image, exps.obs.image)
-        assert torch.equal(exps_ref.obs.instr, exps.obs.instr)
-        assert log_ref["num_frames"] == log["num_frames"] and log_ref["episodes_done"] == log["episodes_done"]
-        assert log_ref["num_frames_per_episode"] == log["num_frames_per_episode"]
+            assert torch.equal(a, b), (level, it, f)
+        assert torch.equal(torch.from_numpy(ref("obs.image")), exps.obs.image)
+        assert torch.equal(torch.from_numpy(ref("obs.instr")), exps.obs.instr)
+        assert int(ref("num_frames")) == log["num_frames"] and int(ref("episodes_done")) == log["episodes_done"]
+        assert list(ref("num_frames_per_episode")) == list(log["num_frames_per_episode"])
         for k in ("return_per_episode", "reshaped_return_per_episode"):
-            assert np.allclose(log_ref[k], log[k], rtol=0 if exact else 1e-6, atol=0 if exact else 1e-6), k
+            assert np.array_equal(ref(k), np.asarray(log[k], dtype=np.float64)), k
         total_done += log["episodes_done"]
     assert total_done >= 5                                 # the comparison crossed auto-resets
 

@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""Fixtures of tests/golden/refpin/, recorded from the REFERENCE itself: babyai imported UNMODIFIED on the restated gym /
+gym_minigrid shim of oracle/shim (oracle/refenv.py finds the tree; BABYAI_REFERENCE points elsewhere).  The reference tree never
+travels with the repository: the fixtures are committed, and the tests replay the protocols of tests/refpin_util.py on the oracle
+and on the engine's host build against them.
+
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_refpin.py [part ...]      parts: levels random strict vocab rollout bot (default: all)
+
+  levels   the 105 registered ids, the constructor attributes of every level, and what the reference's own smoke test of
+           levelgen.py reads (surface / grid of a seed-0 construction, the mission of its first reset)  -> levels.json
+  random   tests/test_oracle_reference.py's random-action episodes of every level                      -> random_episodes.json
+  strict   tests/test_strict_modes.py's episodes with the verifier's strict modes switched on           -> strict_modes.json
+  vocab    the reference's InstructionsPreprocessor (babyai/utils/format.py) on tests/test_vocab_remap.py's missions -> vocab.npz
+  rollout  the reference's BaseAlgo.collect_experiences (babyai/rl/algos/base.py) over tests/rollout_util.ToyACModel -> rollout.npz
+  bot      the reference's expert (babyai/bot.py) answering tests/test_hostsim_bot.py's live protocols: every decision, step result
+           and stack depth, in call order (refpin_util.Recording; the tests replay them)                 -> bot_reference.json.gz
+"""
+import json
+import os
+import sys
+import tempfile
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.dont_write_bytecode = True
+from oracle import refenv  # noqa: E402
+from oracle import levels as olevels  # noqa: E402
+import refpin_util as rp  # noqa: E402
+
+assert refenv.have_reference(), "needs the reference tree (BABYAI_REFERENCE)"
+with warnings.catch_warnings():
+    warnings.simplefilter("ignore")
+    refenv.import_reference()
+    from babyai.levels import level_dict  # noqa: E402
+
+
+def write_json(name, obj):
+    os.makedirs(rp.GOLDEN, exist_ok=True)
+    with open(rp.golden_path(name), "w") as f:
+        json.dump(obj, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote", rp.golden_path(name))
+
+
+def part_levels():
+    attrs, smoke = {}, {}
+    for name in sorted(level_dict):
+        attrs[name] = rp.level_attrs(level_dict[name](seed=1))
+        m0 = level_dict[name](seed=0)
+        d = rp.Digest()
+        d.add(m0.unwrapped.grid.encode(), np.uint8)
+        rec = {"surface": m0.surface, "grid": d.hexdigest()}
+        rec["reset_mission"] = m0.reset()["mission"]
+        smoke[name] = rec
+    write_json("levels.json", {"registered": sorted(level_dict), "attrs": attrs, "seed0": smoke})
+
+
+def part_random():
+    out = {}
+    for name in sorted(olevels.SPECS):
+        def env_for_seed(seed):
+            e = rp.reference_level(level_dict, name)
+            e.seed(seed)
+            return e
+        out[name] = rp.random_episodes(env_for_seed)
+    write_json("random_episodes.json", out)
+
+
+def part_strict():
+    from babyai.levels.verifier import SeqInstr, AndInstr
+    out = {}
+    for name, leaf_bits, seq in rp.STRICT_CASES:
+        def env_for_seed(seed):
+            e = rp.reference_level(level_dict, name)
+            e.seed(seed)
+            return e
+
+        def arm(ref):
+            if seq and isinstance(ref.instrs, SeqInstr) and not isinstance(ref.instrs, AndInstr):
+                ref.instrs.strict = True
+            if leaf_bits:
+                def leaves(i):
+                    return leaves(i.instr_a) + leaves(i.instr_b) if isinstance(i, SeqInstr) else [i]
+                for leaf in leaves(ref.instrs):
+                    leaf.strict = True
+        out[name] = rp.strict_episodes(env_for_seed, arm)
+    write_json("strict_modes.json", out)
+
+
+def part_vocab():
+    from babyai.utils.format import InstructionsPreprocessor, get_vocab_path
+    missions = rp.vocab_missions()
+    with tempfile.TemporaryDirectory() as d:
+        os.environ["BABYAI_STORAGE"] = d
+        trained = InstructionsPreprocessor("trained")
+        trained([{"mission": m} for m in missions[:300]])      # a "trained model": its vocabulary grew over the first 300 missions
+        trained.vocab.save()
+        vocab = json.load(open(get_vocab_path("trained")))
+        ref = InstructionsPreprocessor("trained")                # ... continued from the saved file over all 10^4, 500 per batch
+        rows = []
+        for lo in range(0, len(missions), 500):
+            rows += list(ref([{"mission": m} for m in missions[lo:lo + 500]]).numpy())
+        width = max(len(r) for r in rows)
+        ids = np.zeros((len(rows), width), dtype=np.int16)
+        for i, r in enumerate(rows):
+            ids[i, :len(r)] = r
+        small = InstructionsPreprocessor("small")                # a vocabulary that has seen two missions
+        small([{"mission": m} for m in missions[:2]])
+        v2 = dict(small.vocab.vocab)
+        known_only = [m for m in missions if all(w in v2 for w in m.replace(",", " ").split())][:200]
+        again = InstructionsPreprocessor("small")
+        again.vocab.vocab = dict(v2)
+        again_rows = [list(again([{"mission": m}]).numpy()[0]) for m in known_only]
+        w2 = max(len(r) for r in again_rows)
+        again_ids = np.zeros((len(again_rows), w2), dtype=np.int16)
+        for i, r in enumerate(again_rows):
+            again_ids[i, :len(r)] = r
+    os.makedirs(rp.GOLDEN, exist_ok=True)
+    np.savez_compressed(rp.golden_path("vocab.npz"), missions_sha256=rp.missions_digest(missions), trained_vocab=json.dumps(vocab, sort_keys=True),
+                        ids=ids, small_vocab=json.dumps(v2, sort_keys=True), known_only=np.array(known_only), again_ids=again_ids)
+    print("wrote", rp.golden_path("vocab.npz"))
+
+
+def part_rollout():
+    import gym
+    import torch
+    from babyai.rl.algos.base import BaseAlgo
+    from babyai.rl.utils import DictList
+    from rollout_util import ToyACModel, pad_tokens
+
+    class Algo(BaseAlgo):
+        def update_parameters(self):
+            pass
+
+    def preprocess(obss, device=None):
+        return DictList({"image": torch.tensor(np.array([o["image"] for o in obss]), dtype=torch.float),
+                         "instr": torch.tensor(pad_tokens([o["mission"] for o in obss]))})
+
+    out = {}
+    for level, scale in rp.ROLLOUT_CASES:
+        envs = []
+        for s in rp.ROLLOUT_SEEDS:
+            e = gym.make("BabyAI-%s-v0" % level)
+            e.seed(int(s))
+            envs.append(e)
+        algo = Algo(envs, ToyACModel(), rp.ROLLOUT_T, 0.99, 7e-4, 0.95, 0.01, 0.5, 0.5, 1, preprocess,
+                    lambda _0, _1, reward, _2, scale=scale: scale * reward, None)
+        for it in range(rp.ROLLOUT_ITERS):                   # state carries across rollouts (memory, masks, log tails)
+            exps, log = algo.collect_experiences()
+            for f in rp.ROLLOUT_FIELDS + ("obs.image", "obs.instr"):
+                t = getattr(exps.obs, f[4:]) if f.startswith("obs.") else getattr(exps, f)
+                out[rp.rollout_key(level, scale, it, f)] = t.numpy()
+            for k in ("num_frames", "episodes_done"):
+                out[rp.rollout_key(level, scale, it, k)] = np.array(log[k])
+            for k in ("num_frames_per_episode", "return_per_episode", "reshaped_return_per_episode"):
+                out[rp.rollout_key(level, scale, it, k)] = np.array(log[k], dtype=np.float64 if "return" in k else np.int64)
+        del algo                                             # (ParallelEnv.__del__ ends its worker processes)
+    os.makedirs(rp.GOLDEN, exist_ok=True)
+    np.savez_compressed(rp.golden_path("rollout.npz"), **out)
+    print("wrote", rp.golden_path("rollout.npz"))
+
+
+def part_bot():
+    import test_hostsim_bot as tb
+    out = {}
+
+    def record(key, protocol, *args):
+        rec = rp.Recording(rp.LiveBotRef())
+        protocol(rec, *args)                                 # (the host build is checked against the live answers as they come)
+        out[key] = rec.log
+    for level, n_envs, steps in tb.DIFFERENTIAL:
+        record("differential/%s" % level, tb._differential, level, n_envs, steps)
+    for level in tb.SWITCH_ON:
+        record("switch_on/%s" % level, tb._switch_on, level)
+    record("stack_capacity", tb._stack_capacity)
+    os.makedirs(rp.GOLDEN, exist_ok=True)
+    import gzip
+    with gzip.GzipFile(rp.golden_path("bot_reference.json.gz"), "wb", mtime=0) as f:     # (mtime 0: the same bytes on every run)
+        f.write((json.dumps(out, sort_keys=True, separators=(",", ":")) + "\n").encode())
+    print("wrote", rp.golden_path("bot_reference.json.gz"))
+
+
+PARTS = {"levels": part_levels, "random": part_random, "strict": part_strict, "vocab": part_vocab, "rollout": part_rollout, "bot": part_bot}
+
+if __name__ == "__main__":
+    for p in sys.argv[1:] or list(PARTS):
+        PARTS[p]()
