@@ -19,7 +19,8 @@
 //   k_tokens       lane = env: mission text as fixed-vocabulary token ids of the envs that started a new episode.
 //   k_render_q / k_render   RGBImgPartialObsWrapper as a pure tile-atlas gather: atlas + per-cell tile ids in LDS, 16 bytes per lane per
 //                  store, a wave writes 1 KiB of contiguous pixels; persistent blocks fed by ONE ticket counter from 262 144 envs
-//                  (k_render_q), one-shot (512, 2) blocks below.
+//                  (k_render_q), one-shot (512, 2) blocks below.  Into the registered target (bbai_set_render_target): k_render_delta,
+//                  the delta render -- only the 128-byte lines whose cells changed since the frame the buffer holds are stored.
 //   k_bot<W>       lane = env: one decision of the reference's GOFAI expert (babyai/bot.py) per env, W = occupancy target
 //                  (bbai_bot.hpp); only launched by bbai_bot_act / bbai_bot_rollout.
 //
@@ -194,6 +195,15 @@ struct bbai_env {
     int render_queue_blocks;   // option "render_queue_blocks": their total number (0 = by render_queue_bpc)
     int render_pace;      // option "render_pace" (experiment): 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
                           // one counter serves them
+    // delta rendering (bbai_set_render_target): the registered buffer, and the atlas tile ids of the frame it holds
+    uint8_t* rt_pixels;   // the registered caller-owned uint8[n][9408] buffer (NULL: none); only this handle's renders write there
+    uint8_t* rt_shadow;   // [n][49] tile id of every cell of the frame in rt_pixels (allocated at the first registration)
+    bool rt_valid;        // rt_shadow describes rt_pixels; false after registration / bbai_set_atlas / bbai_render_invalidate / a full render into it
+    int64_t rt_filled;    // while not valid: envs [0, rt_filled) rewritten by full renders with shadow ids since (a split render's halves)
+    int render_delta;     // BBAI_RENDER_DELTA / option "render_delta": 1 (default) = renders into the registered buffer store only changed lines
+    int render_delta_sched;    // option "render_delta_sched": 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
+    int render_delta_tpb;      // option "render_delta_tpb": 512 (default, also for 0) or 1024 threads per delta render block
+    int render_delta_bpc;      // option "render_delta_bpc": delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
     int n_cus;            // compute units of the device
     int done_action_enum; // option "done_action_enum": done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
     int consume_fused;    // BBAI_CONSUME_FUSED / option "consume_fused": -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
@@ -1541,7 +1551,8 @@ __device__ __forceinline__ uint64_t render_chunk(const uint8_t* s_atlas, const u
 template <int RENDER_GROUP, int RENDER_BLOCK>     // envs per block iteration (between two barriers); threads per block
 __global__ __launch_bounds__(RENDER_BLOCK) void k_render(int64_t n, const uint8_t* __restrict__ image,
                                                          uint8_t* __restrict__ pixels, const uint8_t* __restrict__ atlas,
-                                                         const uint8_t* __restrict__ lut, int n_tiles) {
+                                                         const uint8_t* __restrict__ lut, int n_tiles,
+                                                         uint8_t* __restrict__ shadow /* NULL, or the registered target's tile ids [n][49] (k_render_delta) */) {
     __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
     __shared__ uint8_t s_lut[512];
     __shared__ uint8_t s_tile[RENDER_GROUP * VIEW * VIEW + 8];
@@ -1559,6 +1570,7 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render(int64_t n, const uint8_
             const uint8_t* o = image + (env0 + e) * OBS_BYTES + cell * 3;
             const int key = o[0] | (o[1] << 3) | (o[2] << 6);
             s_tile[c] = s_lut[(cell == 3 * VIEW + 6 ? 256 : 0) + key];
+            if (shadow) shadow[env0 * (VIEW * VIEW) + c] = s_tile[c];
         }
         __syncthreads();
         // 16 bytes per lane per store: a wave writes 1 KiB of contiguous pixels
@@ -1591,7 +1603,8 @@ template <int RENDER_GROUP, int RENDER_BLOCK, int NC, int K>
 __global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint8_t* __restrict__ image,
                                                            uint8_t* __restrict__ pixels, const uint8_t* __restrict__ atlas,
                                                            const uint8_t* __restrict__ lut, int n_tiles, unsigned int* __restrict__ counters,
-                                                           int pace_x16 /* experiment: 0, or 1/16 ns of wall clock per ticket (render_launch) */) {
+                                                           int pace_x16 /* experiment: 0, or 1/16 ns of wall clock per ticket (render_launch) */,
+                                                           uint8_t* __restrict__ shadow /* NULL, or the registered target's tile ids [n][49] (k_render_delta) */) {
     __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
     __shared__ uint8_t s_lut[512];
     __shared__ uint8_t s_tile[2][RENDER_GROUP * VIEW * VIEW + 8];
@@ -1630,6 +1643,7 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint
                 const uint8_t* o = image + (env0 + e) * OBS_BYTES + cell * 3;
                 const int key = o[0] | (o[1] << 3) | (o[2] << 6);
                 s_tile[buf][c] = s_lut[(cell == 3 * VIEW + 6 ? 256 : 0) + key];
+                if (shadow) shadow[env0 * (VIEW * VIEW) + c] = s_tile[buf][c];
             }
             if (kk == 0 && threadIdx.x == 0) s_ticket[tp ^ 1] = atomicAdd(counter, 1u);      // the next ticket rides under this one's stores
             __syncthreads();
@@ -1652,6 +1666,136 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint
         unsigned int* departed = counters + 64 * NC;
         if (atomicAdd(departed, 1u) == gridDim.x - 1) {
             for (int c = 0; c <= NC; ++c) atomicExch(counters + 64 * c, 0u);
+        }
+    }
+}
+
+// ---- delta render into the registered target (bbai_set_render_target) ----------------------------------------------------------
+// The registered buffer holds the previous frame of every env, and the handle's shadow plane holds the atlas tile id of every cell
+// of that frame (uint8[n][49]).  A frame cell whose tile id is unchanged has unchanged bytes, so only the 128-byte lines that
+// touch a changed cell are stored -- whole lines, never partial ones.  8 envs are 8 x 9408 = 588 x 128 bytes: a unit of 8 envs
+// starts on a line boundary whenever the buffer does (render_launch checks the alignment), and a line belongs to one unit; inside
+// it a line touches one env or two (9408 = 73.5 lines).  Per G-env group of a block iteration:
+//   A   one wave per env, one lane per cell: the new tile id (s_lut, as k_render), its old id from the shadow, a ballot gives the
+//       env's 49-bit dirty mask; the changed cells' ids go back to the shadow;
+//   B1  one lane per line: (dirty mask of its env(s)) & (the cells the line touches: a per-block table) -> a compacted line list;
+//   B2  8 lanes per listed line, 16 bytes each (render_chunk, as k_render): one full 128-byte line per 8 lanes.
+// Work is assigned statically (no ticket counter: one counter serves ~88 M tickets/s, which is the full render's own time at
+// 8-env tickets), so the next group's encoding and shadow bytes are loaded before the current group's stores.  SCHED 0: block b
+// takes groups b, b + grid, ... (the chip's stores advance as one window); 1: a contiguous range of groups per block.
+// Tables and tiles are double-buffered: two barriers per group.  While the shadow is not valid, render_launch runs the full render
+// (k_render_q / k_render) instead, which writes every byte and, given the shadow, every tile id.
+constexpr int LINE_BYTES = 128;
+constexpr int DELTA_UNIT = 8;                                          // envs per line-aligned unit
+constexpr int UNIT_LINES = DELTA_UNIT * PIX_BYTES / LINE_BYTES;        // 588
+constexpr int CELLS = VIEW * VIEW;
+constexpr int AGENT_CELL = 3 * VIEW + 6;
+static_assert(DELTA_UNIT * PIX_BYTES % LINE_BYTES == 0 && PIX_BYTES % 64 == 0, "8-env units are whole 128-byte lines");
+
+// The cells of one env that bytes [s, t) of its 56x56x3 image come from (s, t multiples of 8: one 8-byte chunk per tile row piece).
+__device__ __forceinline__ uint64_t line_cells(int s, int t) {
+    uint64_t m = 0;
+    for (int b = s; b < t; b += 8) {
+        const int ch = b >> 3, py = ch / CHUNKS_PER_ROW, cx = ch - py * CHUNKS_PER_ROW;
+        m |= 1ull << ((cx / 3) * VIEW + (py >> 3));
+    }
+    return m;
+}
+
+template <int G, int T, int SCHED>
+__global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __restrict__ image, uint8_t* __restrict__ pixels,
+                                                    uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
+                                                    const uint8_t* __restrict__ atlas, const uint8_t* __restrict__ lut, int n_tiles) {
+    static_assert(G % DELTA_UNIT == 0 && T % 64 == 0 && G % (T / 64) == 0, "whole units per group, whole envs per wave");
+    constexpr int W = T / 64, EPW = G / W, GL = G / DELTA_UNIT * UNIT_LINES;
+    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
+    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];        // cells of the line's first / second env (0: one env)
+    __shared__ uint8_t s_lea[UNIT_LINES];                              // the line's first env in the unit
+    __shared__ uint64_t s_dmask[2][G];
+    __shared__ uint8_t s_lut[512];
+    __shared__ uint8_t s_tile[2][G * CELLS + 8];
+    __shared__ uint16_t s_list[2][GL];
+    __shared__ unsigned int s_nd[2];
+    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
+    for (int k = threadIdx.x; k < 512; k += T) s_lut[k] = lut[k];
+    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
+        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
+        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
+        s_lea[l] = (uint8_t)ea;
+        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
+        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ngroups = (n + G - 1) / G;
+    int64_t g, gend, gstep;
+    if (SCHED == 0) { g = blockIdx.x; gend = ngroups; gstep = gridDim.x; }
+    else { const int64_t per = (ngroups + gridDim.x - 1) / gridDim.x; g = blockIdx.x * per; gend = g + per < ngroups ? g + per : ngroups; gstep = 1; }
+    // phase A's inputs of group `grp`, loaded ahead: 3 encoding bytes + the old id of this lane's cell in each of the wave's envs
+    uint32_t o0[EPW], o1[EPW], o2[EPW], old[EPW];
+    auto load = [&](int64_t grp) {
+#pragma unroll
+        for (int j = 0; j < EPW; ++j) {
+            const int64_t env = grp * G + wave + j * W;
+            o0[j] = o1[j] = o2[j] = old[j] = 0;
+            if (grp < gend && lane < CELLS && env < n) {
+                const uint8_t* o = image + env * OBS_BYTES + lane * 3;
+                o0[j] = o[0]; o1[j] = o[1]; o2[j] = o[2];
+                old[j] = shadow[env * CELLS + lane];
+            }
+        }
+    };
+    load(g);
+    __syncthreads();                                  // atlas, lut and line table loaded
+    int buf = 0;
+    for (; g < gend; g += gstep, buf ^= 1) {
+        const int64_t env0 = g * G;
+        const int ne = (int)(n - env0 < G ? n - env0 : G);
+        // A: new ids, dirty masks, shadow write-back
+#pragma unroll
+        for (int j = 0; j < EPW; ++j) {
+            const int e = wave + j * W;
+            const bool live = lane < CELLS && e < ne;
+            const int key = o0[j] | (o1[j] << 3) | (o2[j] << 6);
+            const uint32_t id = live ? s_lut[(lane == AGENT_CELL ? 256 : 0) + key] : 0;
+            const bool d = live && id != old[j];
+            const uint64_t m = __ballot(d);
+            if (live) s_tile[buf][e * CELLS + lane] = (uint8_t)id;
+            if (d) shadow[(env0 + e) * CELLS + lane] = (uint8_t)id;
+            if (lane == 0) s_dmask[buf][e] = m;
+        }
+        if (threadIdx.x == 0) s_nd[buf] = 0;
+        __syncthreads();
+        // B1: the group's dirty lines as a list (any order: every listed line is stored whole, by 8 lanes)
+        const int nl = (int)(((int64_t)ne * PIX_BYTES + LINE_BYTES - 1) / LINE_BYTES);
+        for (int L0 = threadIdx.x - lane; L0 < nl; L0 += T) {              // (whole waves: the ballot below)
+            const int L = L0 + lane;
+            bool d = false;
+            if (L < nl) {
+                const int u = L / UNIT_LINES, l = L - u * UNIT_LINES, ea = u * DELTA_UNIT + s_lea[l];
+                d = ((s_dmask[buf][ea] & s_lma[l]) | (s_lmb[l] ? s_dmask[buf][ea + 1] & s_lmb[l] : 0)) != 0;
+            }
+            const uint64_t m = __ballot(d);
+            if (!m) continue;
+            unsigned int base = 0;
+            if (lane == 0) base = atomicAdd(&s_nd[buf], (unsigned int)__builtin_popcountll(m));
+            base = __shfl(base, 0);
+            if (d) s_list[buf][base + __builtin_popcountll(m & ((1ull << lane) - 1))] = (uint16_t)L;
+        }
+        __syncthreads();
+        const int64_t gn = g + gstep;
+        load(gn);                                     // the next group's inputs ride under this group's stores
+        // B2: 16 bytes per lane, 8 lanes per listed line
+        const int nq = ne * VEC_PER_ENV, nd8 = (int)s_nd[buf] * 8;
+        u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
+        for (int i = threadIdx.x; i < nd8; i += T) {
+            const int q = (int)s_list[buf][i >> 3] * 8 + (i & 7);
+            if (q >= nq) continue;                    // (past the end of an odd-sized last group: half a line)
+            const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
+            const uint8_t* t49 = s_tile[buf] + e * CELLS;
+            const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
+            const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
+            u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+            __builtin_nontemporal_store(v, out + q);
         }
     }
 }
@@ -2059,6 +2203,8 @@ static int create_finish(bbai_env* e) {
         e->consume_fused = cf ? atoi(cf) : -1;
         const char* tv = getenv("BBAI_RENDER_TPB");
         e->render_tpb = tv ? atoi(tv) : 0;
+        const char* dv = getenv("BBAI_RENDER_DELTA");
+        e->render_delta = dv ? atoi(dv) != 0 : 1;
     }
     return BBAI_OK;
 }
@@ -2084,7 +2230,7 @@ void bbai_destroy(bbai_env* e) {
     void* bot_ptrs[] = {e->bot_state, e->bot_work, e->bot_stats, e->bot_rows};
     for (void* p : bot_ptrs) if (p) (void)hipFree(p);
     void* ptrs[] = {e->rec, e->hot, e->stale, e->mt, e->mti, e->vhead, e->vset, e->next_rec, e->next_hot, e->pending, e->first_slot, e->win_meta, e->totals, e->flow, e->gen_list, e->gen_count, e->reset_list, e->counters,
-                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids};
+                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->host_flags) (void)hipHostFree((void*)e->host_flags);
     delete e;
@@ -2523,6 +2669,22 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
     HIP_TRY(hipMemcpy(e->atlas, tiles, (size_t)n_tiles * TILE_BYTES, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->lut, lut, 512, hipMemcpyHostToDevice));
     e->n_tiles = n_tiles;
+    e->rt_valid = false; e->rt_filled = 0;           // the registered frame was drawn with the old atlas
+    return BBAI_OK;
+}
+
+int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
+    if (!e) ARG_FAIL("null handle");
+    ON_DEVICE(e->device);
+    if (pixels && !e->rt_shadow) HIP_TRY(hipMalloc((void**)&e->rt_shadow, (size_t)e->n * CELLS));
+    e->rt_pixels = pixels;
+    e->rt_valid = false; e->rt_filled = 0;
+    return BBAI_OK;
+}
+
+int bbai_render_invalidate(bbai_env* e) {
+    if (!e) ARG_FAIL("null handle");
+    e->rt_valid = false; e->rt_filled = 0;
     return BBAI_OK;
 }
 
@@ -2536,12 +2698,46 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
 // moved from 10.8 to 11.4 ns between boxes and between two processes on one box, an idle chip puts it elsewhere than the loop does
 // (a first-render tuner), and a perturb-and-observe controller on the launches' own durations paid more for its event pairs and its
 // hovering than it gained.  The one counter's 1.50 ms is the same on all of them: it ships; the gate stays as a knob.
-static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, void* stream, int64_t n_render = -1 /* envs input / pixels hold (default: the batch); the shape follows the BATCH size */) {
+static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, void* stream, int64_t n_render = -1 /* envs input / pixels hold (default: the batch); the shape follows the BATCH size */,
+                         int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */) {
     CallScope call(e, (hipStream_t)stream);
     if (call.rc != BBAI_OK) return call.rc;
     const int64_t nr = n_render < 0 ? e->n : n_render;
     {
     ProfScope prof_(e, 2, (hipStream_t)stream);
+    // The registered target (bbai_set_render_target): envs [env_off, env_off + nr) of it are rendered by k_render_delta, which stores
+    // only the lines whose cells changed -- or, while the shadow is not valid, by the full render below, which then also writes every
+    // tile id.  Any other render that writes into the registered buffer leaves a frame the shadow does not describe: it is invalidated.
+    // A render elsewhere leaves it alone.
+    uint8_t* const rt = e->rt_pixels;
+    const int64_t pb = PIX_BYTES;
+    const bool on_target = rt && pixels == rt + env_off * pb && env_off >= 0 && env_off + nr <= e->n;
+    const bool delta = on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
+    if (rt && !delta && pixels < rt + e->n * pb && pixels + nr * pb > rt) { e->rt_valid = false; e->rt_filled = 0; }
+    // the shadow is not valid: the full render below writes every byte of the range and, given `shadow`, every tile id of it
+    uint8_t* const shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
+    if (shadow && env_off == e->rt_filled) e->rt_filled = env_off + nr;        // (recorded before the launch: a failed launch fails the call)
+    if (shadow && e->rt_filled >= e->n) e->rt_valid = true;
+    if (delta && !shadow) {
+        const int cus = e->n_cus > 0 ? e->n_cus : 256;
+        // 1 048 576 BossLevel envs, random actions, settings alternated in one process (tools/ab.py; profiles/render_delta/ab.jsonl),
+        // k_render ms per launch: (1024 threads, 1 block per CU) interleaved 0.813, contiguous ranges 0.795, 2 blocks per CU 0.795;
+        // (512, 1) 0.795; (512, 3) 0.665 <- default: three independent blocks per CU hide one another's encoding / shadow loads and
+        // barriers (42 KB of LDS each: three fit).  Full render (k_render_q) 1.507.
+        const int T = e->render_delta_tpb == 1024 ? 1024 : 512;
+        constexpr int G = 32;
+        const int64_t groups = (nr + G - 1) / G;
+        const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
+        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
+        uint8_t* sh = e->rt_shadow + env_off * CELLS;
+#define RENDER_D(TT, SS) hipLaunchKernelGGL((k_render_delta<G, TT, SS>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, sh, \
+                                            e->atlas, e->lut, e->n_tiles)
+        if (T == 512) { if (e->render_delta_sched == 1) RENDER_D(512, 1); else RENDER_D(512, 0); }
+        else { if (e->render_delta_sched == 1) RENDER_D(1024, 1); else RENDER_D(1024, 0); }
+#undef RENDER_D
+        HIP_TRY(hipGetLastError());
+        return call.leave();
+    }
     // From 262 144 envs up: k_render_q -- ONE persistent 1024-thread block per CU, 8-env groups handed out by ONE ticket
     // counter.  Everything below was measured inside the step loop, settings alternated in one process (tools/ab.py),
     // 1 048 576 BossLevel envs, k_render ms per launch (profiles/r04/render_queue_*.jsonl; four leases = four boxes):
@@ -2573,7 +2769,7 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
             const int64_t want = e->render_queue_blocks > 0 ? e->render_queue_blocks : (e->render_queue_bpc > 0 ? (int64_t)cus * e->render_queue_bpc : (int64_t)cus * 1024 / TT); \
             const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, tickets)); \
             hipLaunchKernelGGL((k_render_q<GG, TT, NC, KK>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, \
-                               e->atlas, e->lut, e->n_tiles, e->render_tickets, pace); } while (0)
+                               e->atlas, e->lut, e->n_tiles, e->render_tickets, pace, shadow); } while (0)
         switch (qm) {          // (shapes other than 1 stay for measurements: tests/test_gpu_parity.py checks every one byte for byte)
         default:
         case 1: RENDER_Q(8, 1024, 1, 1); break;       // shipped
@@ -2598,7 +2794,7 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
     if (G != 2 && G != 4 && G != 8) G = big ? 8 : 2;
     if (T != 256 && T != 512 && T != 1024) T = big ? 1024 : 512;
     const dim3 grid((unsigned)((nr + G - 1) / G));
-#define RENDER_LAUNCH(GG, TT) hipLaunchKernelGGL((k_render<GG, TT>), grid, dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, e->atlas, e->lut, e->n_tiles)
+#define RENDER_LAUNCH(GG, TT) hipLaunchKernelGGL((k_render<GG, TT>), grid, dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, e->atlas, e->lut, e->n_tiles, shadow)
 #define RENDER_G(GG) do { if (T == 1024) RENDER_LAUNCH(GG, 1024); else if (T == 512) RENDER_LAUNCH(GG, 512); else RENDER_LAUNCH(GG, 256); } while (0)
     if (G == 2) RENDER_G(2); else if (G == 4) RENDER_G(4); else RENDER_G(8);
 #undef RENDER_G
@@ -2667,7 +2863,7 @@ static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* imag
             { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
             { int rc = call2.leave(); if (rc != BBAI_OK) return rc; }
         }
-        return render_launch(e, image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na);
+        return render_launch(e, image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na, na);
     }
 }
 
@@ -3190,6 +3386,10 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     else if (!strcmp(name, "render_pace")) e->render_pace = v < 0 ? 0 : v;
     else if (!strcmp(name, "render_group")) e->render_group = v;
     else if (!strcmp(name, "render_tpb")) e->render_tpb = v;
+    else if (!strcmp(name, "render_delta")) { e->render_delta = v != 0; e->rt_valid = false; e->rt_filled = 0; }
+    else if (!strcmp(name, "render_delta_sched")) e->render_delta_sched = v;
+    else if (!strcmp(name, "render_delta_tpb")) e->render_delta_tpb = v;
+    else if (!strcmp(name, "render_delta_bpc")) e->render_delta_bpc = std::max(0, v);
     else if (!strcmp(name, "step_prio")) e->step_prio = v;
     else if (!strcmp(name, "pregen_group")) e->pregen_group = v;
     else if (!strcmp(name, "pregen_lane")) {
@@ -3237,6 +3437,11 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     else if (!strcmp(name, "render_pace")) *out = e->render_pace;
     else if (!strcmp(name, "render_group")) *out = e->render_group;
     else if (!strcmp(name, "render_tpb")) *out = e->render_tpb;
+    else if (!strcmp(name, "render_delta")) *out = e->render_delta;
+    else if (!strcmp(name, "render_delta_sched")) *out = e->render_delta_sched;
+    else if (!strcmp(name, "render_delta_tpb")) *out = e->render_delta_tpb;
+    else if (!strcmp(name, "render_delta_bpc")) *out = e->render_delta_bpc;
+    else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
     else if (!strcmp(name, "step_prio")) *out = e->step_prio;
     else if (!strcmp(name, "pregen_group")) *out = e->pregen_group;
     else if (!strcmp(name, "pregen_lane")) *out = e->pregen_lane;

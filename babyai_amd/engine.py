@@ -61,6 +61,9 @@ def load_library():
         lib.bbai_step_render.argtypes = [P, P, P, P, P, P, P, I32, P, P]
     lib.bbai_set_atlas.argtypes = [P, P, I32, P]
     lib.bbai_render.argtypes = [P, P, P, P]
+    if hasattr(lib, "bbai_set_render_target"):
+        lib.bbai_set_render_target.argtypes = [P, P]
+        lib.bbai_render_invalidate.argtypes = [P]
     lib.bbai_set_token_buffer.argtypes = [P, P]
     lib.bbai_export_state.argtypes = [P, I64, I64, P, P, P]
     lib.bbai_import_state.argtypes = [P, I64, I64, P, P, P]
@@ -99,6 +102,7 @@ EXPORTED_SYMBOLS = (
     "bbai_checkpoint_bytes", "bbai_checkpoint_save", "bbai_checkpoint_load", "bbai_profile", "bbai_profile_read", "bbai_gae", "bbai_tap",
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
+    "bbai_set_render_target", "bbai_render_invalidate",
 )
 
 
@@ -219,6 +223,9 @@ class BatchedBabyAIEnv(object):
                 lut = np.ascontiguousarray(atlas["lut"], dtype=np.uint8)
                 _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0],
                                                           lut.ctypes.data), "bbai_set_atlas")
+                # renders into self.pixels store only the lines that changed (include/bbai.h bbai_set_render_target)
+                if hasattr(self.lib, "bbai_set_render_target"):
+                    _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
         self._missions = None
         self._obs_version = 0
         self.kernel_events = None      # bench.py: list of (tag, start_event, end_event) when enabled
@@ -280,6 +287,10 @@ class BatchedBabyAIEnv(object):
         out = self.pixels if out is None else out
         _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
         return out
+
+    def render_invalidate(self):
+        """Call after writing into self.pixels yourself: the next render rewrites every byte (include/bbai.h bbai_render_invalidate)."""
+        _check(self.lib, self.lib.bbai_render_invalidate(self.handle), "bbai_render_invalidate")
 
     def reset(self):
         _check(self.lib, self.lib.bbai_reset(self.handle, self.image.data_ptr(), self.direction.data_ptr(),

@@ -113,6 +113,19 @@ int bbai_render(bbai_env* env, const uint8_t* image_dev, uint8_t* pixels_dev, vo
 int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_dev, uint8_t* dir_dev, float* reward_dev,
                      double* reward64_dev, uint8_t* done_dev, int auto_reset, uint8_t* pixels_dev, void* stream);
 
+/* Delta rendering.  bbai_set_render_target registers a caller-owned uint8[N][56][56][3] pixel buffer (NULL unregisters) and says:
+ * "only this handle's renders write here".  The handle then keeps the atlas tile id of every cell of the frame the buffer holds
+ * (49 bytes per env, allocated at the first registration), and a render into the buffer -- bbai_render, bbai_step_render (split
+ * or not), bbai_rollout with pixels -- stores only the 128-byte lines whose cells changed since the frame before: same bytes, a
+ * fraction of the stores (how large a fraction depends on the actions: turns redraw most of the view, blocked moves and object
+ * actions almost nothing).  The first render after registration, after bbai_set_atlas, after bbai_render_invalidate and after
+ * option "render_delta" was set writes every byte.  Renders into any other buffer are full renders and leave the history alone;
+ * a full render into the registered buffer by another path (render_delta 0, a buffer not 128-byte aligned) invalidates it.
+ * A caller that writes into the registered buffer itself calls bbai_render_invalidate before the next render.  Register the
+ * buffer again when it is reallocated: a freed buffer's address may be handed out again with other contents. */
+int bbai_set_render_target(bbai_env* env, uint8_t* pixels_dev);
+int bbai_render_invalidate(bbai_env* env);
+
 /* Mission text as token ids, device-resident (replaces the per-step regex tokenisation of every mission in
  * InstructionsPreprocessor, babyai/utils/format.py:59-75): register a caller-owned uint8[N][72] buffer; the engine
  * rewrites env i's row whenever env i starts a new episode.  Ids follow babyai_amd/missions.py VOCAB, 0 = padding. */
@@ -272,6 +285,11 @@ int bbai_get_done_actions(bbai_env* env);
  *   "render_pace"       experiment: 1/16 ns of wall clock per render ticket (a time gate over two ticket counters); 0 = off (default)
  *   "render_queue_bpc", "render_queue_blocks"   persistent render blocks per CU (0 = 1024 threads' worth) / in total (0 = per CU)
  *   "render_group", "render_tpb"   envs / threads per one-shot render block (0 = by batch size)
+ *   "render_delta"      1 (default; BBAI_RENDER_DELTA) = renders into the registered target store only changed lines
+ *                       (bbai_set_render_target), 0 = full renders everywhere; setting it invalidates the target's history
+ *   "render_delta_sched", "render_delta_tpb", "render_delta_bpc"   the delta render's work split (0 = interleaved groups per
+ *                       block, 1 = contiguous ranges), threads per block (512 default / 1024) and blocks per CU (0 = 3 of 512
+ *                       threads, 1 of 1024)
  *   "step_prio", "pregen_group", "pregen_blocks", "pregen_min", "consume_fused"   as BBAI_STEP_PRIO / BBAI_PREGEN_GROUP /
  *                       BBAI_PREGEN_BLOCKS / BBAI_PREGEN_MIN / BBAI_CONSUME_FUSED
  *   "step_render_split" bbai_step_render / bbai_rollout with pixels: 1 = step the batch in two halves, the second under the first half's
