@@ -42,6 +42,7 @@ __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase
 #include "bbai_genl.hpp"
 #include "bbai_step.hpp"
 #include "bbai_view.hpp"
+#include "bbai_grid.hpp"
 #include "bbai_bot.hpp"
 #include "bbai_seed.hpp"
 
@@ -211,6 +212,10 @@ struct bbai_env {
     uint8_t* atlas;       // [n_tiles][192]
     uint8_t* lut;         // [2][256]
     int n_tiles;
+    uint8_t* grid_atlas[3];   // full-grid picture (bbai_set_grid_atlas), tile sizes 8 / 16 / 32: [GRID_MAX_TILES + 1][ts][ts][3]
+    uint8_t* grid_lut[3];     // [2][5][256]
+    int grid_tiles[3];        // installed tiles (0: none)
+    int grid_bpc;             // option "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
     bool seeded, live;
     uint8_t* bot_state;   // [n][bot_state_bytes(bot_stack)] the expert's per-env plan (bbai_bot_act; allocated on first use)
     int bot_stack;        // subgoal stack capacity per env (BBAI_BOT_STACK, default 48)
@@ -1801,6 +1806,135 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
 }
 
 // ------------------------------------------------------------------------------------------
+// k_render_grid : the full-grid picture, MiniGridEnv.render('rgb_array', highlight, tile_size), of listed envs (bbai_render_grid)
+// ------------------------------------------------------------------------------------------
+// A frame is uint8[H ts][W ts][3] (row = y, as Grid.render lays it out): H x W atlas tiles.  Per work item a block builds the tile-id
+// planes of its envs in LDS (bbai_grid.hpp: ONE lut lookup per cell, from the live record -- live_rec, as k_tokens / k_bot -- the pose and
+// the highlight mask), then streams the frames as 16-byte nontemporal stores, a frame being a flat run of 16-byte chunks (frame bytes
+// are a multiple of 192; row bytes need not be a multiple of 16).  A chunk is made of pieces that never cross a tile row: 8 bytes at
+// tile size 8 (24-byte tile rows, as render_chunk), 16 bytes at 16 and 32; per piece one multiply-high divide finds its pixel row and
+// tile, then the piece is copied from the atlas -- in LDS at 8 and 16 (25 / 102 KB), from L2 at 32 (≈400 KB: it stays resident).
+// Work items (render_grid_launch): several envs per item for small frames, several items per env for large ones; persistent blocks.
+// Writes nothing but `out`.  An id outside [0, n) draws every cell with the zero tile the atlas carries behind its last one.
+constexpr int GRID_BLOCK = 1024;
+constexpr int GRID_MAX_ENVS = 32;                // envs per work item
+constexpr int GRID_ID_BYTES = 4096;              // tile ids of one work item
+constexpr int GRID_MAX_TILES = 132;              // atlas tiles (+ the zero tile)
+constexpr int GRID_UNROLL = 4;                   // 16-byte chunks per lane in flight
+
+template <int TS> struct GridTile {
+    static constexpr int P = TS == 8 ? 8 : 16;           // bytes per piece
+    static constexpr int PPT = TS * 3 / P;               // pieces per tile row: 3, 3, 6
+    static constexpr int BYTES = TS * TS * 3;
+    static constexpr bool LDS = TS <= 16;
+};
+
+struct GridArgs {
+    LevelCfg c;
+    int64_t n;
+    const uint8_t* recs;
+    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
+    int depth;
+    const Hot* hots;
+    const int64_t* ids;          // NULL: envs 0 .. count - 1
+    int64_t count;
+    uint8_t* out;
+    const uint8_t* atlas;        // [n_tiles + 1][TS][TS][3], the last one all zero
+    const uint8_t* lut;          // [2][5][256]
+    int n_tiles, highlight;
+    int envs_per_item, slices;   // one of them is 1
+    int64_t items;
+    uint32_t frame16;            // 16-byte chunks per frame
+    uint64_t frame_magic;        // 2^32 / frame16 + 1: q / frame16 as a multiply-high (q frame16 < 2^32)
+    uint32_t ppr;                // pieces per pixel row
+    uint64_t ppr_magic;
+};
+
+__device__ __forceinline__ uint32_t grid_div(uint32_t q, uint64_t magic) { return (uint32_t)(((uint64_t)q * magic) >> 32); }
+
+template <int TS>
+__device__ __forceinline__ const uint8_t* grid_piece(const uint8_t* atlas, const uint8_t* ids, int W, const GridArgs& a, uint32_t p) {
+    using G = GridTile<TS>;
+    const uint32_t py = grid_div(p, a.ppr_magic), px = p - py * a.ppr;
+    const uint32_t tx = px / G::PPT, part = px - tx * G::PPT;
+    const int id = ids[(py / TS) * W + tx];
+    return atlas + id * G::BYTES + (py % TS) * (TS * 3) + part * G::P;
+}
+
+template <int TS>
+__global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(GridArgs a) {      // (8 waves per SIMD: two blocks per CU)
+    using G = GridTile<TS>;
+    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[G::LDS ? (GRID_MAX_TILES + 1) * G::BYTES : 16];
+    __shared__ __attribute__((aligned(16))) uint8_t s_lut[GRID_LUT_BYTES];
+    __shared__ uint8_t s_ids[GRID_ID_BYTES];
+    __shared__ uint32_t s_hl[GRID_MAX_ENVS][MAX_W];
+    __shared__ Hot s_hot[GRID_MAX_ENVS];
+    __shared__ const uint8_t* s_rec[GRID_MAX_ENVS];
+    const int tid = threadIdx.x;
+    const uint8_t* atlas = a.atlas;
+    if (G::LDS) {
+        for (int k = tid; k < (a.n_tiles + 1) * G::BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_atlas)[k] = ((const u32x4*)a.atlas)[k];
+        atlas = s_atlas;
+    }
+    for (int k = tid; k < GRID_LUT_BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_lut)[k] = ((const u32x4*)a.lut)[k];
+    const int W = a.c.W, HW = a.c.W * a.c.H;
+    const int64_t F16 = a.frame16;
+    constexpr int ESTRIDE = GRID_BLOCK / GRID_MAX_ENVS;       // the envs' view work spread over the waves (two envs per wave)
+    u32x4* const out = (u32x4*)a.out;
+    for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
+        const int64_t first = a.slices > 1 ? item / a.slices : item * a.envs_per_item;      // first output frame of the item
+        const int slice = (int)(item - first * a.slices);                                   // (0 unless sliced)
+        const int ne = a.slices > 1 ? 1 : (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
+        __syncthreads();                                  // atlas loaded / the previous item's ids consumed
+        if (tid % ESTRIDE == 0 && tid / ESTRIDE < ne) {
+            const int e = tid / ESTRIDE;
+            const int64_t env = a.ids ? a.ids[first + e] : first + e;
+            const uint8_t* rec = nullptr;
+            Hot h = {};
+            if (env >= 0 && env < a.n) {
+                h = a.hots[env];
+                rec = live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? h.slot : 0);
+                grid_highlight(a.c, rec, h, s_hl[e]);
+            }
+            s_hot[e] = h;
+            s_rec[e] = rec;
+        }
+        __syncthreads();
+        for (int ci = tid; ci < ne * HW; ci += GRID_BLOCK) {
+            const int e = ci / HW, cell = ci - e * HW;
+            const int y = cell / W, x = cell - y * W;
+            const uint8_t* rec = s_rec[e];
+            s_ids[ci] = (uint8_t)(rec ? grid_tile(a.c, rec, s_hot[e], s_lut, a.highlight, s_hl[e], x, y) : a.n_tiles);
+        }
+        __syncthreads();
+        // chunks [q0, q1) of the item, counted from its first frame's first chunk
+        const int64_t q0 = a.slices > 1 ? slice * F16 / a.slices : 0;
+        const int64_t q1 = a.slices > 1 ? (slice + 1) * F16 / a.slices : ne * F16;
+        u32x4* const base = out + first * F16;
+        for (int64_t qb = q0 + tid; qb < q1; qb += GRID_UNROLL * GRID_BLOCK) {
+            u32x4 v[GRID_UNROLL];
+#pragma unroll
+            for (int u = 0; u < GRID_UNROLL; ++u) {
+                const uint32_t q = (uint32_t)(qb + u * GRID_BLOCK < q1 ? qb + u * GRID_BLOCK : q1 - 1);     // (past the end: a chunk of the item, not stored)
+                const uint32_t e = a.slices > 1 ? 0u : grid_div(q, a.frame_magic);
+                const uint32_t j = q - e * (uint32_t)F16;
+                const uint8_t* ids = s_ids + e * HW;
+                if (TS == 8) {
+                    const uint64_t lo = *(const uint64_t*)grid_piece<TS>(atlas, ids, W, a, 2 * j);
+                    const uint64_t hi = *(const uint64_t*)grid_piece<TS>(atlas, ids, W, a, 2 * j + 1);
+                    v[u] = u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+                } else {
+                    v[u] = *(const u32x4*)grid_piece<TS>(atlas, ids, W, a, j);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < GRID_UNROLL; ++u)
+                if (qb + u * GRID_BLOCK < q1) __builtin_nontemporal_store(v[u], base + qb + u * GRID_BLOCK);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_tokens : mission strings as fixed-vocabulary token ids, produced on the device from the compiled
 // instruction program (grammar: babyai/levels/verifier.py:64-94,248-249,287-288,318-319,366-367,439-440,
 // 480-481,526-527).  Vocabulary ids = babyai_amd/missions.py VOCAB (1..32, 0 = padding).
@@ -2232,6 +2366,7 @@ void bbai_destroy(bbai_env* e) {
     void* ptrs[] = {e->rec, e->hot, e->stale, e->mt, e->mti, e->vhead, e->vset, e->next_rec, e->next_hot, e->pending, e->first_slot, e->win_meta, e->totals, e->flow, e->gen_list, e->gen_count, e->reset_list, e->counters,
                     e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (int k = 0; k < 3; ++k) { if (e->grid_atlas[k]) (void)hipFree(e->grid_atlas[k]); if (e->grid_lut[k]) (void)hipFree(e->grid_lut[k]); }
     if (e->host_flags) (void)hipHostFree((void*)e->host_flags);
     delete e;
 }
@@ -2813,6 +2948,79 @@ int bbai_render(bbai_env* e, const uint8_t* image, uint8_t* pixels, void* stream
     return render_launch(e, image, pixels, stream);
 }
 
+// ---- the full-grid picture (k_render_grid) ----
+static int grid_ts_index(int ts) { return ts == 8 ? 0 : ts == 16 ? 1 : ts == 32 ? 2 : -1; }
+
+int bbai_set_grid_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_tiles, const uint8_t* lut) {
+    const int k = grid_ts_index(tile_size);
+    if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
+    if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    if (n_tiles < 1 || n_tiles > GRID_MAX_TILES) ARG_FAIL("tile count out of range");
+    for (int i = 0; i < GRID_LUT_BYTES; ++i)
+        if (lut[i] >= n_tiles) ARG_FAIL("a lut entry names a tile the atlas does not hold");
+    ON_DEVICE(e->device);
+    const size_t tb = (size_t)tile_size * tile_size * 3;
+    HIP_TRY(hipDeviceSynchronize());                 // (a render still in flight may read the atlas being replaced)
+    if (!e->grid_atlas[k]) HIP_TRY(hipMalloc((void**)&e->grid_atlas[k], (GRID_MAX_TILES + 1) * tb));
+    if (!e->grid_lut[k]) HIP_TRY(hipMalloc((void**)&e->grid_lut[k], GRID_LUT_BYTES));
+    HIP_TRY(hipMemcpy(e->grid_atlas[k], tiles, n_tiles * tb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(e->grid_atlas[k] + n_tiles * tb, 0, tb));        // the zero tile: frames of ids outside [0, n)
+    HIP_TRY(hipMemcpy(e->grid_lut[k], lut, GRID_LUT_BYTES, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    e->grid_tiles[k] = n_tiles;
+    return BBAI_OK;
+}
+
+}  // extern "C"
+
+// Launch shape by frame size F: small frames (F <= 64 KB: GoToLocal at tile size 8 is 12 KB) -- several envs per work item, about 128 KB
+// of frames each; large ones (BossLevel at 32: 1.49 MB) -- an env in slices of about 256 KB.  Persistent blocks: 2 per CU at tile sizes 8
+// and 32 (35 KB / 10 KB of LDS), 1 at 16 (the 102 KB atlas); option "grid_render_bpc" overrides.
+template <int TS>
+static void render_grid_launch(bbai_env* e, int highlight, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    const int k = grid_ts_index(TS);
+    const LevelCfg& c = e->cfg;
+    const int64_t F = (int64_t)c.H * TS * c.W * TS * 3;
+    GridArgs a;
+    a.c = c; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
+    a.ids = ids; a.count = count; a.out = out; a.atlas = e->grid_atlas[k]; a.lut = e->grid_lut[k]; a.n_tiles = e->grid_tiles[k];
+    a.highlight = highlight ? 1 : 0;
+    a.envs_per_item = 1; a.slices = 1;
+    if (F <= 65536) a.envs_per_item = (int)std::max<int64_t>(1, std::min<int64_t>({131072 / F, GRID_MAX_ENVS, GRID_ID_BYTES / (c.W * c.H)}));
+    else a.slices = (int)std::max<int64_t>(1, F / 262144);
+    a.items = a.slices > 1 ? count * a.slices : (count + a.envs_per_item - 1) / a.envs_per_item;
+    a.frame16 = (uint32_t)(F / 16);
+    a.frame_magic = (1ull << 32) / a.frame16 + 1;
+    a.ppr = (uint32_t)(c.W * TS * 3 / GridTile<TS>::P);
+    a.ppr_magic = (1ull << 32) / a.ppr + 1;
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const int bpc = e->grid_bpc > 0 ? e->grid_bpc : (TS == 16 ? 1 : 2);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * bpc));
+    hipLaunchKernelGGL((k_render_grid<TS>), dim3(blocks), dim3(GRID_BLOCK), 0, s, a);
+}
+
+extern "C" {
+
+int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    const int k = grid_ts_index(tile_size);
+    if (!e) ARG_FAIL("null handle");
+    if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
+    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
+    if (!e->grid_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_grid: no atlas for tile size %d (bbai_set_grid_atlas)", tile_size); return BBAI_ERR_STATE; }
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "render_grid before reset"); return BBAI_ERR_STATE; }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    if (call.rc != BBAI_OK) return call.rc;
+    if (k == 0) render_grid_launch<8>(e, highlight, ids, count, out, s);
+    else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
+    else render_grid_launch<32>(e, highlight, ids, count, out, s);
+    HIP_TRY(hipGetLastError());
+    return call.leave();
+}
+
 }  // extern "C"
 
 // step + render of a pixel batch as ONE call.  The render is a pure store stream at the chip's fill rate (k_render_q: 1.50 ms per
@@ -3390,6 +3598,7 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     else if (!strcmp(name, "render_delta_sched")) e->render_delta_sched = v;
     else if (!strcmp(name, "render_delta_tpb")) e->render_delta_tpb = v;
     else if (!strcmp(name, "render_delta_bpc")) e->render_delta_bpc = std::max(0, v);
+    else if (!strcmp(name, "grid_render_bpc")) e->grid_bpc = std::max(0, v);
     else if (!strcmp(name, "step_prio")) e->step_prio = v;
     else if (!strcmp(name, "pregen_group")) e->pregen_group = v;
     else if (!strcmp(name, "pregen_lane")) {
@@ -3441,6 +3650,7 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     else if (!strcmp(name, "render_delta_sched")) *out = e->render_delta_sched;
     else if (!strcmp(name, "render_delta_tpb")) *out = e->render_delta_tpb;
     else if (!strcmp(name, "render_delta_bpc")) *out = e->render_delta_bpc;
+    else if (!strcmp(name, "grid_render_bpc")) *out = e->grid_bpc;
     else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
     else if (!strcmp(name, "step_prio")) *out = e->step_prio;
     else if (!strcmp(name, "pregen_group")) *out = e->pregen_group;

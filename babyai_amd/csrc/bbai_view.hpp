@@ -246,7 +246,9 @@ template <class Sink> BB_HD void encode_cells_to(const uint32_t* cp, Sink o) {
 
 // observe_env through the kernel's pipeline (host build / tests): the window fetched as k_step fetches it from the record's appearance
 // plane (7 rows x 3 aligned dwords), view_cells_perm, encode_cells into a one-row RowPacker area.  `rows` = ROWS_FRONT + 147 + 16 bytes.
-BB_HD int observe_env_perm(const LevelCfg& c, const uint8_t* rec, const Hot& h, int nfe, uint8_t* rows) {
+// view_env_cells: the masked view cells cp[13] alone (cell (vi, vj) = byte 7 vi + vj; 0 = not visible) -- also the full-grid picture's highlight
+// (bbai_grid.hpp).
+BB_HD int view_env_cells(const LevelCfg& c, const uint8_t* rec, const Hot& h, int nfe, uint32_t* cp) {
     const int dir = h.dir;
     const int txm = h.ax + MARGIN + (dir == 0 ? 0 : dir == 2 ? -6 : -3);
     const int tym = h.ay + MARGIN + (dir == 1 ? 0 : dir == 3 ? -6 : -3);
@@ -254,9 +256,13 @@ BB_HD int observe_env_perm(const LevelCfg& c, const uint8_t* rec, const Hot& h, 
     uint32_t wd[3 * VIEW];
     for (int r = 0; r < VIEW; ++r) { wd[3 * r] = q[r * (c.ES >> 2)]; wd[3 * r + 1] = q[r * (c.ES >> 2) + 1]; wd[3 * r + 2] = q[r * (c.ES >> 2) + 2]; }
     const uint32_t ce = h.carry != NONE8 ? rec[c.off_app + h.carry] : (uint32_t)E_EMPTY;
-    uint32_t cp[13];
     int fe2;
     view_cells_perm(wd, txm & 3, dir, ce, nfe, cp, fe2);
+    return fe2;
+}
+BB_HD int observe_env_perm(const LevelCfg& c, const uint8_t* rec, const Hot& h, int nfe, uint8_t* rows) {
+    uint32_t cp[13];
+    const int fe2 = view_env_cells(c, rec, h, nfe, cp);
     encode_cells(cp, RowPacker(rows + ROWS_FRONT, 0));
     return fe2;
 }

@@ -23,6 +23,8 @@ from . import missions
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBAI_ENGINE_LIB") or os.path.join(_HERE, "libbbai_hip.so")      # (override: experiment builds)
 ATLAS_PATH = os.path.join(_HERE, "data", "tile_atlas_ts8.npz")
+GRID_ATLAS_PATH = os.path.join(_HERE, "data", "grid_atlas_ts%d.npz")      # full-grid picture, per tile size (written by build(): tools/gen_grid_atlas.py)
+GRID_TILE_SIZES = (8, 16, 32)
 
 OBS_BYTES = 147
 PIX = 56
@@ -64,6 +66,9 @@ def load_library():
     if hasattr(lib, "bbai_set_render_target"):
         lib.bbai_set_render_target.argtypes = [P, P]
         lib.bbai_render_invalidate.argtypes = [P]
+    if hasattr(lib, "bbai_render_grid"):
+        lib.bbai_set_grid_atlas.argtypes = [P, I32, P, I32, P]
+        lib.bbai_render_grid.argtypes = [P, I32, I32, P, I64, P, P]
     lib.bbai_set_token_buffer.argtypes = [P, P]
     lib.bbai_export_state.argtypes = [P, I64, I64, P, P, P]
     lib.bbai_import_state.argtypes = [P, I64, I64, P, P, P]
@@ -102,7 +107,7 @@ EXPORTED_SYMBOLS = (
     "bbai_checkpoint_bytes", "bbai_checkpoint_save", "bbai_checkpoint_load", "bbai_profile", "bbai_profile_read", "bbai_gae", "bbai_tap",
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
-    "bbai_set_render_target", "bbai_render_invalidate",
+    "bbai_set_render_target", "bbai_render_invalidate", "bbai_set_grid_atlas", "bbai_render_grid",
 )
 
 
@@ -228,6 +233,7 @@ class BatchedBabyAIEnv(object):
                     _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
         self._missions = None
         self._obs_version = 0
+        self._grid_atlases = set()      # tile sizes whose full-grid atlas is installed on the handle (render_grid)
         self.kernel_events = None      # bench.py: list of (tag, start_event, end_event) when enabled
         self.num_actions = 7
         self.max_mission_tokens = min(TOK_MAX, missions.max_mission_tokens(self.cfg))
@@ -286,6 +292,46 @@ class BatchedBabyAIEnv(object):
         image = self.image if image is None else image
         out = self.pixels if out is None else out
         _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
+        return out
+
+    def render_grid(self, ids=None, tile_size=32, highlight=True, out=None):
+        """MiniGridEnv.render('rgb_array', highlight=highlight, tile_size=tile_size) of envs `ids` (None = every env; else an int sequence or
+        an int64 device tensor, any order, repeats allowed) -> uint8[k, H*ts, W*ts, 3] on the device, asynchronous on the current stream
+        (include/bbai.h bbai_render_grid).  Reads the current state and writes nothing but `out`; an id outside [0, num_envs) gives an
+        all-zero frame.  The atlas of a tile size is installed on first use."""
+        torch = self.torch
+        ts = int(tile_size)
+        if ts not in GRID_TILE_SIZES:
+            raise ValueError("tile_size %r: the engine has atlases for %s only (tools/gen_grid_atlas.py makes them)" % (tile_size, GRID_TILE_SIZES))
+        if ts not in self._grid_atlases:
+            if not os.path.isfile(GRID_ATLAS_PATH % ts):
+                raise EngineError("tile atlas %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                                  "(tools/gen_grid_atlas.py)" % (GRID_ATLAS_PATH % ts))
+            with np.load(GRID_ATLAS_PATH % ts) as f:
+                tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
+                lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
+            _check(self.lib, self.lib.bbai_set_grid_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_grid_atlas")
+            self._grid_atlases.add(ts)
+        ids_ptr = None
+        if ids is None:
+            k = self.num_envs
+        else:
+            if not isinstance(ids, torch.Tensor):
+                ids = torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1), device=self.device)
+            if ids.dtype != torch.int64 or ids.device != self.device or ids.dim() != 1:
+                raise ValueError("ids: int64[k] on %s" % (self.device,))
+            ids = ids.contiguous()
+            self._grid_ids = ids            # keep alive until the launch is consumed
+            k = int(ids.shape[0])
+            ids_ptr = ids.data_ptr()
+        shape = (k, self.cfg.H * ts, self.cfg.W * ts, 3)
+        if out is None:
+            with torch.cuda.device(self.dev_index):
+                out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out: contiguous uint8%s on %s" % (list(shape), self.device))
+        _check(self.lib, self.lib.bbai_render_grid(self.handle, ts, 1 if highlight else 0, ids_ptr, k, out.data_ptr() if k else None,
+                                                    self._stream()), "bbai_render_grid")
         return out
 
     def render_invalidate(self):

@@ -250,6 +250,16 @@ class SingleEnv(object):
         a = int(self.engine.bot_actions(prev)[0])
         return None if a == self.engine.BOT_GAVE_UP else a
 
+    def render(self, mode="human", close=False, highlight=True, tile_size=32):
+        """MiniGridEnv.render (gym_minigrid minigrid.py; scripts/manual_control.py:14): 'rgb_array' -> numpy uint8[H*ts, W*ts, 3] of the
+        whole grid, drawn on the device (BatchedBabyAIEnv.render_grid; tile sizes 8, 16, 32).  'human' needs a window, which this
+        engine does not provide."""
+        if close:
+            return None
+        if mode != "rgb_array":
+            raise NotImplementedError("render(mode=%r): only 'rgb_array' (no window: DESIGN.md section 7)" % (mode,))
+        return self.engine.render_grid(None, tile_size=tile_size, highlight=highlight)[0].cpu().numpy()
+
     def close(self):
         self.engine.close()
 

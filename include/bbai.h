@@ -126,6 +126,24 @@ int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_d
 int bbai_set_render_target(bbai_env* env, uint8_t* pixels_dev);
 int bbai_render_invalidate(bbai_env* env);
 
+/* The full-grid picture: MiniGridEnv.render('rgb_array', highlight, tile_size) (gym_minigrid minigrid.py; called by
+ * scripts/manual_control.py:14 with --tile_size, scripts/enjoy.py:101,108 in 'human' mode) of listed envs, on the device.
+ * bbai_set_grid_atlas installs the tile atlas of one tile size (8, 16 or 32; babyai_amd/data/grid_atlas_ts<size>.npz, made by
+ * tools/gen_grid_atlas.py): tiles uint8[n_tiles][ts][ts][3], n_tiles <= 132, and lut[highlight][agent][key] (agent = 0, or 1 + the
+ * agent's direction on that cell; key = type | colour << 3 | state << 6); synchronous.  A handle keeps the atlas of every tile size
+ * installed on it.  BBAI_ERR_ARG for another tile size, a tile count out of range or a lut entry >= n_tiles.
+ * bbai_render_grid writes frame k = the picture of env ids_dev[k] (int64 device array; NULL = envs 0 .. count - 1) into
+ * out_dev + k * H*ts * W*ts * 3 (16-byte aligned), pixel [row y][column x][rgb] as Grid.render lays it out: the grid's cells, the
+ * agent's triangle on its cell, and -- highlight != 0 -- the cells the agent sees lightened (the carried object is not drawn).  It
+ * reads the current state and writes nothing but out_dev (not the pixel observations, not the registered render target, no state);
+ * asynchronous on `stream`, ordered behind the handle's previous calls like every state-reading call.  An id outside [0, n) yields an
+ * all-zero frame, never an out-of-bounds read.  BBAI_ERR_STATE without an atlas of that tile size or before the first reset;
+ * BBAI_ERR_ARG for a tile size other than 8 / 16 / 32, count < 0, count > n without ids, or a missing / misaligned out_dev. */
+int bbai_set_grid_atlas(bbai_env* env, int tile_size, const uint8_t* tiles_host, int n_tiles,
+                        const uint8_t* lut_host /* [2][5][256] */);
+int bbai_render_grid(bbai_env* env, int tile_size, int highlight, const int64_t* ids_dev /* NULL = envs 0..count-1 */,
+                     int64_t count, uint8_t* out_dev /* [count][H*ts][W*ts][3] */, void* stream);
+
 /* Mission text as token ids, device-resident (replaces the per-step regex tokenisation of every mission in
  * InstructionsPreprocessor, babyai/utils/format.py:59-75): register a caller-owned uint8[N][72] buffer; the engine
  * rewrites env i's row whenever env i starts a new episode.  Ids follow babyai_amd/missions.py VOCAB, 0 = padding. */
