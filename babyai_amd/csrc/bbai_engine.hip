@@ -1935,6 +1935,110 @@ __global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(Gr
 }
 
 // ------------------------------------------------------------------------------------------
+// k_full_obs : the fully observable encoding, FullyObsWrapper.observation, of listed envs (bbai_observe_full, bbai_step_full)
+// ------------------------------------------------------------------------------------------
+// A frame is uint8[W][H][3] (F = 3 W H bytes, indexed [x][y] as grid.encode() is).  Work item = envs_per_item envs; per item a block
+//   1. copies the H interior rows of each env's appearance plane (H x ES bytes of the live record -- live_rec: both state layouts) into
+//      LDS as dwords, FULL_UNROLL independent loads per lane in flight: ONE memory round trip per item (a load per cell in a loop is one
+//      round trip per trip, and it measured 2.1 TB/s);
+//   2. writes each cell's 3 bytes (bbai_grid.hpp full_cell, on the LDS rows) into the item's frames in LDS at their [x][y] place;
+//   3. stores the item's frames -- ONE contiguous byte range of `out` -- from LDS as 16-byte nontemporal chunks that cross frame boundaries
+//      freely (BossLevel: F = 1452, not a multiple of 16).  envs_per_item is a multiple of 16 / gcd(F, 16), so every item starts 16-byte
+//      aligned and only the end of the whole output can hold a partial chunk: that tail is stored byte by byte.
+// The next item's ids and Hots are loaded into registers while the current one is worked on.  Writes nothing but `out`.  An id outside
+// [0, n) gives an all-zero frame.
+constexpr int FULL_BLOCK = 512;
+constexpr int FULL_LDS = 24576;               // frame bytes of one work item (3 x 25 x 25 x 16 = 30 000 > this: see full_launch)
+constexpr int FULL_APP = 16384;               // appearance rows of one work item
+constexpr int FULL_MAX_ENVS = 128;            // envs per work item
+constexpr int FULL_BPC = 3;                   // persistent blocks per CU (≈ 43 KB of LDS each)
+constexpr int FULL_UNROLL = 8;                // dword loads per lane in flight
+
+struct FullArgs {
+    LevelCfg c;
+    int64_t n;
+    const uint8_t* recs;
+    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
+    int depth;
+    const Hot* hots;
+    const int64_t* ids;          // NULL: envs 0 .. count - 1
+    int64_t count;
+    uint8_t* out;
+    int envs_per_item;
+    int64_t items;
+    uint64_t hw_magic, w_magic, rd_magic;   // multiply-high divides by W H, W and the dwords of an env's rows (grid_div; q < 2^16)
+};
+
+// (env, Hot) of entry k of an item: the Hot as one 16-byte load, zero for an id outside [0, n)
+__device__ __forceinline__ void full_entry(const FullArgs& a, int64_t k, int64_t& env, u32x4& h) {
+    env = a.ids ? a.ids[k] : k;
+    h = u32x4{0u, 0u, 0u, 0u};
+    if (env >= 0 && env < a.n) h = ((const u32x4*)a.hots)[env];
+    else env = -1;
+}
+
+__global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      // (6 waves per SIMD: FULL_BPC blocks per CU)
+    __shared__ __attribute__((aligned(16))) uint8_t s_frames[FULL_LDS];
+    __shared__ __attribute__((aligned(16))) uint32_t s_app[FULL_APP / 4];
+    __shared__ __attribute__((aligned(16))) Hot s_hot[FULL_MAX_ENVS];
+    __shared__ const uint8_t* s_rec[FULL_MAX_ENVS];
+    const int tid = threadIdx.x;
+    const int W = a.c.W, H = a.c.H, HW = W * H, F = 3 * HW, ES = a.c.ES;
+    const int RD = H * ES / 4;                          // dwords of an env's interior rows (ES: a multiple of 4)
+    const int D0 = MARGIN * ES / 4;                     // first dword of the interior rows
+    int64_t env = -1;
+    u32x4 h = {0u, 0u, 0u, 0u};
+    int64_t item = blockIdx.x;
+    if (item < a.items && tid < a.envs_per_item && item * a.envs_per_item + tid < a.count) full_entry(a, item * a.envs_per_item + tid, env, h);
+    for (; item < a.items; item += gridDim.x) {
+        const int64_t first = item * a.envs_per_item;
+        const int ne = (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
+        __syncthreads();                                  // the previous item's frames are stored
+        if (tid < ne) {
+            const uint8_t* rec = env >= 0 ? live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? (int)(h.w >> 24) : 0)      // (h.w >> 24 = slot)
+                                          : nullptr;
+            ((u32x4*)s_hot)[tid] = h;
+            s_rec[tid] = rec;
+        }
+        __syncthreads();
+        for (int k0 = tid; k0 < ne * RD; k0 += FULL_UNROLL * FULL_BLOCK) {
+            uint32_t v[FULL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < FULL_UNROLL; ++u) {
+                const int k = k0 + u * FULL_BLOCK;
+                v[u] = 0;
+                if (k < ne * RD) {
+                    const int e = (int)grid_div((uint32_t)k, a.rd_magic);
+                    const uint8_t* rec = s_rec[e];
+                    if (rec) v[u] = ((const uint32_t*)rec)[D0 + (k - e * RD)];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FULL_UNROLL; ++u)
+                if (k0 + u * FULL_BLOCK < ne * RD) s_app[k0 + u * FULL_BLOCK] = v[u];
+        }
+        {   // the next item's entries, under this item's work
+            const int64_t nf = (item + gridDim.x) * a.envs_per_item;
+            env = -1;
+            if (item + gridDim.x < a.items && tid < a.envs_per_item && nf + tid < a.count) full_entry(a, nf + tid, env, h);
+        }
+        __syncthreads();
+        for (int ci = tid; ci < ne * HW; ci += FULL_BLOCK) {
+            const int e = (int)grid_div((uint32_t)ci, a.hw_magic), cell = ci - e * HW;
+            const int y = (int)grid_div((uint32_t)cell, a.w_magic), x = cell - y * W;
+            uint8_t* o = s_frames + e * F + (x * H + y) * 3;
+            if (s_rec[e]) full_cell_key(((const uint8_t*)s_app)[e * RD * 4 + y * ES + x + MARGIN], s_hot[e], x, y, o);
+            else o[0] = o[1] = o[2] = 0;
+        }
+        __syncthreads();
+        const int bytes = ne * F, chunks = bytes >> 4;
+        uint8_t* const dst = a.out + first * F;           // 16-byte aligned (see above)
+        for (int q = tid; q < chunks; q += FULL_BLOCK) __builtin_nontemporal_store(((const u32x4*)s_frames)[q], (u32x4*)dst + q);
+        for (int b = (chunks << 4) + tid; b < bytes; b += FULL_BLOCK) dst[b] = s_frames[b];      // (the last item only)
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_tokens : mission strings as fixed-vocabulary token ids, produced on the device from the compiled
 // instruction program (grammar: babyai/levels/verifier.py:64-94,248-249,287-288,318-319,366-367,439-440,
 // 480-481,526-527).  Vocabulary ids = babyai_amd/missions.py VOCAB (1..32, 0 = padding).
@@ -3018,6 +3122,65 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
     else render_grid_launch<32>(e, highlight, ids, count, out, s);
     HIP_TRY(hipGetLastError());
+    return call.leave();
+}
+
+}  // extern "C"
+
+// Launch shape: items of as many envs as fit FULL_LDS and FULL_APP (at most FULL_MAX_ENVS), a multiple of 16 / gcd(F, 16) so that every
+// item's range of `out` starts on a 16-byte boundary (the largest grids with an odd F, 25 x 25 at ES 36, would need 16 x 1875 B: refused,
+// no level has one -- BossLevel: 16 envs, 23 232 B of frames, 11 264 B of rows); persistent blocks, FULL_BPC per CU.
+static int full_launch(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    const LevelCfg& c = e->cfg;
+    const int F = 3 * c.W * c.H;
+    int g = 16;
+    while (F % g) g >>= 1;                                // gcd(F, 16)
+    const int align = 16 / g;
+    const int epi = std::min({FULL_MAX_ENVS, FULL_LDS / F, FULL_APP / (c.H * c.ES)}) / align * align;
+    if (epi < 1) { snprintf(g_err, sizeof(g_err), "observe_full: grid %d x %d too large", c.W, c.H); return BBAI_ERR_ARG; }
+    FullArgs a;
+    a.c = c; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
+    a.ids = ids; a.count = count; a.out = out;
+    a.envs_per_item = epi;
+    a.items = (count + epi - 1) / epi;
+    a.hw_magic = (1ull << 32) / (uint32_t)(c.W * c.H) + 1;
+    a.w_magic = (1ull << 32) / (uint32_t)c.W + 1;
+    a.rd_magic = (1ull << 32) / (uint32_t)(c.H * c.ES / 4) + 1;
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * FULL_BPC));
+    hipLaunchKernelGGL(k_full_obs, dim3(blocks), dim3(FULL_BLOCK), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+extern "C" {
+
+int bbai_observe_full(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    if (!e) ARG_FAIL("null handle");
+    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
+    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "observe_full before reset"); return BBAI_ERR_STATE; }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    if (call.rc != BBAI_OK) return call.rc;
+    { int rc = full_launch(e, ids, count, out, s); if (rc != BBAI_OK) return rc; }
+    return call.leave();
+}
+
+int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
+                   uint8_t* dones, int auto_reset, uint8_t* full, void* stream) {
+    if (!e || !actions || !image || !dirs || !rewards || !dones || !full) ARG_FAIL("null handle or buffer");
+    if ((uintptr_t)full & 15) ARG_FAIL("full observation buffer not 16-byte aligned");
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "step before reset"); return BBAI_ERR_STATE; }
+    if (auto_reset && !e->seeded) { snprintf(g_err, sizeof(g_err), "auto-reset step before seed"); return BBAI_ERR_STATE; }
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    if (call.rc != BBAI_OK) return call.rc;
+    { int rc = step_launch(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum); if (rc != BBAI_OK) return rc; }
+    { int rc = full_launch(e, nullptr, e->n, full, s); if (rc != BBAI_OK) return rc; }
     return call.leave();
 }
 

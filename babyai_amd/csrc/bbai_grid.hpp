@@ -8,6 +8,9 @@
 // grid dropped); the agent's own cell is always among them.  The carried object is not drawn.  The visibility comes out of the
 // step's own view pipeline (bbai_view.hpp view_env_cells: an encoded view cell is visible iff its type is not 0).
 //
+// The fully observable encoding (full_cell, k_full_obs) is the same grid without pixels: FullyObsWrapper.observation (restated in
+// oracle/shim/gym_minigrid/wrappers.py:39-56) = grid.encode() indexed [x][y], the agent's cell overwritten with (10 = agent, 0 = red, dir).
+//
 // Atlas lut (tools/gen_grid_atlas.py): lut[(highlight * 5 + agent) * 256 + key], agent = 0 or 1 + dir, key = appearance byte.
 #pragma once
 #include "bbai_types.hpp"
@@ -51,6 +54,26 @@ BB_HD void grid_tile_ids(const LevelCfg& c, const uint8_t* rec, const Hot& h, co
     grid_highlight(c, rec, h, hl);
     for (int y = 0; y < c.H; ++y)
         for (int x = 0; x < c.W; ++x) ids[y * c.W + x] = (uint8_t)grid_tile(c, rec, h, lut, highlight, hl, x, y);
+}
+
+// FullyObsWrapper's 3 bytes of cell (x, y): (type, colour, state) = the appearance byte's fields (engine.py grid_encoding), or
+// (10, 0, dir) on the agent's cell.
+constexpr int FULL_AGENT = 10;
+// full_cell_key: the same from the cell's appearance byte `key` (k_full_obs reads it from rows staged in LDS).
+BB_HD void full_cell_key(int key, const Hot& h, int x, int y, uint8_t* o) {
+    const bool agent = x == h.ax && y == h.ay;
+    o[0] = (uint8_t)(agent ? FULL_AGENT : key & 7);
+    o[1] = (uint8_t)(agent ? 0 : (key >> 3) & 7);
+    o[2] = (uint8_t)(agent ? (h.dir & 3) : key >> 6);
+}
+BB_HD void full_cell(const LevelCfg& c, const uint8_t* rec, const Hot& h, int x, int y, uint8_t* o) {
+    full_cell_key(rec[e_index(c, x, y)], h, x, y, o);
+}
+
+// The whole frame of one env: out[(x * H + y) * 3 + k].
+BB_HD void full_frame(const LevelCfg& c, const uint8_t* rec, const Hot& h, uint8_t* out) {
+    for (int y = 0; y < c.H; ++y)
+        for (int x = 0; x < c.W; ++x) full_cell(c, rec, h, x, y, out + (x * c.H + y) * 3);
 }
 
 }  // namespace bbai

@@ -38,6 +38,14 @@ class EngineError(RuntimeError):
     pass
 
 
+def check_tile_size(tile_size):
+    """RGBImgObsWrapper's tile size, checked before any device work: the engine has atlases for GRID_TILE_SIZES only."""
+    ts = int(tile_size)
+    if ts != tile_size or ts not in GRID_TILE_SIZES:
+        raise ValueError("tile_size %r: the engine has atlases for %s only (tools/gen_grid_atlas.py makes them)" % (tile_size, GRID_TILE_SIZES))
+    return ts
+
+
 def load_library():
     """dlopen the HIP engine; raises EngineError (never falls back to a CPU path)."""
     global _lib
@@ -69,6 +77,9 @@ def load_library():
     if hasattr(lib, "bbai_render_grid"):
         lib.bbai_set_grid_atlas.argtypes = [P, I32, P, I32, P]
         lib.bbai_render_grid.argtypes = [P, I32, I32, P, I64, P, P]
+    if hasattr(lib, "bbai_observe_full"):
+        lib.bbai_observe_full.argtypes = [P, P, I64, P, P]
+        lib.bbai_step_full.argtypes = [P, P, P, P, P, P, P, I32, P, P]
     lib.bbai_set_token_buffer.argtypes = [P, P]
     lib.bbai_export_state.argtypes = [P, I64, I64, P, P, P]
     lib.bbai_import_state.argtypes = [P, I64, I64, P, P, P]
@@ -107,7 +118,7 @@ EXPORTED_SYMBOLS = (
     "bbai_checkpoint_bytes", "bbai_checkpoint_save", "bbai_checkpoint_load", "bbai_profile", "bbai_profile_read", "bbai_gae", "bbai_tap",
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
-    "bbai_set_render_target", "bbai_render_invalidate", "bbai_set_grid_atlas", "bbai_render_grid",
+    "bbai_set_render_target", "bbai_render_invalidate", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
 )
 
 
@@ -184,15 +195,22 @@ class BatchedBabyAIEnv(object):
                  succeeds only on a `done` action right after the step that completed it; include/bbai.h
                  bbai_set_done_actions).  None (default) = as the reference decides it: on iff that environment variable is
                  non-empty; True / False force it for this batch
+    full_obs : the fully observable wrappers instead of the 7x7 view: obs image = FullyObsWrapper's uint8[N, W, H, 3] (`full`; pixel=False)
+                 or RGBImgObsWrapper's uint8[N, H*tile_size, W*tile_size, 3] (pixel=True: render('rgb_array', highlight=False)); the
+                 obs dict then has no use for 'direction', which the list-of-dicts adapters leave out as the wrappers do.  The 7x7
+                 `image`, `direction`, rewards and dones are computed and kept as without it
+    tile_size : RGBImgObsWrapper's tile size with full_obs=True, pixel=True: 8, 16 or 32
     validate_actions : check every step()'s actions on the device first and raise AssertionError("unknown action") like
                  the reference (gym_minigrid MiniGridEnv.step) instead of treating bytes 8..255 as `done` (include/bbai.h);
                  costs one reduction and a host synchronisation per step, so it is off by default
     """
 
     def __init__(self, env_id, num_envs, device="cuda:0", seeds=None, pixel=False, auto_reset=True, validate_actions=False,
-                 done_actions=None):
+                 done_actions=None, full_obs=False, tile_size=8):
         import torch
         self.torch = torch
+        self.full_obs = bool(full_obs)
+        self.tile_size = check_tile_size(tile_size) if self.full_obs and pixel else int(tile_size)
         if not torch.cuda.is_available():
             raise EngineError("no ROCm GPU visible: the batched engine has no CPU path")
         self.lib = load_library()
@@ -221,7 +239,12 @@ class BatchedBabyAIEnv(object):
             self.reward64 = torch.zeros((n,), dtype=torch.float64, device=self.device)
             self.done = torch.zeros((n,), dtype=torch.uint8, device=self.device)
             self.pixels = None
-            if self.pixel:
+            self.full = None        # full_obs: the observation image (observe_full)
+            if self.full_obs:
+                c, ts = self.cfg, self.tile_size
+                shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
+                self.full = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+            elif self.pixel:
                 self.pixels = torch.zeros((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
                 atlas = np.load(ATLAS_PATH)
                 tiles = np.ascontiguousarray(atlas["tiles"], dtype=np.uint8)
@@ -273,7 +296,13 @@ class BatchedBabyAIEnv(object):
 
     def _obs(self, rendered=False):
         img = self.image
-        if self.pixel and rendered:
+        if self.full_obs:
+            if not rendered:
+                ev = self._ev_begin()
+                self.observe_full()
+                self._ev_end("full_obs", ev)
+            img = self.full
+        elif self.pixel and rendered:
             img = self.pixels
         elif self.pixel:
             ev = self._ev_begin()
@@ -312,26 +341,48 @@ class BatchedBabyAIEnv(object):
                 lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
             _check(self.lib, self.lib.bbai_set_grid_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_grid_atlas")
             self._grid_atlases.add(ts)
-        ids_ptr = None
+        k, ids_ptr = self._id_list(ids)
+        out = self._frames_out(out, (k, self.cfg.H * ts, self.cfg.W * ts, 3))
+        _check(self.lib, self.lib.bbai_render_grid(self.handle, ts, 1 if highlight else 0, ids_ptr, k, out.data_ptr() if k else None,
+                                                    self._stream()), "bbai_render_grid")
+        return out
+
+    def _id_list(self, ids):
+        """(k, device pointer or None) of an env id list: None = every env; an int sequence or an int64 device tensor."""
+        torch = self.torch
         if ids is None:
-            k = self.num_envs
-        else:
-            if not isinstance(ids, torch.Tensor):
-                ids = torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1), device=self.device)
-            if ids.dtype != torch.int64 or ids.device != self.device or ids.dim() != 1:
-                raise ValueError("ids: int64[k] on %s" % (self.device,))
-            ids = ids.contiguous()
-            self._grid_ids = ids            # keep alive until the launch is consumed
-            k = int(ids.shape[0])
-            ids_ptr = ids.data_ptr()
-        shape = (k, self.cfg.H * ts, self.cfg.W * ts, 3)
+            return self.num_envs, None
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1), device=self.device)
+        if ids.dtype != torch.int64 or ids.device != self.device or ids.dim() != 1:
+            raise ValueError("ids: int64[k] on %s" % (self.device,))
+        ids = ids.contiguous()
+        self._grid_ids = ids            # keep alive until the launch is consumed
+        return int(ids.shape[0]), ids.data_ptr()
+
+    def _frames_out(self, out, shape):
+        torch = self.torch
         if out is None:
             with torch.cuda.device(self.dev_index):
                 out = torch.empty(shape, dtype=torch.uint8, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
             raise ValueError("out: contiguous uint8%s on %s" % (list(shape), self.device))
-        _check(self.lib, self.lib.bbai_render_grid(self.handle, ts, 1 if highlight else 0, ids_ptr, k, out.data_ptr() if k else None,
-                                                    self._stream()), "bbai_render_grid")
+        return out
+
+    def observe_full(self, ids=None, out=None):
+        """The full observation of envs `ids` (None = every env; else an int sequence or an int64 device tensor, any order, repeats
+        allowed) from the current state, asynchronous on the current stream: FullyObsWrapper's uint8[k, W, H, 3] (include/bbai.h
+        bbai_observe_full) -- or, in a full_obs pixel batch, RGBImgObsWrapper's uint8[k, H*ts, W*ts, 3] (render_grid(ids, tile_size,
+        highlight=False)).  ids = out = None in a full_obs batch refreshes `full`, the observation step() returns (after load_checkpoint
+        or import_state, which do not carry it).  An id outside [0, num_envs) gives an all-zero frame."""
+        if self.full_obs and ids is None and out is None:
+            out = self.full
+        if self.full_obs and self.pixel:
+            return self.render_grid(ids, tile_size=self.tile_size, highlight=False, out=out)
+        k, ids_ptr = self._id_list(ids)
+        out = self._frames_out(out, (k, self.cfg.W, self.cfg.H, 3))
+        _check(self.lib, self.lib.bbai_observe_full(self.handle, ids_ptr, k, out.data_ptr() if k else None, self._stream()),
+               "bbai_observe_full")
         return out
 
     def render_invalidate(self):
@@ -370,7 +421,14 @@ class BatchedBabyAIEnv(object):
             raise ValueError("need %d actions" % self.num_envs)
         self._actions = actions     # keep alive until the launch is consumed
         ev = self._ev_begin()
-        if self.pixel and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
+        if self.full_obs and not self.pixel and self.kernel_events is None:
+            # FullyObsWrapper's step: transition + the full observation of every env as ONE call (include/bbai.h bbai_step_full)
+            _check(self.lib, self.lib.bbai_step_full(self.handle, actions.data_ptr(), self.image.data_ptr(),
+                                                      self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
+                                                      self.done.data_ptr(), 1 if self.auto_reset else 0, self.full.data_ptr(),
+                                                      self._stream()), "bbai_step_full")
+            return self._obs(rendered=True), self.reward, self.done, {}
+        if self.pixel and not self.full_obs and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
             # the wrapped env's step: transition + render as ONE call (include/bbai.h bbai_step_render)
             _check(self.lib, self.lib.bbai_step_render(self.handle, actions.data_ptr(), self.image.data_ptr(),
                                                         self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
@@ -414,11 +472,14 @@ class BatchedBabyAIEnv(object):
         self._actions = actions
         _check(self.lib, self.lib.bbai_rollout(self.handle, T, actions.data_ptr(), self.image.data_ptr(), self.direction.data_ptr(),
                                                 self.reward.data_ptr(), self.reward64.data_ptr(), self.done.data_ptr(), 1 if self.auto_reset else 0,
-                                                self.pixels.data_ptr() if self.pixel else None, ctypes.byref(log) if log is not None else None,
+                                                self.pixels.data_ptr() if self.pixels is not None else None, ctypes.byref(log) if log is not None else None,
                                                 self._stream()), "bbai_rollout")
+        if self.full_obs:
+            self.observe_full()          # the last step's full observation (the tap log keeps its 7x7 rows)
         self._obs_version += 1
         self._missions = Missions(self)
-        return {"image": self.pixels if self.pixel else self.image, "direction": self.direction, "mission": self._missions}
+        image = self.full if self.full_obs else self.pixels if self.pixel else self.image
+        return {"image": image, "direction": self.direction, "mission": self._missions}
 
     # ---- state access -------------------------------------------------------------------
     def programs(self, first=0, count=None):

@@ -91,7 +91,9 @@ class TensorObssPreprocessor(object):
         """trim=True pads to the longest mission of the batch like the reference (one device->host read of the length);
         trim=False uses the level's fixed width (no synchronisation)."""
         torch = self.env.torch
-        obs = obs if obs is not None else {"image": self.env.pixels if self.env.pixel else self.env.image}
+        if obs is None:
+            env = self.env
+            obs = {"image": env.full if getattr(env, "full_obs", False) else env.pixels if env.pixel else env.image}
         image = obs["image"].to(torch.float32)                  # RawImagePreprocessor: float image, no scaling
         tok = self.tokens
         width = max(int((tok != 0).sum(dim=1).max().item()), 1) if trim else self.width

@@ -17,8 +17,8 @@ the no-edit route (`babyai_amd.integrate.install()`).
 """
 import numpy as np
 
-from .engine import BatchedBabyAIEnv
-from .levels import LEVELS, level_name
+from .engine import BatchedBabyAIEnv, check_tile_size
+from .levels import LEVELS, level_name, make_cfg
 
 
 class _Box(object):
@@ -48,13 +48,27 @@ class _Discrete(object):
         self.n = n
 
 
-def _spaces(pixel):
-    return _DictSpace({"image": _Box((56, 56, 3) if pixel else (7, 7, 3))}), _Discrete(7)
+def _spaces(pixel, full_obs=False, env_id=None, tile_size=8):
+    """observation_space['image'] has the shape of the returned image: RGBImgPartialObsWrapper (56, 56, 3) or the 7x7 view; with
+    full_obs FullyObsWrapper's (W, H, 3) or RGBImgObsWrapper's (H * tile_size, W * tile_size, 3) -- not square on 19 levels."""
+    if full_obs:
+        c = make_cfg(env_id)
+        shape = (c.H * tile_size, c.W * tile_size, 3) if pixel else (c.W, c.H, 3)
+    else:
+        shape = (56, 56, 3) if pixel else (7, 7, 3)
+    return _DictSpace({"image": _Box(shape)}), _Discrete(7)
+
+
+def _full_args(full_obs, pixel, tile_size):
+    """(full_obs, tile_size) checked before any device work: a tile size without an atlas raises ValueError here."""
+    full_obs = bool(full_obs)
+    return full_obs, check_tile_size(tile_size) if full_obs and pixel else int(tile_size)
 
 
 class ObsList(object):
     """`list[dict]` view over the batched observation: item i is
-    {'image': np.uint8[7,7,3] (or [56,56,3]), 'direction': int, 'mission': str}.
+    {'image': np.uint8[7,7,3] (or [56,56,3]), 'direction': int, 'mission': str} -- without 'direction' when the batch is wrapped
+    in a pixel or fully observable wrapper (their dicts hold image and mission only).
     Images are copied to the host once per step (one D2H of the whole batch), dicts are built lazily."""
 
     def __init__(self, image_host, direction_host, missions, pixel):
@@ -67,7 +81,7 @@ class ObsList(object):
         if isinstance(i, slice):
             return [self[k] for k in range(*i.indices(len(self)))]
         d = {"image": self._image[i], "mission": self._missions[i]}
-        if not self._pixel:           # the pixel wrapper's dict has no 'direction' key
+        if not self._pixel:           # the pixel / full wrappers' dicts have no 'direction' key
             d["direction"] = int(self._dir[i])
         return d
 
@@ -83,13 +97,18 @@ class _EnvView(object):
 
 
 class _VecBase(object):
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, engine=None):
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, engine=None, full_obs=False, tile_size=8):
         """`engine`: an object with BatchedBabyAIEnv's tensor protocol to run on instead of building one (tests put the
-        CPU oracle there to drive the reference's consumers through this adapter code without a GPU)."""
-        self.engine = engine if engine is not None else BatchedBabyAIEnv(env_id, num_envs, device=device, pixel=pixel, auto_reset=auto_reset)
+        CPU oracle there to drive the reference's consumers through this adapter code without a GPU).  `full_obs` / `tile_size`:
+        FullyObsWrapper (pixel=False) or RGBImgObsWrapper(env, tile_size) (pixel=True) instead of the 7x7 view (BatchedBabyAIEnv)."""
+        full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
+        if engine is None:
+            engine = BatchedBabyAIEnv(env_id, num_envs, device=device, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size)
+        self.engine = engine
         self.num_envs = num_envs
         self.pixel = pixel
-        self.observation_space, self.action_space = _spaces(pixel)
+        self.full_obs = full_obs
+        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size)
         if seeds is not None:
             self.seed(seeds)
 
@@ -109,7 +128,7 @@ class _VecBase(object):
 
     def _obs_list(self, obs):
         # everything an obs dict may be asked for later is copied out now: images, directions and the mission programs
-        return ObsList(obs["image"].cpu().numpy(), obs["direction"].cpu().numpy(), obs["mission"].snapshot(), self.pixel)
+        return ObsList(obs["image"].cpu().numpy(), obs["direction"].cpu().numpy(), obs["mission"].snapshot(), self.pixel or self.full_obs)
 
     def reset(self):
         return self._obs_list(self.engine.reset())
@@ -142,16 +161,18 @@ class BatchedParallelEnv(_VecBase):
     """`ParallelEnv` protocol (penv.py:18-59): auto-reset -- when an env finishes, the returned obs is the
     first obs of its next episode while reward/done belong to the terminal step (penv.py:8-11,49-50)."""
 
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None):
-        super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=True, seeds=seeds, engine=engine)
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8):
+        super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=True, seeds=seeds, engine=engine, full_obs=full_obs,
+                         tile_size=tile_size)
 
 
 class BatchedManyEnvs(_VecBase):
     """`ManyEnvs` protocol (evaluate.py:58-81): no auto-reset; a finished env re-emits its last
     (obs, reward, done, info) until the next reset()."""
 
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None):
-        super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=False, seeds=seeds, engine=engine)
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8):
+        super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=False, seeds=seeds, engine=engine, full_obs=full_obs,
+                         tile_size=tile_size)
         self.done = [False] * num_envs
 
     def reset(self):
@@ -191,10 +212,12 @@ class SingleEnv(object):
 
     actions = Actions
 
-    def __init__(self, env_id, device="cuda:0", pixel=False, seed=None):
-        self.engine = BatchedBabyAIEnv(env_id, 1, device=device, pixel=pixel, auto_reset=False)
+    def __init__(self, env_id, device="cuda:0", pixel=False, seed=None, full_obs=False, tile_size=8):
+        full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
+        self.engine = BatchedBabyAIEnv(env_id, 1, device=device, pixel=pixel, auto_reset=False, full_obs=full_obs, tile_size=tile_size)
         self.pixel = pixel
-        self.observation_space, self.action_space = _spaces(pixel)
+        self.full_obs = full_obs
+        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size)
         self.step_count = 0
         self.mission = self.surface = ""
         if seed is not None:
@@ -206,7 +229,7 @@ class SingleEnv(object):
 
     def _one(self, obs):
         d = {"image": obs["image"][0].cpu().numpy(), "mission": obs["mission"][0]}
-        if not self.pixel:
+        if not (self.pixel or self.full_obs):
             d["direction"] = int(obs["direction"][0])
         self.mission = self.surface = d["mission"]
         return d
@@ -264,9 +287,11 @@ class SingleEnv(object):
         self.engine.close()
 
 
-def make(env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None):
-    """Batched twin of `gym.make(env_id)` (ids registered at babyai/levels/levelgen.py:467-493).
+def make(env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, full_obs=False, tile_size=8):
+    """Batched twin of `gym.make(env_id)` (ids registered at babyai/levels/levelgen.py:467-493), optionally wrapped in
+    FullyObsWrapper (full_obs=True) or RGBImgObsWrapper(env, tile_size) (full_obs=True, pixel=True).
     Returns the tensor-level `BatchedBabyAIEnv`."""
     if level_name(env_id) not in LEVELS:
         raise KeyError("unknown / unsupported level id %r" % (env_id,))
-    return BatchedBabyAIEnv(env_id, num_envs, device=device, seeds=seeds, pixel=pixel, auto_reset=auto_reset)
+    full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
+    return BatchedBabyAIEnv(env_id, num_envs, device=device, seeds=seeds, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size)

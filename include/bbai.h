@@ -144,6 +144,21 @@ int bbai_set_grid_atlas(bbai_env* env, int tile_size, const uint8_t* tiles_host,
 int bbai_render_grid(bbai_env* env, int tile_size, int highlight, const int64_t* ids_dev /* NULL = envs 0..count-1 */,
                      int64_t count, uint8_t* out_dev /* [count][H*ts][W*ts][3] */, void* stream);
 
+/* The fully observable encoding: FullyObsWrapper.observation (gym_minigrid wrappers.py; restated in
+ * oracle/shim/gym_minigrid/wrappers.py:39-56) -- grid.encode() of the whole W x H grid, indexed [x][y], cell = (type, colour,
+ * state), the agent's cell overwritten with (10 = agent, 0 = red, agent_dir) -- on the device.
+ * bbai_observe_full (replaces FullyObsWrapper(env).observation(obs)['image'] of the current state) writes frame k = env ids_dev[k]
+ * (int64 device array; NULL = envs 0 .. count - 1) into out_dev + k * W*H*3 (16-byte aligned).  It reads the current state and writes
+ * nothing but out_dev; asynchronous on `stream`, ordered behind the handle's previous calls.  An id outside [0, n) yields an all-zero
+ * frame.  BBAI_ERR_STATE before the first reset; BBAI_ERR_ARG for count < 0, count > n without ids, or a missing / misaligned out_dev.
+ * bbai_step_full (replaces FullyObsWrapper(env).step for every env): bbai_step, then the full observation of EVERY env of the state the
+ * step leaves behind -- a finished env's next episode under auto_reset, a frozen env's final state without -- into
+ * full_dev[n][W][H][3] (16-byte aligned), as ONE call.  image_dev (the 7x7 view) is written as by bbai_step. */
+int bbai_observe_full(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..count-1 */, int64_t count,
+                      uint8_t* out_dev /* [count][W][H][3] */, void* stream);
+int bbai_step_full(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_dev, uint8_t* dir_dev, float* reward_dev,
+                   double* reward64_dev, uint8_t* done_dev, int auto_reset, uint8_t* full_dev /* [n][W][H][3] */, void* stream);
+
 /* Mission text as token ids, device-resident (replaces the per-step regex tokenisation of every mission in
  * InstructionsPreprocessor, babyai/utils/format.py:59-75): register a caller-owned uint8[N][72] buffer; the engine
  * rewrites env i's row whenever env i starts a new episode.  Ids follow babyai_amd/missions.py VOCAB, 0 = padding. */
