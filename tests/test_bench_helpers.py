@@ -107,3 +107,18 @@ def test_judged_line_is_small():
 def test_full_record_goes_to_a_side_file(tmp_path):
     path = bench.write_full_record(_synthetic_record(2), str(tmp_path / "sub" / "full.json"))
     assert path == str(tmp_path / "sub" / "full.json") and json.load(open(path))["n_gpus"] == 1
+
+
+def test_plain_run_line_carries_the_headline_alone():
+    """Without --full a run measures the headline and nothing else: its line has the same headline fields, and nulls where the roofline,
+    the parity replay, the CPU baseline and the other configs would be."""
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    rec = _synthetic_record(0)
+    for k in ("roofline", "parity", "cpu_baseline", "configs", "scaling_implied"):
+        rec[k] = None
+    line = json.loads(bench.compact_line(rec, None))
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "scaling"):
+        assert line[k] == rec[k], k
+    assert abs(line["value"] - rec["value"]) / rec["value"] < 1e-6 and abs(line["ms_per_step"] - rec["ms_per_step"]) / rec["ms_per_step"] < 1e-6
+    for k in ("roofline", "parity", "cpu_baseline", "configs", "scaling_implied", "kernel_avg_ms", "full_record"):
+        assert line[k] is None, k

@@ -18,7 +18,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["--level", "GoToLocal", "--no-pixel", "--steps", "16", "--warmup", "4", "--min-seconds", "30", "--max-blocks", "4",
-          "--no-cpu-baseline", "--prewarm-seconds", "0", "--parity-envs", "64"]
+          "--no-cpu-baseline", "--prewarm-seconds", "0", "--parity-envs", "64", "--full"]
 
 
 def _free_port():

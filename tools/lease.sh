@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 export TMPDIR=/tmp
-B="python $REPO/bench.py --steps 20 --warmup 5"
+B="python $REPO/bench.py --full --steps 20 --warmup 5"
 export BBAI_BENCH_LINE=full     # every job parses the FULL record from stdout; `judged` / `rejudged` run the driver's command as the driver does
 
 suite() {            # the GPU test suite (optionally: -k expression)
@@ -57,12 +57,12 @@ pmc() {              # FETCH_SIZE / WRITE_SIZE, one pass each, no other tracing 
     find $OUT -name "*kernel_trace.csv" -size +20M -delete
 }
 bench() {            # one BASELINE config as its own line: bench:C2 [extra args]
-    cd /tmp && timeout 600 python $REPO/bench.py --config $1 --no-extra-configs ${@:2} > $OUT/bench_$1.json 2>> $OUT/bench.err
+    cd /tmp && timeout 600 python $REPO/bench.py --full --config $1 --no-extra-configs ${@:2} > $OUT/bench_$1.json 2>> $OUT/bench.err
     python $REPO/tools/summarize_profile.py --line $OUT/bench_$1.json
 }
 benchenv() {         # one BASELINE config under an environment setting: benchenv:BBAI_GATE_STRICT=1:C4[:extra bench args]
     local kv=$1 cfg=$2; shift 2
-    cd /tmp && env ${kv//,/ } timeout 600 python $REPO/bench.py --config $cfg --no-extra-configs --no-cpu-baseline ${@} > $OUT/bench_${cfg}_$kv.json 2>> $OUT/bench.err      # (several settings: A=1,B=2)
+    cd /tmp && env ${kv//,/ } timeout 600 python $REPO/bench.py --full --config $cfg --no-extra-configs --no-cpu-baseline ${@} > $OUT/bench_${cfg}_$kv.json 2>> $OUT/bench.err      # (several settings: A=1,B=2)
     python - <<PY
 import json
 d = json.loads(open("$OUT/bench_${cfg}_$kv.json").read().strip().splitlines()[-1])
@@ -95,7 +95,7 @@ ab() {               # tools/ab.py presets
 sq() {               # SQ counter pass over the headline bench: where the waves of k_render / k_step spend their cycles
     cd /tmp && rm -rf $OUT/pmc_sq
     timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU \
-        --kernel-trace --output-format csv -d $OUT/pmc_sq -o boss -- python $REPO/bench.py --steps 8 --warmup 2 --no-cpu-baseline --parity-envs 0 --min-seconds 0 --no-extra-configs ${@} > $OUT/rocprof_sq.log 2>&1
+        --kernel-trace --output-format csv -d $OUT/pmc_sq -o boss -- python $REPO/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --parity-envs 0 --min-seconds 0 --no-extra-configs ${@} > $OUT/rocprof_sq.log 2>&1
     python - <<PY | tee $OUT/sq_counters.txt
 import csv, glob, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -255,7 +255,7 @@ lib() {              # the same ab spec under two engine builds, alternated twic
 loopab() {           # bench.py's block loop: one bbai_rollout call per block against per-step calls from Python, per config, alternated twice
     cd /tmp
     for rep in 1 2; do for cfg in C2 C3 C4-shard C4 C5; do for mode in "" "--rollout-entry"; do
-        timeout 300 python $REPO/bench.py --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 64 --min-seconds 0.4 $mode 2>> $OUT/loopab.err | python -c "
+        timeout 300 python $REPO/bench.py --full --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 64 --min-seconds 0.4 $mode 2>> $OUT/loopab.err | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'config': '$cfg', 'loop': 'bbai_rollout' if '$mode' else 'python', 'ms_per_step': round(d['ms_per_step'], 5), 'value': d['value'], 'kernels': d['roofline']['kernel_avg_ms'], 'parity': (d['parity'] or {}).get('mismatches_all_ranks')}))" | tee -a $OUT/loop_ab.jsonl
@@ -265,7 +265,7 @@ profcfg() {          # profcfg:<config>[:<bench args>] -- the evidence set of ON
                      # FETCH_SIZE and WRITE_SIZE passes (each on its own: gpurun refuses counter + trace-domain mixes), and the SQ pass; condensed by
                      # tools/summarize_profile.py into profiles/<tag>/ and profiles/pmc_latest.json (one entry per workload)
     local cfg=$1; shift
-    local B1="python $REPO/bench.py --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.25 --max-blocks 8 --steps 192 $@"      # (192: whole look-ahead windows of 16 / 64 / 96 ticks -- every k_step_ticks launch of a block takes the same number of steps)
+    local B1="python $REPO/bench.py --full --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.25 --max-blocks 8 --steps 192 $@"      # (192: whole look-ahead windows of 16 / 64 / 96 ticks -- every k_step_ticks launch of a block takes the same number of steps)
     cd /tmp && rm -rf $OUT/stats_$cfg $OUT/pmc_fetch_$cfg $OUT/pmc_write_$cfg $OUT/pmc_sq_$cfg
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$cfg -o t -- $B1 > $OUT/bench_${cfg}_under_rocprof.json 2> $OUT/rocprof_stats_$cfg.log
     timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch_$cfg -o t -- $B1 > /dev/null 2> $OUT/rocprof_fetch_$cfg.log
@@ -278,7 +278,7 @@ profcfg() {          # profcfg:<config>[:<bench args>] -- the evidence set of ON
 }
 benchlib() {         # one BASELINE config on another engine build: benchlib:<name>:<path to .so relative to the repo>:<config>[:bench args] -> bench_<config>_<name>.json
     local name=$1 so=$2 cfg=$3; shift 3
-    cd /tmp && BBAI_ENGINE_LIB=$REPO/$so timeout 600 python $REPO/bench.py --config $cfg --no-extra-configs --no-cpu-baseline ${@} > $OUT/bench_${cfg}_$name.json 2>> $OUT/bench.err
+    cd /tmp && BBAI_ENGINE_LIB=$REPO/$so timeout 600 python $REPO/bench.py --full --config $cfg --no-extra-configs --no-cpu-baseline ${@} > $OUT/bench_${cfg}_$name.json 2>> $OUT/bench.err
     python - <<PY
 import json
 d = json.loads(open("$OUT/bench_${cfg}_$name.json").read().strip().splitlines()[-1])
@@ -289,7 +289,7 @@ PY
 }
 tracecfg() {         # rocprofv3 kernel trace of one BASELINE config (tracecfg:C2): launch gaps on the small shards
     cd /tmp && rm -rf $OUT/trace_$1
-    timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$1 -o t -- python $REPO/bench.py --config $1 --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.2 --steps 256 --warmup 16 > $OUT/trace_$1.json 2> $OUT/trace_$1.log
+    timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$1 -o t -- python $REPO/bench.py --full --config $1 --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.2 --steps 256 --warmup 16 > $OUT/trace_$1.json 2> $OUT/trace_$1.log
     python - <<PY | tee $OUT/trace_$1_gaps.txt
 import csv, glob
 rows = []
@@ -317,7 +317,7 @@ timeline() {         # timeline:<config>:<A=1,B=2 settings or ->[:<bench args>] 
     local cfg=$1 kv=$2; shift 2
     local name=timeline_${cfg}_${kv}
     cd /tmp && rm -rf $OUT/$name
-    env ${kv//,/ } DUMMY=1 timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/$name -o t -- python $REPO/bench.py --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.2 --max-blocks 6 $@ > $OUT/$name.json 2> $OUT/$name.log
+    env ${kv//,/ } DUMMY=1 timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/$name -o t -- python $REPO/bench.py --full --config $cfg --no-extra-configs --no-cpu-baseline --parity-envs 0 --min-seconds 0.2 --max-blocks 6 $@ > $OUT/$name.json 2> $OUT/$name.log
     python - <<PY | tee $OUT/$name.txt
 import csv, glob
 rows = []
