@@ -205,6 +205,8 @@ struct bbai_env {
     int render_delta_sched;    // option "render_delta_sched": 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
     int render_delta_tpb;      // option "render_delta_tpb": 512 (default, also for 0) or 1024 threads per delta render block
     int render_delta_bpc;      // option "render_delta_bpc": delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
+    uint64_t* rt_dmask;   // [n] the dirty-cell mask of every env, left by k_step for the store-only render (k_render_dstore); allocated with rt_shadow
+    int render_delta_from_step;   // option "render_delta_from_step": 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
     int done_action_enum; // option "done_action_enum": done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
     int consume_fused;    // BBAI_CONSUME_FUSED / option "consume_fused": -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
@@ -910,19 +912,101 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
         }
     }
 }
+// The dirty cells of a step whose render is a delta render of the registered target (render_launch: k_render_dstore).  k_step's tail, after
+// step_body has stored the block's rows: lanes over (env, cell) of the block's 64 rows, 16 cells per lane and chunk -- the chunk's 16 shadow
+// bytes in one coalesced 16-byte load, its 48 encoding bytes in three 16-byte LDS reads (a row is 49 cells at the output pitch of 147 =
+// 3 x 49: cell b of the block is LDS bytes [3 b, 3 b + 3)) -- the new tile id of every cell (the same s_lut lookup as k_render, the agent's
+// table for AGENT_CELL), the changed ones written back to the shadow (the chunk whole, where one differs), and per env a 64-bit dirty mask
+// (bit = cell) into `dmask`: gathered by LDS atomics in the first 512 bytes of the row area, which nothing reads any more.
+constexpr int CELLS = VIEW * VIEW;
+constexpr int AGENT_CELL = 3 * VIEW + 6;
+constexpr int DIRTY_CHUNKS = (STEP_BLOCK * CELLS / 16 + STEP_BLOCK - 1) / STEP_BLOCK;      // 16-byte shadow chunks per lane: 196 per block -> 4
+static_assert(STEP_BLOCK * CELLS % 16 == 0 && OBS_BYTES == 3 * CELLS, "a block's shadow rows are whole 16-byte chunks; a row is 3 bytes per cell");
+__device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __restrict__ shadow /* [n][49] */, uint64_t* __restrict__ dmask /* [n] */,
+                                           const uint8_t* __restrict__ lut, uint8_t* const s_rows, uint8_t* const s_lut, const int lane) {
+    const int nb = n - env0 < STEP_BLOCK ? (int)(n - env0) : STEP_BLOCK;
+    const int nbytes = nb * CELLS;
+    uint8_t* const sh = shadow + env0 * CELLS;                   // (16-byte aligned: env0 is a multiple of 64)
+    const uint2 lv = ((const uint2*)lut)[lane];
+    uint32_t old[DIRTY_CHUNKS][4];
+#pragma unroll
+    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
+        const int v = lane + k * STEP_BLOCK;
+        old[k][0] = old[k][1] = old[k][2] = old[k][3] = 0;
+        if (16 * v + 16 <= nbytes) {
+            const u32x4 w = ((const u32x4*)sh)[v];
+            old[k][0] = w[0]; old[k][1] = w[1]; old[k][2] = w[2]; old[k][3] = w[3];
+        } else {                                                 // (the last, partial block's last chunk)
+            for (int i = 0; i < 16 && 16 * v + i < nbytes; ++i) old[k][i >> 2] |= (uint32_t)sh[16 * v + i] << (8 * (i & 3));
+        }
+    }
+    *(uint2*)(s_lut + 8 * lane) = lv;
+    __syncthreads();                                             // (one wave: the lut's LDS writes before its reads)
+    uint64_t ma[DIRTY_CHUNKS], mb[DIRTY_CHUNKS];                 // the chunk's dirty cells in its first env, and in the next one
+#pragma unroll
+    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
+        const int v = lane + k * STEP_BLOCK;
+        ma[k] = mb[k] = 0;
+        if (16 * v >= nbytes) continue;
+        const u32x4* enc = (const u32x4*)(s_rows + 48 * v);
+        const u32x4 q0 = enc[0], q1 = enc[1], q2 = enc[2];
+        const uint32_t ew[12] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2[0], q2[1], q2[2], q2[3]};
+        const int ea = 16 * v / CELLS;
+        int cell = 16 * v - ea * CELLS;
+        bool second = false;
+        uint32_t nw[4] = {0, 0, 0, 0};
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            if (16 * v + i < nbytes) {
+                const int o0 = (ew[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 0xFF;
+                const int o1 = (ew[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 0xFF;
+                const int o2 = (ew[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 0xFF;
+                const int key = o0 | (o1 << 3) | (o2 << 6);
+                const uint32_t id = s_lut[(cell == AGENT_CELL ? 256 : 0) + key];
+                nw[i >> 2] |= id << (8 * (i & 3));
+                if (id != ((old[k][i >> 2] >> (8 * (i & 3))) & 0xFFu)) {
+                    any = true;
+                    if (second) mb[k] |= 1ull << cell; else ma[k] |= 1ull << cell;
+                }
+            }
+            if (++cell == CELLS) { cell = 0; second = true; }
+        }
+        if (any) {
+            if (16 * v + 16 <= nbytes) { u32x4 w = {nw[0], nw[1], nw[2], nw[3]}; ((u32x4*)sh)[v] = w; }
+            else for (int i = 0; i < 16 && 16 * v + i < nbytes; ++i) sh[16 * v + i] = (uint8_t)(nw[i >> 2] >> (8 * (i & 3)));
+        }
+    }
+    __syncthreads();                                             // every lane has read its rows: their first 512 bytes take the masks
+    unsigned long long* const s_dm = (unsigned long long*)s_rows;
+    s_dm[lane] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
+        const int ea = 16 * (lane + k * STEP_BLOCK) / CELLS;
+        if (ma[k]) atomicOr(s_dm + ea, (unsigned long long)ma[k]);
+        if (mb[k]) atomicOr(s_dm + ea + 1, (unsigned long long)mb[k]);
+    }
+    __syncthreads();
+    if (lane < nb) dmask[env0 + lane] = s_dm[lane];
+}
+
 // What a step launch is given: the kernels' one argument (the kernarg segment IS this struct).
 struct StepArgs {
     LevelCfg c; int64_t n; uint8_t* recs; Hot* hots; uint64_t* stales; uint32_t* vheads; uint64_t* vsets; const uint8_t* actions; uint8_t* image; uint8_t* dirs;
     float* rewards; double* rewards64; uint8_t* dones; int auto_reset; int32_t* reset_list; uint8_t* reset_slot; uint32_t* counters; int prio; uint8_t* vplane;
     uint16_t* fcache; uint8_t* lsm_arr; int enum_done; FuseArgs fuse; int64_t block0; uint8_t* cplane; TapArgs tap;
     int ticks;            // k_step_ticks: steps this launch takes; tick t reads actions + t n and logs into the tap rows t * tap.count further on
+    uint8_t* dshadow; uint64_t* dmask; const uint8_t* lut;     // k_step: dshadow != NULL = the dirty cells of this step for its delta render (step_dirty)
 };
 template <bool VP, int FUSE, bool CP = false>
 __global__ __launch_bounds__(STEP_BLOCK, BBAI_STEP_WAVES) void k_step(StepArgs a) {
     // the block's observation rows at the OUTPUT pitch of 147 bytes (bbai_step.hpp RowPacker), 16 bytes of front padding
     __shared__ __attribute__((aligned(16))) uint8_t s_obs[ROWS_FRONT + STEP_BLOCK * OBS_BYTES + 16];
+    __shared__ __attribute__((aligned(8))) uint8_t s_lut[512];      // step_dirty (9 952 bytes in all: 16 blocks = 16 waves still fit a CU's 160 KiB)
     step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset, a.reset_list,
                             a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.fuse, a.block0, a.cplane, a.tap, s_obs, (int)threadIdx.x, (int)blockIdx.x);
+    if (a.dshadow) step_dirty(a.n, ((int64_t)blockIdx.x + a.block0) * STEP_BLOCK, a.dshadow, a.dmask, a.lut, s_obs + ROWS_FRONT, s_lut, (int)threadIdx.x);
 }
 // Several ticks in one launch (bbai_rollout, open-loop actions): an env's step touches only its own state, its block's LDS rows and -- for a
 // finished env -- look-ahead slots the window gate in front of the launch has vouched for, so a block walks through its ticks on its own, with
@@ -1693,8 +1777,6 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint
 constexpr int LINE_BYTES = 128;
 constexpr int DELTA_UNIT = 8;                                          // envs per line-aligned unit
 constexpr int UNIT_LINES = DELTA_UNIT * PIX_BYTES / LINE_BYTES;        // 588
-constexpr int CELLS = VIEW * VIEW;
-constexpr int AGENT_CELL = 3 * VIEW + 6;
 static_assert(DELTA_UNIT * PIX_BYTES % LINE_BYTES == 0 && PIX_BYTES % 64 == 0, "8-env units are whole 128-byte lines");
 
 // The cells of one env that bytes [s, t) of its 56x56x3 image come from (s, t multiples of 8: one 8-byte chunk per tile row piece).
@@ -1795,6 +1877,114 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
         for (int i = threadIdx.x; i < nd8; i += T) {
             const int q = (int)s_list[buf][i >> 3] * 8 + (i & 7);
             if (q >= nq) continue;                    // (past the end of an odd-sized last group: half a line)
+            const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
+            const uint8_t* t49 = s_tile[buf] + e * CELLS;
+            const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
+            const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
+            u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+            __builtin_nontemporal_store(v, out + q);
+        }
+    }
+}
+
+// k_render_dstore: the delta render of a step whose k_step has already found the dirty cells (step_dirty: the dirty masks in `dmask`, the
+// new tile ids in the shadow).  Stores only: per G-env group it reads the G masks and the ids the stored lines are drawn from -- 8-byte
+// pieces of the group's shadow rows, a piece loaded when a cell of it is drawn: its env is dirty, or the piece holds cells of the one line
+// its env shares with the other env of its pair (envs 2k, 2k + 1 of a unit: line 73 + 147 k) and that line is stored; no encoding, no lut,
+// no shadow write, no per-env phase.  Line list (B1) and stores (B2) as k_render_delta; the same static interleaved groups (SCHED 0).  The inputs are loaded a
+// group ahead (the ids) and two groups ahead (the masks, which decide what ids are loaded), under the current group's stores.
+constexpr int DSTORE_PIECES = 32 * CELLS / 8;                          // 8-byte shadow pieces of a 32-env group
+template <int G, int T>
+__global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restrict__ pixels, const uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
+                                                     const uint64_t* __restrict__ dmask /* [n] */, const uint8_t* __restrict__ atlas, int n_tiles) {
+    static_assert(G == 32 && T >= DSTORE_PIECES && T >= G && T % 64 == 0, "one 8-byte shadow piece per thread and group");
+    constexpr int GL = G / DELTA_UNIT * UNIT_LINES;
+    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
+    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];
+    __shared__ uint8_t s_lea[UNIT_LINES];
+    __shared__ uint64_t s_dmask[2][G];
+    __shared__ __attribute__((aligned(8))) uint8_t s_tile[2][G * CELLS + 8];
+    __shared__ uint16_t s_list[2][GL];
+    __shared__ unsigned int s_nd[2];
+    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
+    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
+        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
+        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
+        s_lea[l] = (uint8_t)ea;
+        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
+        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
+    }
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t ngroups = (n + G - 1) / G;
+    const int64_t gstep = gridDim.x;
+    int64_t g = blockIdx.x;
+    // the dirty mask of env `tid` of group `grp` (0 past the end)
+    auto load_mask = [&](int64_t grp) -> uint64_t {
+        const int64_t env = grp * G + tid;
+        return (tid < G && grp < ngroups && env < n) ? dmask[env] : 0ull;
+    };
+    // the cells of the line an even env shares with the next one (its last 64 bytes), and of the odd env (its first 64)
+    const uint64_t shared_a = line_cells(PIX_BYTES - LINE_BYTES / 2, PIX_BYTES), shared_b = line_cells(0, LINE_BYTES / 2);
+    static_assert(PIX_BYTES % LINE_BYTES == LINE_BYTES / 2, "two envs of a pair share one line");
+    // are the cells [c0, c1] of env e of the group drawn (masks: s_dmask[b]; envs past the end have none)
+    auto drawn = [&](int b, int e, int c0, int c1) -> bool {
+        if (s_dmask[b][e]) return true;
+        const uint64_t pm = (c1 == 63 ? ~0ull : (2ull << c1) - 1) & ~((1ull << c0) - 1);
+        const bool shared_stored = ((s_dmask[b][e & ~1] & shared_a) | (s_dmask[b][e | 1] & shared_b)) != 0;
+        return shared_stored && (pm & ((e & 1) ? shared_b : shared_a)) != 0;
+    };
+    // this thread's 8-byte piece of group `grp`'s ids, if a cell of it is drawn
+    auto load_ids = [&](int64_t grp, int b) -> uint2 {
+        uint2 r = make_uint2(0u, 0u);
+        if (tid >= DSTORE_PIECES || grp >= ngroups) return r;
+        const int b0 = 8 * tid, b1 = b0 + 7, ea = b0 / CELLS, eb = b1 / CELLS;
+        const bool need = eb == ea ? drawn(b, ea, b0 - ea * CELLS, b1 - ea * CELLS) : (drawn(b, ea, b0 - ea * CELLS, CELLS - 1) || drawn(b, eb, 0, b1 - eb * CELLS));
+        if (!need) return r;
+        const int64_t base = grp * G * CELLS + 8 * tid, end = n * CELLS;
+        if (base + 8 <= end) return *(const uint2*)(shadow + base);
+        uint32_t w[2] = {0u, 0u};
+        for (int i = 0; i < 8 && base + i < end; ++i) w[i >> 2] |= (uint32_t)shadow[base + i] << (8 * (i & 3));
+        return make_uint2(w[0], w[1]);
+    };
+    if (tid < G) s_dmask[0][tid] = load_mask(g);
+    uint64_t mreg = load_mask(g + gstep);
+    __syncthreads();                                  // atlas, line table and the first group's masks
+    uint2 idr = load_ids(g, 0);
+    int buf = 0;
+    for (; g < ngroups; g += gstep, buf ^= 1) {
+        const int64_t env0 = g * G;
+        const int ne = (int)(n - env0 < G ? n - env0 : G);
+        // A: this group's ids and the next group's masks into LDS
+        if (tid < DSTORE_PIECES) *(uint2*)(s_tile[buf] + 8 * tid) = idr;
+        if (tid < G) s_dmask[buf ^ 1][tid] = mreg;
+        if (tid == 0) s_nd[buf] = 0;
+        __syncthreads();
+        // B1: the group's dirty lines as a list (as k_render_delta)
+        const int nl = (int)(((int64_t)ne * PIX_BYTES + LINE_BYTES - 1) / LINE_BYTES);
+        for (int L0 = tid - lane; L0 < nl; L0 += T) {
+            const int L = L0 + lane;
+            bool d = false;
+            if (L < nl) {
+                const int u = L / UNIT_LINES, l = L - u * UNIT_LINES, ea = u * DELTA_UNIT + s_lea[l];
+                d = ((s_dmask[buf][ea] & s_lma[l]) | (s_lmb[l] ? s_dmask[buf][ea + 1] & s_lmb[l] : 0)) != 0;
+            }
+            const uint64_t m = __ballot(d);
+            if (!m) continue;
+            unsigned int base = 0;
+            if (lane == 0) base = atomicAdd(&s_nd[buf], (unsigned int)__builtin_popcountll(m));
+            base = __shfl(base, 0);
+            if (d) s_list[buf][base + __builtin_popcountll(m & ((1ull << lane) - 1))] = (uint16_t)L;
+        }
+        // the next group's ids (its masks are in LDS since the barrier above) and the masks of the one after it ride under the stores
+        idr = load_ids(g + gstep, buf ^ 1);
+        mreg = load_mask(g + 2 * gstep);
+        __syncthreads();
+        // B2: 16 bytes per lane, 8 lanes per listed line (as k_render_delta)
+        const int nq = ne * VEC_PER_ENV, nd8 = (int)s_nd[buf] * 8;
+        u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
+        for (int i = tid; i < nd8; i += T) {
+            const int q = (int)s_list[buf][i >> 3] * 8 + (i & 7);
+            if (q >= nq) continue;
             const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
             const uint8_t* t49 = s_tile[buf] + e * CELLS;
             const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
@@ -2443,6 +2633,7 @@ static int create_finish(bbai_env* e) {
         e->render_tpb = tv ? atoi(tv) : 0;
         const char* dv = getenv("BBAI_RENDER_DELTA");
         e->render_delta = dv ? atoi(dv) != 0 : 1;
+        e->render_delta_from_step = -1;
     }
     return BBAI_OK;
 }
@@ -2468,7 +2659,7 @@ void bbai_destroy(bbai_env* e) {
     void* bot_ptrs[] = {e->bot_state, e->bot_work, e->bot_stats, e->bot_rows};
     for (void* p : bot_ptrs) if (p) (void)hipFree(p);
     void* ptrs[] = {e->rec, e->hot, e->stale, e->mt, e->mti, e->vhead, e->vset, e->next_rec, e->next_hot, e->pending, e->first_slot, e->win_meta, e->totals, e->flow, e->gen_list, e->gen_count, e->reset_list, e->counters,
-                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow};
+                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow, e->rt_dmask};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int k = 0; k < 3; ++k) { if (e->grid_atlas[k]) (void)hipFree(e->grid_atlas[k]); if (e->grid_lut[k]) (void)hipFree(e->grid_lut[k]); }
     if (e->host_flags) (void)hipHostFree((void*)e->host_flags);
@@ -2768,7 +2959,9 @@ static bool use_fused_consume(const bbai_env* e) {
 //   step_prepare  the window gate (fused: the slots this step's waves consume must be there) + what the kernel needs to know about the window
 //   step_kernel   k_step over the 64-env blocks [block0, block0 + nblocks) on stream `ks`
 //   step_finish   k_consume (unfused) / mission tokens / the window's close + refill -- on the caller's stream, behind EVERY k_step of the step
-struct StepPlan { FuseArgs fa; bool fused; uint32_t* counter; TapArgs tap = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}; };
+struct StepPlan { FuseArgs fa; bool fused; uint32_t* counter; TapArgs tap = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+                  bool dirty = false;      // k_step finds the dirty cells of the registered target for its render (step_render_launch, step_dirty)
+};
 static int step_prepare(bbai_env* e, int auto_reset, hipStream_t s, StepPlan& p) {
     p.fused = auto_reset && (e->inplace || use_fused_consume(e));
     p.counter = e->counters + 16 * e->step_parity;
@@ -2801,6 +2994,7 @@ static int step_kernel(bbai_env* e, const StepPlan& p, const uint8_t* actions, u
     a.rewards = rewards; a.rewards64 = rewards64; a.dones = dones; a.auto_reset = auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
     a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = enum_done; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
     a.tap = p.tap; a.ticks = ticks;
+    a.dshadow = p.dirty && ticks == 1 ? e->rt_shadow : nullptr; a.dmask = e->rt_dmask; a.lut = e->lut;
 #define STEP_LAUNCH(VV, FF, CC) do { if (ticks > 1) hipLaunchKernelGGL((k_step_ticks<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); \
                                      else hipLaunchKernelGGL((k_step<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); } while (0)
     if (e->inplace && e->cplane) STEP_LAUNCH(false, 3, true);
@@ -2916,6 +3110,7 @@ int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
     if (!e) ARG_FAIL("null handle");
     ON_DEVICE(e->device);
     if (pixels && !e->rt_shadow) HIP_TRY(hipMalloc((void**)&e->rt_shadow, (size_t)e->n * CELLS));
+    if (pixels && !e->rt_dmask) HIP_TRY(hipMalloc((void**)&e->rt_dmask, (size_t)e->n * sizeof(uint64_t)));
     e->rt_pixels = pixels;
     e->rt_valid = false; e->rt_filled = 0;
     return BBAI_OK;
@@ -2925,6 +3120,17 @@ int bbai_render_invalidate(bbai_env* e) {
     if (!e) ARG_FAIL("null handle");
     e->rt_valid = false; e->rt_filled = 0;
     return BBAI_OK;
+}
+
+int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
+    if (!e || !out) ARG_FAIL("null handle or buffer");
+    if (!e->rt_shadow) { snprintf(g_err, sizeof(g_err), "render_shadow before bbai_set_render_target"); return BBAI_ERR_STATE; }
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    if (call.rc != BBAI_OK) return call.rc;
+    HIP_TRY(hipMemcpyAsync(out, e->rt_shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
+    return call.leave();
 }
 
 }  // extern "C"
@@ -2937,8 +3143,15 @@ int bbai_render_invalidate(bbai_env* e) {
 // moved from 10.8 to 11.4 ns between boxes and between two processes on one box, an idle chip puts it elsewhere than the loop does
 // (a first-render tuner), and a perturb-and-observe controller on the launches' own durations paid more for its event pairs and its
 // hovering than it gained.  The one counter's 1.50 ms is the same on all of them: it ships; the gate stays as a knob.
+// Is a render of envs [env_off, env_off + nr) into `pixels` a delta render of the registered target (given a valid shadow)?
+static bool delta_target(const bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
+    const uint8_t* const rt = e->rt_pixels;
+    const bool on_target = rt && pixels == rt + env_off * (int64_t)PIX_BYTES && env_off >= 0 && env_off + nr <= e->n;
+    return on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
+}
 static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, void* stream, int64_t n_render = -1 /* envs input / pixels hold (default: the batch); the shape follows the BATCH size */,
-                         int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */) {
+                         int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */,
+                         bool from_step = false /* the step in front found the dirty cells (step_dirty): store them (k_render_dstore) */) {
     CallScope call(e, (hipStream_t)stream);
     if (call.rc != BBAI_OK) return call.rc;
     const int64_t nr = n_render < 0 ? e->n : n_render;
@@ -2950,8 +3163,7 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
     // A render elsewhere leaves it alone.
     uint8_t* const rt = e->rt_pixels;
     const int64_t pb = PIX_BYTES;
-    const bool on_target = rt && pixels == rt + env_off * pb && env_off >= 0 && env_off + nr <= e->n;
-    const bool delta = on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
+    const bool delta = delta_target(e, pixels, env_off, nr);
     if (rt && !delta && pixels < rt + e->n * pb && pixels + nr * pb > rt) { e->rt_valid = false; e->rt_filled = 0; }
     // the shadow is not valid: the full render below writes every byte of the range and, given `shadow`, every tile id of it
     uint8_t* const shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
@@ -2963,12 +3175,17 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
         // k_render ms per launch: (1024 threads, 1 block per CU) interleaved 0.813, contiguous ranges 0.795, 2 blocks per CU 0.795;
         // (512, 1) 0.795; (512, 3) 0.665 <- default: three independent blocks per CU hide one another's encoding / shadow loads and
         // barriers (42 KB of LDS each: three fit).  Full render (k_render_q) 1.507.
-        const int T = e->render_delta_tpb == 1024 ? 1024 : 512;
+        const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
         constexpr int G = 32;
         const int64_t groups = (nr + G - 1) / G;
         const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
         const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
         uint8_t* sh = e->rt_shadow + env_off * CELLS;
+        if (from_step) {
+            hipLaunchKernelGGL((k_render_dstore<G, 512>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, nr, pixels, sh, e->rt_dmask + env_off, e->atlas, e->n_tiles);
+            HIP_TRY(hipGetLastError());
+            return call.leave();
+        }
 #define RENDER_D(TT, SS) hipLaunchKernelGGL((k_render_delta<G, TT, SS>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, sh, \
                                             e->atlas, e->lut, e->n_tiles)
         if (T == 512) { if (e->render_delta_sched == 1) RENDER_D(512, 1); else RENDER_D(512, 0); }
@@ -3202,13 +3419,25 @@ constexpr int64_t STEP_RENDER_SPLIT_MIN = 262144;
 #ifndef STEP_RENDER_SPLIT_DEFAULT
 #define STEP_RENDER_SPLIT_DEFAULT 0
 #endif
-static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
-                              int auto_reset, uint8_t* pixels, hipStream_t s, int enum_done) {
+// Option "render_delta_from_step" -1 (default): from this batch size up.  BossLevel pixels, bench.py's random actions, kernel medians
+// (profiles/render_delta_from_step/): at 1 048 576 envs the render gains more than k_step pays (k_render 608 -> 529 us, k_step 100 -> 143,
+// settings alternated in one process: 0.704 -> 0.666 ms per step); at 131 072 / 262 144 / 524 288 envs the render's inputs stay in the
+// memory-side cache, k_render_delta's input stage is nearly free and the render does not gain (82 / 153 / 288 us either way) while k_step
+// pays 11-22 us.
+constexpr int64_t RENDER_FROM_STEP_MIN_ENVS = 786432;
+static int step_render_launch_(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
+                               int auto_reset, uint8_t* pixels, hipStream_t s, int enum_done, bool& dirty) {
     StepPlan p;
     {
         CallScope call(e, s);
         if (call.rc != BBAI_OK) return call.rc;
         { int rc = step_prepare(e, auto_reset, s, p); if (rc != BBAI_OK) return rc; }
+        // The render is a delta render of the registered target with a valid shadow, and k_step's LDS rows are the step's final observations
+        // (fused / in-place consume, or no auto-reset; an unfused k_consume rewrites the finished envs' rows later): k_step finds the dirty
+        // cells and updates the shadow (step_dirty), the render only stores (k_render_dstore).  From the step kernel on, the shadow is ahead
+        // of the frame until the render has been launched: a failure in between invalidates it (step_render_launch).
+        const bool from_step = e->render_delta_from_step < 0 ? e->n >= RENDER_FROM_STEP_MIN_ENVS : e->render_delta_from_step != 0;
+        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !auto_reset) && delta_target(e, pixels, 0, e->n) && e->rt_valid;
         const int want = e->step_render_split < 0 ? (STEP_RENDER_SPLIT_DEFAULT && e->n >= STEP_RENDER_SPLIT_MIN) : e->step_render_split;      // (an explicit 1: any size)
         const int64_t nb = step_blocks(e), hb = nb / 2;
         const bool split = want && pixels && (p.fused || !auto_reset) && hb > 0;
@@ -3216,7 +3445,7 @@ static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* imag
             { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, enum_done, 0, nb); if (rc != BBAI_OK) return rc; }
             { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
             { int rc = call.leave(); if (rc != BBAI_OK) return rc; }
-            return pixels ? render_launch(e, image, pixels, s) : BBAI_OK;
+            return pixels ? render_launch(e, image, pixels, s, -1, 0, p.dirty) : BBAI_OK;
         }
         const int64_t na = hb * STEP_BLOCK;                   // envs of the first half (a multiple of every render group size)
         // the second half's k_step, on the split stream, behind everything the caller's stream holds so far (the gate included)
@@ -3226,7 +3455,7 @@ static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* imag
         HIP_TRY(hipEventRecord(e->ev_splitB, e->split));
         { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, enum_done, 0, hb); if (rc != BBAI_OK) return rc; }
         { int rc = call.leave(); if (rc != BBAI_OK) return rc; }
-        { int rc = render_launch(e, image, pixels, s, na); if (rc != BBAI_OK) return rc; }
+        { int rc = render_launch(e, image, pixels, s, na, 0, p.dirty); if (rc != BBAI_OK) return rc; }
         HIP_TRY(hipStreamWaitEvent(s, e->ev_splitB, 0));
         {
             CallScope call2(e, s);
@@ -3234,8 +3463,15 @@ static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* imag
             { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
             { int rc = call2.leave(); if (rc != BBAI_OK) return rc; }
         }
-        return render_launch(e, image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na, na);
+        return render_launch(e, image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na, na, p.dirty);
     }
+}
+static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
+                              int auto_reset, uint8_t* pixels, hipStream_t s, int enum_done) {
+    bool dirty = false;
+    const int rc = step_render_launch_(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, pixels, s, enum_done, dirty);
+    if (rc != BBAI_OK && dirty) { e->rt_valid = false; e->rt_filled = 0; }
+    return rc;
 }
 
 extern "C" {
@@ -3761,6 +3997,7 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     else if (!strcmp(name, "render_delta_sched")) e->render_delta_sched = v;
     else if (!strcmp(name, "render_delta_tpb")) e->render_delta_tpb = v;
     else if (!strcmp(name, "render_delta_bpc")) e->render_delta_bpc = std::max(0, v);
+    else if (!strcmp(name, "render_delta_from_step")) e->render_delta_from_step = v < 0 ? -1 : v != 0;
     else if (!strcmp(name, "grid_render_bpc")) e->grid_bpc = std::max(0, v);
     else if (!strcmp(name, "step_prio")) e->step_prio = v;
     else if (!strcmp(name, "pregen_group")) e->pregen_group = v;
@@ -3813,6 +4050,7 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     else if (!strcmp(name, "render_delta_sched")) *out = e->render_delta_sched;
     else if (!strcmp(name, "render_delta_tpb")) *out = e->render_delta_tpb;
     else if (!strcmp(name, "render_delta_bpc")) *out = e->render_delta_bpc;
+    else if (!strcmp(name, "render_delta_from_step")) *out = e->render_delta_from_step;
     else if (!strcmp(name, "grid_render_bpc")) *out = e->grid_bpc;
     else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
     else if (!strcmp(name, "step_prio")) *out = e->step_prio;

@@ -74,6 +74,8 @@ def load_library():
     if hasattr(lib, "bbai_set_render_target"):
         lib.bbai_set_render_target.argtypes = [P, P]
         lib.bbai_render_invalidate.argtypes = [P]
+    if hasattr(lib, "bbai_render_shadow"):
+        lib.bbai_render_shadow.argtypes = [P, P, P]
     if hasattr(lib, "bbai_render_grid"):
         lib.bbai_set_grid_atlas.argtypes = [P, I32, P, I32, P]
         lib.bbai_render_grid.argtypes = [P, I32, I32, P, I64, P, P]
@@ -118,7 +120,7 @@ EXPORTED_SYMBOLS = (
     "bbai_checkpoint_bytes", "bbai_checkpoint_save", "bbai_checkpoint_load", "bbai_profile", "bbai_profile_read", "bbai_gae", "bbai_tap",
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
-    "bbai_set_render_target", "bbai_render_invalidate", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
+    "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
 )
 
 
@@ -388,6 +390,13 @@ class BatchedBabyAIEnv(object):
     def render_invalidate(self):
         """Call after writing into self.pixels yourself: the next render rewrites every byte (include/bbai.h bbai_render_invalidate)."""
         _check(self.lib, self.lib.bbai_render_invalidate(self.handle), "bbai_render_invalidate")
+
+    def render_shadow(self):
+        """The tile ids of the frame the registered buffer holds, uint8[N][49] (include/bbai.h bbai_render_shadow)."""
+        import torch
+        out = torch.empty((self.num_envs, 49), dtype=torch.uint8, device=self.pixels.device)
+        _check(self.lib, self.lib.bbai_render_shadow(self.handle, out.data_ptr(), self._stream()), "bbai_render_shadow")
+        return out
 
     def reset(self):
         _check(self.lib, self.lib.bbai_reset(self.handle, self.image.data_ptr(), self.direction.data_ptr(),

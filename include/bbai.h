@@ -125,6 +125,9 @@ int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_d
  * buffer again when it is reallocated: a freed buffer's address may be handed out again with other contents. */
 int bbai_set_render_target(bbai_env* env, uint8_t* pixels_dev);
 int bbai_render_invalidate(bbai_env* env);
+/* A copy of the registered buffer's tile ids, uint8[N][49] (cell = 7 x + y of the encoded view), into a device buffer, on `stream`:
+ * what the next delta render compares against (tests). */
+int bbai_render_shadow(bbai_env* env, uint8_t* out_dev, void* stream);
 
 /* The full-grid picture: MiniGridEnv.render('rgb_array', highlight, tile_size) (gym_minigrid minigrid.py; called by
  * scripts/manual_control.py:14 with --tile_size, scripts/enjoy.py:101,108 in 'human' mode) of listed envs, on the device.
