@@ -220,6 +220,58 @@ int hs_step64_done_enum(const LevelCfg* cfg, uint8_t* rec, Hot* hot, uint64_t* s
     return (order ? step_env_prefetch(*cfg, rec, vp, *hot, *stale, action, *reward, lsm, true)
                   : step_env(*cfg, rec, vp, *hot, *stale, action, *reward, lsm, true)) ? 1 : 0;
 }
+// ---- a whole batch per call (tests/hostsim_util.py HostBatch: the reference of the device's step kernels at scale) --------------
+// Env i's state: mt[i * MT_N ..], mti[i], rec[i * rec_bytes ..], hot[i], stale[i], lsm[i] (NULL: normal mode; else the done-action
+// mode's lastStepMatch bits, 0 at every episode start).  Outputs as the engine's: image[i][147], dirs[i], reward[i] (f64), done[i].
+void hs_seed_batch(int n, const uint64_t* seeds, uint32_t* mt, int32_t* mti) {
+    for (int i = 0; i < n; ++i) { seed_env(seeds[i], mt + (size_t)i * MT_N); mti[i] = MT_N; }
+}
+// HostEnv.reset for one env: the next level of its stream, the first observation, then PutNext*Carrying's start carry.
+static void batch_new_episode(const LevelCfg* cfg, uint32_t* mt, int32_t* mti, uint8_t* rec, Hot* hot, uint64_t* stale, uint32_t* lsm,
+                              uint8_t* image, uint8_t* dir) {
+    hs_generate(cfg, mt, mti, rec, hot);
+    *stale = 0;
+    if (lsm) *lsm = 0;
+    observe_env(*cfg, rec, *hot, image);
+    *dir = hot->dir;
+    hs_start_carry(cfg, rec, hot, stale);
+}
+void hs_reset_batch(const LevelCfg* cfg, int n, uint32_t* mt, int32_t* mti, uint8_t* rec, Hot* hot, uint64_t* stale, uint32_t* lsm,
+                    uint8_t* image, uint8_t* dirs) {
+    for (int i = 0; i < n; ++i)
+        batch_new_episode(cfg, mt + (size_t)i * MT_N, mti + i, rec + (size_t)i * cfg->rec_bytes, hot + i, stale + i, lsm ? lsm + i : nullptr,
+                          image + (size_t)i * OBS_BYTES, dirs + i);
+}
+// One step of every env in k_step's order of operations (step_env_prefetch), action 7 = BBAI_ACTION_RESET_ENV.  auto_reset: a finished env
+// starts its next episode at once (its first observation is the output); else it freezes (Hot.frozen = 1) and re-emits its outputs, untouched,
+// until the caller resets it.  enum_done (done-action mode): this step's `done` actions count as the enum member (hs_step64_done_enum).
+void hs_step_batch(const LevelCfg* cfg, int n, uint32_t* mt, int32_t* mti, uint8_t* rec, Hot* hot, uint64_t* stale, uint32_t* lsm, int enum_done,
+                   const uint8_t* actions, int auto_reset, uint8_t* image, uint8_t* dirs, double* reward, uint8_t* done) {
+    for (int i = 0; i < n; ++i) {
+        Hot& h = hot[i];
+        if (h.frozen) continue;
+        uint8_t* r = rec + (size_t)i * cfg->rec_bytes;
+        const int action = actions[i];
+        double rw = 0.0;
+        bool d = true;
+        if (action != A_RESET_ENV) {
+            const Prog* p = (const Prog*)(r + cfg->off_prog);
+            uint64_t sets[8];
+            for (int k = 0; k < 8; ++k) sets[k] = p->set[k >> 1][k & 1];
+            VProg vp; vp.bind(vhead_pack(*p), sets, 1);
+            d = step_env_prefetch(*cfg, r, vp, h, stale[i], action, rw, lsm ? lsm + i : nullptr, enum_done != 0);
+        }
+        reward[i] = rw;
+        done[i] = d ? 1 : 0;
+        if (d && auto_reset) {
+            batch_new_episode(cfg, mt + (size_t)i * MT_N, mti + i, r, &h, stale + i, lsm ? lsm + i : nullptr, image + (size_t)i * OBS_BYTES, dirs + i);
+        } else {
+            observe_env(*cfg, r, h, image + (size_t)i * OBS_BYTES);
+            dirs[i] = h.dir;
+            if (d) h.frozen = 1;
+        }
+    }
+}
 int hs_step(const LevelCfg* cfg, uint8_t* rec, Hot* hot, uint64_t* stale, int action, float* reward) {
     double r = 0.0;
     const int d = hs_step64(cfg, rec, hot, stale, action, &r);

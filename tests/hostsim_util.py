@@ -44,6 +44,11 @@ def lib():
         L.hs_bot_set_lanes.argtypes = [ctypes.c_int]
         L.hs_bot_dead_reason.argtypes = [P]
         L.hs_bot_stack_depth.argtypes = [P]
+        L.hs_step64_done.argtypes = [P, P, P, P, ctypes.c_int, P, P]
+        L.hs_step64_done_enum.argtypes = [P, P, P, P, ctypes.c_int, P, P, ctypes.c_int]
+        L.hs_seed_batch.argtypes = [ctypes.c_int, P, P, P]
+        L.hs_reset_batch.argtypes = [P, ctypes.c_int, P, P, P, P, P, P, P, P]
+        L.hs_step_batch.argtypes = [P, ctypes.c_int, P, P, P, P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]
         _lib = L
     return _lib
 
@@ -108,6 +113,60 @@ class HostEnv(object):
     def grid_bytes(self):
         c = self.cfg
         return self.rec[:c.ES * c.EH].reshape(c.EH, c.ES)[5:5 + c.H, 5:5 + c.W]
+
+
+class HostBatch(object):
+    """N envs of the C++ core on the host, one ctypes call per batch step (hostsim.cpp hs_step_batch): the outputs the engine's step
+    kernels write -- image uint8[N, 7, 7, 3], direction, reward64 (f64) and its f32 rounding, done -- and the state export_state() reads back
+    (records, hot, stale).  Steps in k_step's order of operations; action 7 = BBAI_ACTION_RESET_ENV.  auto_reset: a finished env starts its
+    next level at once (HostEnv.reset); else it freezes (hot byte 13 = 1) and re-emits its outputs until reset().  done_actions: the
+    reference's BABYAI_DONE_ACTIONS verifier mode (per-env lastStepMatch bits); enum_done: its `done` counts as the enum member."""
+
+    def __init__(self, cfg, seeds, auto_reset=True, done_actions=False, enum_done=False):
+        self.L = lib()
+        self.cfg = cfg
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+        self.n = n = len(seeds)
+        self.auto_reset, self.enum_done = bool(auto_reset), bool(enum_done)
+        self.mt = np.zeros((n, 624), np.uint32)
+        self.mti = np.zeros(n, np.int32)
+        self.L.hs_seed_batch(n, seeds.ctypes.data, self.mt.ctypes.data, self.mti.ctypes.data)
+        self.rec = np.zeros((n, cfg.rec_bytes), np.uint8)
+        self.hot = np.zeros((n, 16), np.uint8)
+        self.hot[:, 14] = 0xFF           # last_locked = none
+        self.stale = np.zeros(n, np.uint64)
+        self.lsm = np.zeros(n, np.uint32) if done_actions else None
+        self.image = np.zeros((n, 7, 7, 3), np.uint8)
+        self.direction = np.zeros(n, np.uint8)
+        self.reward64 = np.zeros(n, np.float64)
+        self.done = np.zeros(n, np.uint8)
+
+    def _state(self):
+        return (ctypes.byref(self.cfg), self.n, self.mt.ctypes.data, self.mti.ctypes.data, self.rec.ctypes.data, self.hot.ctypes.data,
+                self.stale.ctypes.data, self.lsm.ctypes.data if self.lsm is not None else None)
+
+    def reset(self):
+        self.hot[:, 13] = 0             # (frozen)
+        self.L.hs_reset_batch(*self._state(), self.image.ctypes.data, self.direction.ctypes.data)
+        return self.image
+
+    def step(self, actions):
+        act = np.ascontiguousarray(np.asarray(actions, dtype=np.uint8).reshape(self.n))
+        self.L.hs_step_batch(*self._state(), int(self.enum_done), act.ctypes.data, int(self.auto_reset), self.image.ctypes.data,
+                             self.direction.ctypes.data, self.reward64.ctypes.data, self.done.ctypes.data)
+        return self.image, self.reward, self.done
+
+    @property
+    def reward(self):
+        return self.reward64.astype(np.float32)
+
+    @property
+    def step_count(self):
+        return self.hot[:, 4].astype(np.int32) | self.hot[:, 5].astype(np.int32) << 8
+
+    @property
+    def max_steps(self):
+        return self.hot[:, 6].astype(np.int32) | self.hot[:, 7].astype(np.int32) << 8
 
 
 class HostBot(object):

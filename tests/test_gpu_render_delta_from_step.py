@@ -98,6 +98,38 @@ def test_single_room_in_place_with_resets(gpu, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("level", [ROOM, BOSS])
+def test_frozen_envs_without_auto_reset(gpu, level):
+    """auto_reset=False: k_step finds the dirty cells of a step whose finished envs freeze and re-emit their last observation (the branch of
+    bbai_step_render for `!auto_reset`), in the in-place layout (GoToLocal) and the classic one (BossLevel), at an odd batch size past the
+    option's default threshold; reset commands (action 7) freeze envs of both levels, a reset() in mid-run thaws them all."""
+    import torch
+    from babyai_amd.action_stream import actions_torch
+    n, T = 786432 + 64 + 3, 60
+    a, b = pair(gpu, n, level=level, seeds=29, auto_reset=False)
+    assert a.get_option("inplace") == (1 if level == ROOM else 0)
+    acts = actions_torch(9, 0, T, 0, n, gpu)
+    gen = torch.Generator(device=gpu)
+    gen.manual_seed(4)
+    frozen = 0
+    for t in range(T):
+        if t == 40:
+            a.reset()
+            b.reset()
+            assert same(a, b), t
+        act = torch.where(torch.rand((n,), device=gpu, generator=gen) < 0.01, torch.full_like(acts[t], 7), acts[t])
+        a.step(act)
+        b.step(act)
+        if t == 39:
+            frozen = int(a.done.sum())
+        if t % 10 == 0 or t == 39:
+            assert same(a, b), t
+    assert same(a, b) and frozen > n // 5
+    assert torch.equal(a.done, b.done) and torch.equal(a.reward64, b.reward64)
+    assert torch.equal(full_render(a), a.pixels)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("split", [0, 1])
 def test_split_steps(gpu, split):
     """bbai_step_render in two halves: both halves' renders take the step's dirty cells (the second one at an env offset)."""
