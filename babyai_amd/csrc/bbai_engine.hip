@@ -206,6 +206,7 @@ struct bbai_env {
     int render_delta_tpb;      // option "render_delta_tpb": 512 (default, also for 0) or 1024 threads per delta render block
     int render_delta_bpc;      // option "render_delta_bpc": delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
     uint64_t* rt_dmask;   // [n] the dirty-cell mask of every env, left by k_step for the store-only render (k_render_dstore); allocated with rt_shadow
+    int render_piece_bytes;    // option "render_piece_bytes": the delta render's store unit, 64-byte pieces (default) or 128 (whole lines)
     int render_delta_from_step;   // option "render_delta_from_step": 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
     int done_action_enum; // option "done_action_enum": done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
@@ -1761,8 +1762,9 @@ __global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint
 
 // ---- delta render into the registered target (bbai_set_render_target) ----------------------------------------------------------
 // The registered buffer holds the previous frame of every env, and the handle's shadow plane holds the atlas tile id of every cell
-// of that frame (uint8[n][49]).  A frame cell whose tile id is unchanged has unchanged bytes, so only the 128-byte lines that
-// touch a changed cell are stored -- whole lines, never partial ones.  8 envs are 8 x 9408 = 588 x 128 bytes: a unit of 8 envs
+// of that frame (uint8[n][49]).  A frame cell whose tile id is unchanged has unchanged bytes, so only the parts of the frame that
+// touch a changed cell are stored: 64-byte pieces by default (render_piece_bytes; store_dirty_pieces below), or, with the option at
+// 128, whole 128-byte lines -- the line form this paragraph describes.  8 envs are 8 x 9408 = 588 x 128 bytes: a unit of 8 envs
 // starts on a line boundary whenever the buffer does (render_launch checks the alignment), and a line belongs to one unit; inside
 // it a line touches one env or two (9408 = 73.5 lines).  Per G-env group of a block iteration:
 //   A   one wave per env, one lane per cell: the new tile id (s_lut, as k_render), its old id from the shadow, a ballot gives the
@@ -1778,6 +1780,7 @@ constexpr int LINE_BYTES = 128;
 constexpr int DELTA_UNIT = 8;                                          // envs per line-aligned unit
 constexpr int UNIT_LINES = DELTA_UNIT * PIX_BYTES / LINE_BYTES;        // 588
 static_assert(DELTA_UNIT * PIX_BYTES % LINE_BYTES == 0 && PIX_BYTES % 64 == 0, "8-env units are whole 128-byte lines");
+constexpr int RENDER_PIECE_DEFAULT = 64;                               // option "render_piece_bytes" (render_launch)
 
 // The cells of one env that bytes [s, t) of its 56x56x3 image come from (s, t multiples of 8: one 8-byte chunk per tile row piece).
 __device__ __forceinline__ uint64_t line_cells(int s, int t) {
@@ -1789,29 +1792,67 @@ __device__ __forceinline__ uint64_t line_cells(int s, int t) {
     return m;
 }
 
-template <int G, int T, int SCHED>
+// ---- piece-granular stores (render_piece_bytes P < 128) --------------------------------------------------------------------------
+// A P-byte piece (P divides 9408, so no piece crosses an env boundary and every env starts on the piece grid when the buffer does) is
+// stored when a cell it is drawn from changed.  Stores are byte-masked and the memory side does not read a partial line back (FETCH_SIZE
+// stays flat), but the store RATE falls with the piece: tools/ubench_sector_store.hip, 1 048 576 frames, a BossLevel-like dirty mix,
+// ms against whole lines: 64 B 0.96, 32 B 1.81, 16 B 2.32 (WRITE_SIZE 0.87 / 0.74 / 0.74).  64-byte pieces ship: in the step loop they
+// cut the headline's render by 3 % (profiles/render_pieces/); 32 and below lose more in rate than they save in bytes.
+// Per env the cells of every piece come from a per-block table (s_pm: NP 49-bit masks), and ONE wave handles a dirty env: a lane per
+// piece tests (dirty mask & piece cells), a ballot compacts the dirty pieces into the wave's own LDS list, and the wave stores them
+// 16 bytes per lane, consecutive lanes on consecutive chunks.  The list is the wave's: no LDS atomic, no workgroup barrier.
+template <int P>
+struct Pieces {
+    static_assert(P == 16 || P == 32 || P == 64, "pieces of 16, 32 or 64 bytes");
+    static_assert(PIX_BYTES % P == 0, "whole pieces per env");
+    static constexpr int NP = PIX_BYTES / P;          // pieces per env (147 at P = 64)
+    static constexpr int S = P / 16;                  // 16-byte stores per piece
+};
+
+__device__ __forceinline__ void wave_lds_sync() {     // the wave's own LDS writes are visible to its other lanes (no workgroup barrier)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int P>
+__device__ __forceinline__ void init_piece_cells(uint64_t* s_pm, int tid, int nthreads) {
+    for (int p = tid; p < Pieces<P>::NP; p += nthreads) s_pm[p] = line_cells(p * P, p * P + P);
+}
+
+// Stores the pieces of one env whose cells meet the dirty mask `m` (wave-uniform, nonzero).  Called by a whole wave; `wl` is the
+// wave's list (NP entries), `t49` the env's 49 tile ids, `out` the env's first 16-byte chunk.
+template <int P>
+__device__ __forceinline__ void store_dirty_pieces(uint64_t m, const uint64_t* s_pm, uint16_t* wl, const uint8_t* s_atlas, const uint8_t* t49,
+                                                   u32x4* out, int lane) {
+    constexpr int NP = Pieces<P>::NP, S = Pieces<P>::S;
+    int cnt = 0;
+    for (int p0 = 0; p0 < NP; p0 += 64) {
+        const int p = p0 + lane;
+        const bool d = p < NP && (m & s_pm[p]) != 0;
+        const uint64_t b = __ballot(d);
+        if (d) wl[cnt + __builtin_popcountll(b & ((1ull << lane) - 1))] = (uint16_t)p;
+        cnt += __builtin_popcountll(b);
+    }
+    wave_lds_sync();
+    for (int i = lane; i < cnt * S; i += 64) {
+        const int k = (int)wl[i / S] * S + (i & (S - 1));
+        const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
+        const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
+        u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+        __builtin_nontemporal_store(v, out + k);
+    }
+    wave_lds_sync();                                  // the list is read before the wave's next env writes it
+}
+
+template <int G, int T, int SCHED, int P>
 __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __restrict__ image, uint8_t* __restrict__ pixels,
                                                     uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
                                                     const uint8_t* __restrict__ atlas, const uint8_t* __restrict__ lut, int n_tiles) {
     static_assert(G % DELTA_UNIT == 0 && T % 64 == 0 && G % (T / 64) == 0, "whole units per group, whole envs per wave");
     constexpr int W = T / 64, EPW = G / W, GL = G / DELTA_UNIT * UNIT_LINES;
     __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];        // cells of the line's first / second env (0: one env)
-    __shared__ uint8_t s_lea[UNIT_LINES];                              // the line's first env in the unit
-    __shared__ uint64_t s_dmask[2][G];
     __shared__ uint8_t s_lut[512];
-    __shared__ uint8_t s_tile[2][G * CELLS + 8];
-    __shared__ uint16_t s_list[2][GL];
-    __shared__ unsigned int s_nd[2];
-    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    for (int k = threadIdx.x; k < 512; k += T) s_lut[k] = lut[k];
-    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
-        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
-        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
-        s_lea[l] = (uint8_t)ea;
-        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
-        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
-    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t ngroups = (n + G - 1) / G;
     int64_t g, gend, gstep;
@@ -1831,6 +1872,55 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
             }
         }
     };
+    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
+    for (int k = threadIdx.x; k < 512; k += T) s_lut[k] = lut[k];
+    if constexpr (P < LINE_BYTES) {
+        // Pieces: the wave that finds an env's dirty mask (A) also stores its pieces, from the ids it has just written to LDS -- no
+        // workgroup barrier in the loop, one tile buffer (a wave writes an env's ids again only after it has stored that env).
+        __shared__ uint64_t s_pm[Pieces<P>::NP];
+        __shared__ uint16_t s_wl[W][Pieces<P>::NP];
+        __shared__ uint8_t s_tile1[G * CELLS + 8];
+        init_piece_cells<P>(s_pm, threadIdx.x, T);
+        load(g);
+        __syncthreads();                              // atlas, lut and piece table loaded
+        for (; g < gend; g += gstep) {
+            const int64_t env0 = g * G;
+            const int ne = (int)(n - env0 < G ? n - env0 : G);
+            uint64_t dm[EPW];
+#pragma unroll
+            for (int j = 0; j < EPW; ++j) {
+                const int e = wave + j * W;
+                const bool live = lane < CELLS && e < ne;
+                const int key = o0[j] | (o1[j] << 3) | (o2[j] << 6);
+                const uint32_t id = live ? s_lut[(lane == AGENT_CELL ? 256 : 0) + key] : 0;
+                const bool d = live && id != old[j];
+                dm[j] = __ballot(d);
+                if (live) s_tile1[e * CELLS + lane] = (uint8_t)id;
+                if (d) shadow[(env0 + e) * CELLS + lane] = (uint8_t)id;
+            }
+            load(g + gstep);                          // the next group's inputs ride under this group's stores
+            wave_lds_sync();
+#pragma unroll
+            for (int j = 0; j < EPW; ++j) {
+                const int e = wave + j * W;
+                if (dm[j]) store_dirty_pieces<P>(dm[j], s_pm, s_wl[wave], s_atlas, s_tile1 + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
+            }
+        }
+        return;
+    } else {
+    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];        // cells of the line's first / second env (0: one env)
+    __shared__ uint8_t s_lea[UNIT_LINES];                              // the line's first env in the unit
+    __shared__ uint64_t s_dmask[2][G];
+    __shared__ uint8_t s_tile[2][G * CELLS + 8];
+    __shared__ uint16_t s_list[2][GL];
+    __shared__ unsigned int s_nd[2];
+    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
+        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
+        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
+        s_lea[l] = (uint8_t)ea;
+        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
+        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
+    }
     load(g);
     __syncthreads();                                  // atlas, lut and line table loaded
     int buf = 0;
@@ -1885,6 +1975,7 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
             __builtin_nontemporal_store(v, out + q);
         }
     }
+    }
 }
 
 // k_render_dstore: the delta render of a step whose k_step has already found the dirty cells (step_dirty: the dirty masks in `dmask`, the
@@ -1894,26 +1985,14 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
 // no shadow write, no per-env phase.  Line list (B1) and stores (B2) as k_render_delta; the same static interleaved groups (SCHED 0).  The inputs are loaded a
 // group ahead (the ids) and two groups ahead (the masks, which decide what ids are loaded), under the current group's stores.
 constexpr int DSTORE_PIECES = 32 * CELLS / 8;                          // 8-byte shadow pieces of a 32-env group
-template <int G, int T>
+template <int G, int T, int P>
 __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restrict__ pixels, const uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
                                                      const uint64_t* __restrict__ dmask /* [n] */, const uint8_t* __restrict__ atlas, int n_tiles) {
     static_assert(G == 32 && T >= DSTORE_PIECES && T >= G && T % 64 == 0, "one 8-byte shadow piece per thread and group");
     constexpr int GL = G / DELTA_UNIT * UNIT_LINES;
     __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];
-    __shared__ uint8_t s_lea[UNIT_LINES];
-    __shared__ uint64_t s_dmask[2][G];
     __shared__ __attribute__((aligned(8))) uint8_t s_tile[2][G * CELLS + 8];
-    __shared__ uint16_t s_list[2][GL];
-    __shared__ unsigned int s_nd[2];
     for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
-        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
-        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
-        s_lea[l] = (uint8_t)ea;
-        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
-        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
-    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int64_t ngroups = (n + G - 1) / G;
     const int64_t gstep = gridDim.x;
@@ -1923,6 +2002,64 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
         const int64_t env = grp * G + tid;
         return (tid < G && grp < ngroups && env < n) ? dmask[env] : 0ull;
     };
+    // 8 ids of group `grp` from the shadow (bounds-checked at the end of the range)
+    auto load_piece = [&](int64_t grp) -> uint2 {
+        const int64_t base = grp * G * CELLS + 8 * tid, end = n * CELLS;
+        if (base + 8 <= end) return *(const uint2*)(shadow + base);
+        uint32_t w[2] = {0u, 0u};
+        for (int i = 0; i < 8 && base + i < end; ++i) w[i >> 2] |= (uint32_t)shadow[base + i] << (8 * (i & 3));
+        return make_uint2(w[0], w[1]);
+    };
+    if constexpr (P < LINE_BYTES) {
+        // Pieces: only the dirty envs' ids are loaded (a piece of an env draws on that env's cells alone); one wave per dirty env stores
+        // its pieces (store_dirty_pieces).  One workgroup barrier per group: the ids (two buffers) and the masks (three buffers: the
+        // next group's masks are written while a slower wave may still read the current ones) are written in A and read behind it.
+        constexpr int W = T / 64, EPW = G / W;
+        __shared__ uint64_t s_pm[Pieces<P>::NP];
+        __shared__ uint16_t s_wl[W][Pieces<P>::NP];
+        __shared__ uint64_t s_dm3[3][G];
+        const int wave = tid >> 6;
+        init_piece_cells<P>(s_pm, tid, T);
+        auto load_ids = [&](int64_t grp, int b) -> uint2 {
+            if (tid >= DSTORE_PIECES || grp >= ngroups) return make_uint2(0u, 0u);
+            const int ea = (8 * tid) / CELLS, eb = (8 * tid + 7) / CELLS;
+            if (!s_dm3[b][ea] && !s_dm3[b][eb]) return make_uint2(0u, 0u);
+            return load_piece(grp);
+        };
+        if (tid < G) s_dm3[0][tid] = load_mask(g);
+        uint64_t mreg = load_mask(g + gstep);
+        __syncthreads();                              // atlas, piece table and the first group's masks
+        uint2 idr = load_ids(g, 0);
+        int buf = 0, mb = 0;
+        for (; g < ngroups; g += gstep, buf ^= 1, mb = mb == 2 ? 0 : mb + 1) {
+            const int64_t env0 = g * G;
+            const int mn = mb == 2 ? 0 : mb + 1;
+            if (tid < DSTORE_PIECES) *(uint2*)(s_tile[buf] + 8 * tid) = idr;
+            if (tid < G) s_dm3[mn][tid] = mreg;
+            __syncthreads();
+            idr = load_ids(g + gstep, mn);            // the next group's ids and the masks of the one after it ride under the stores
+            mreg = load_mask(g + 2 * gstep);
+#pragma unroll
+            for (int j = 0; j < EPW; ++j) {
+                const int e = wave + j * W;
+                const uint64_t m = s_dm3[mb][e];      // (0 past the end of the range)
+                if (m) store_dirty_pieces<P>(m, s_pm, s_wl[wave], s_atlas, s_tile[buf] + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
+            }
+        }
+        return;
+    } else {
+    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];
+    __shared__ uint8_t s_lea[UNIT_LINES];
+    __shared__ uint64_t s_dmask[2][G];
+    __shared__ uint16_t s_list[2][GL];
+    __shared__ unsigned int s_nd[2];
+    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
+        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
+        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
+        s_lea[l] = (uint8_t)ea;
+        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
+        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
+    }
     // the cells of the line an even env shares with the next one (its last 64 bytes), and of the odd env (its first 64)
     const uint64_t shared_a = line_cells(PIX_BYTES - LINE_BYTES / 2, PIX_BYTES), shared_b = line_cells(0, LINE_BYTES / 2);
     static_assert(PIX_BYTES % LINE_BYTES == LINE_BYTES / 2, "two envs of a pair share one line");
@@ -1940,11 +2077,7 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
         const int b0 = 8 * tid, b1 = b0 + 7, ea = b0 / CELLS, eb = b1 / CELLS;
         const bool need = eb == ea ? drawn(b, ea, b0 - ea * CELLS, b1 - ea * CELLS) : (drawn(b, ea, b0 - ea * CELLS, CELLS - 1) || drawn(b, eb, 0, b1 - eb * CELLS));
         if (!need) return r;
-        const int64_t base = grp * G * CELLS + 8 * tid, end = n * CELLS;
-        if (base + 8 <= end) return *(const uint2*)(shadow + base);
-        uint32_t w[2] = {0u, 0u};
-        for (int i = 0; i < 8 && base + i < end; ++i) w[i >> 2] |= (uint32_t)shadow[base + i] << (8 * (i & 3));
-        return make_uint2(w[0], w[1]);
+        return load_piece(grp);
     };
     if (tid < G) s_dmask[0][tid] = load_mask(g);
     uint64_t mreg = load_mask(g + gstep);
@@ -1992,6 +2125,7 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
             u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
             __builtin_nontemporal_store(v, out + q);
         }
+    }
     }
 }
 
@@ -2634,6 +2768,7 @@ static int create_finish(bbai_env* e) {
         const char* dv = getenv("BBAI_RENDER_DELTA");
         e->render_delta = dv ? atoi(dv) != 0 : 1;
         e->render_delta_from_step = -1;
+        e->render_piece_bytes = RENDER_PIECE_DEFAULT;
     }
     return BBAI_OK;
 }
@@ -3181,15 +3316,21 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
         const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
         const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
         uint8_t* sh = e->rt_shadow + env_off * CELLS;
+        const int pb = e->render_piece_bytes;
         if (from_step) {
-            hipLaunchKernelGGL((k_render_dstore<G, 512>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, nr, pixels, sh, e->rt_dmask + env_off, e->atlas, e->n_tiles);
+#define RENDER_S(PP) hipLaunchKernelGGL((k_render_dstore<G, 512, PP>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, nr, pixels, sh, e->rt_dmask + env_off, \
+                                        e->atlas, e->n_tiles)
+            if (pb == 128) RENDER_S(128); else RENDER_S(64);
+#undef RENDER_S
             HIP_TRY(hipGetLastError());
             return call.leave();
         }
-#define RENDER_D(TT, SS) hipLaunchKernelGGL((k_render_delta<G, TT, SS>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, sh, \
-                                            e->atlas, e->lut, e->n_tiles)
-        if (T == 512) { if (e->render_delta_sched == 1) RENDER_D(512, 1); else RENDER_D(512, 0); }
-        else { if (e->render_delta_sched == 1) RENDER_D(1024, 1); else RENDER_D(1024, 0); }
+#define RENDER_D(TT, SS, PP) hipLaunchKernelGGL((k_render_delta<G, TT, SS, PP>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, sh, \
+                                                e->atlas, e->lut, e->n_tiles)
+#define RENDER_DP(TT, SS) do { if (pb == 128) RENDER_D(TT, SS, 128); else RENDER_D(TT, SS, 64); } while (0)
+        if (T == 512) { if (e->render_delta_sched == 1) RENDER_DP(512, 1); else RENDER_DP(512, 0); }
+        else { if (e->render_delta_sched == 1) RENDER_DP(1024, 1); else RENDER_DP(1024, 0); }
+#undef RENDER_DP
 #undef RENDER_D
         HIP_TRY(hipGetLastError());
         return call.leave();
@@ -3998,6 +4139,10 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     else if (!strcmp(name, "render_delta_tpb")) e->render_delta_tpb = v;
     else if (!strcmp(name, "render_delta_bpc")) e->render_delta_bpc = std::max(0, v);
     else if (!strcmp(name, "render_delta_from_step")) e->render_delta_from_step = v < 0 ? -1 : v != 0;
+    else if (!strcmp(name, "render_piece_bytes")) {
+        if (v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
+        e->render_piece_bytes = v;
+    }
     else if (!strcmp(name, "grid_render_bpc")) e->grid_bpc = std::max(0, v);
     else if (!strcmp(name, "step_prio")) e->step_prio = v;
     else if (!strcmp(name, "pregen_group")) e->pregen_group = v;
@@ -4051,6 +4196,7 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     else if (!strcmp(name, "render_delta_tpb")) *out = e->render_delta_tpb;
     else if (!strcmp(name, "render_delta_bpc")) *out = e->render_delta_bpc;
     else if (!strcmp(name, "render_delta_from_step")) *out = e->render_delta_from_step;
+    else if (!strcmp(name, "render_piece_bytes")) *out = e->render_piece_bytes;
     else if (!strcmp(name, "grid_render_bpc")) *out = e->grid_bpc;
     else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
     else if (!strcmp(name, "step_prio")) *out = e->step_prio;
