@@ -1,0 +1,325 @@
+// ------------------------------------------------------------------------------------------
+// Demonstrations that stay on the device (babyai_amd/imitation.py DemoStore / DemoBatch):
+//   k_demo_spans  one chunk of bbai_bot_rollout history -> every stream's first solved episode (demos.py scan_chunk)
+//   k_demo_pack   the spans of up to C history chunks   -> the store's flat arrays
+//   k_demo_batch  a sorted list of demos of a store     -> the flat batch of imitation.py:226-251 (or a sub-store)
+// The two copies write ALIGNED 16-byte chunks of one contiguous destination; a chunk's bytes come from at most two source
+// runs (147-byte history rows in k_demo_pack, whole demos in k_demo_batch), each fetched as two aligned 16-byte loads
+// and byte-aligned in registers.  Every unaligned 16-byte window that is fetched lies INSIDE a source run (a chunk that
+// crosses into the next run takes the run's last 16 bytes and the next run's first 16, and shifts the pair), so the
+// aligned loads around it stay inside any allocation that starts 16-byte aligned and is a multiple of 16 bytes long.
+// ------------------------------------------------------------------------------------------
+#pragma once
+
+namespace bbai {
+
+constexpr int DEMO_BLOCK = 256;                 // lanes per block
+constexpr int DEMO_UNROLL = 2;                  // 16-byte chunks per lane: both chunks' loads are issued before the first store
+constexpr int DEMO_BLOCK_BYTES = DEMO_BLOCK * DEMO_UNROLL * 16;
+constexpr int DEMO_SLICE = 64;                  // runs a block can meet: 8192 / 147 + 2 = 57 frames, every demo holds at least one
+constexpr uint32_t DEMO_ROW = 147;              // bytes of one 7x7x3 frame
+constexpr uint32_t DEMO_DIV147 = 29217465u;     // ceil(2^32 / 147): __umulhi(x, .) == x / 147 for x < 7 * 10^7
+
+struct DemoChunkPtrs {                          // include/bbai.h bbai_demo_chunk: the outputs of one bbai_bot_rollout call
+    const uint8_t* image; const uint8_t* dir; const uint8_t* action; const uint8_t* tokens;
+};
+
+// bytes [sh, sh + 16) of the 32 bytes {lo, hi}, sh = 0..15.  Scalars only: a select between two elements of a private array becomes a
+// dynamically indexed load, and the array then lives in scratch or LDS instead of registers.
+__device__ __forceinline__ u32x4 demo_shr(const u32x4 lo, const u32x4 hi, uint32_t sh) {
+    const bool d2 = (sh & 8u) != 0, d1 = (sh & 4u) != 0;
+    const uint32_t b = sh & 3u;
+    const uint32_t a0 = d2 ? lo.z : lo.x, a1 = d2 ? lo.w : lo.y, a2 = d2 ? hi.x : lo.z, a3 = d2 ? hi.y : lo.w, a4 = d2 ? hi.z : hi.x, a5 = d2 ? hi.w : hi.y;
+    const uint32_t c0 = d1 ? a1 : a0, c1 = d1 ? a2 : a1, c2 = d1 ? a3 : a2, c3 = d1 ? a4 : a3, c4 = d1 ? a5 : a4;
+    u32x4 w;
+    w.x = __builtin_amdgcn_alignbyte(c1, c0, b);
+    w.y = __builtin_amdgcn_alignbyte(c2, c1, b);
+    w.z = __builtin_amdgcn_alignbyte(c3, c2, b);
+    w.w = __builtin_amdgcn_alignbyte(c4, c3, b);
+    return w;
+}
+
+// the 16 bytes at p (any byte phase): the two aligned 16-byte words around them.  All 16 bytes must be readable.
+struct DemoWindow {
+    u32x4 lo, hi; uint32_t phase;
+    __device__ __forceinline__ void load(const uint8_t* p) {
+        phase = (uint32_t)((uintptr_t)p & 15u);
+        const u32x4* q = (const u32x4*)(p - phase);
+        lo = q[0];
+        hi = lo;
+        if (phase) hi = q[1];                   // (phase 0: the second word may lie behind the allocation)
+    }
+    __device__ __forceinline__ u32x4 get() const {
+        return demo_shr(lo, hi, phase);
+    }
+};
+
+// One destination chunk: `a` alone (shift 0), or the last `16 - shift` bytes of the window `a` followed by the first
+// `shift` bytes of the window `b` (a = the 16 bytes that END run A, b = the 16 bytes that BEGIN run B).
+struct DemoPiece {
+    DemoWindow a, b; uint32_t shift; bool two;
+    __device__ __forceinline__ void load(const uint8_t* pa, const uint8_t* pb, uint32_t sh) {
+        shift = sh; two = pb != nullptr;
+        a.load(pa);
+        if (two) b.load(pb);
+    }
+    __device__ __forceinline__ u32x4 get() const {
+        const u32x4 wa = a.get();
+        if (!two) return wa;
+        const u32x4 wb = b.get();
+        return demo_shr(wa, wb, shift);
+    }
+};
+
+// aligned 16-byte store of chunk `q` of `dst`; the destination's last chunk may be short
+__device__ __forceinline__ void demo_store(uint8_t* dst, int64_t q, const u32x4 v, int64_t total_bytes) {
+    const int64_t left = total_bytes - q * 16;
+    if (left >= 16) { ((u32x4*)dst)[q] = v; return; }
+    for (int i = 0; i < (int)left; ++i) {
+        const uint32_t w = i < 4 ? v.x : i < 8 ? v.y : i < 12 ? v.z : v.w;
+        dst[q * 16 + i] = (uint8_t)(w >> (8 * (i & 3)));
+    }
+}
+
+// index of the run that holds frame f: the largest k in [0, count) with start[k] <= f (start ascending, start[0] <= f)
+__device__ __forceinline__ int64_t demo_find(const int64_t* __restrict__ start, int64_t count, int64_t f) {
+    int64_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (start[mid] <= f) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the same in the block's slice (frames relative to the block's first): the largest j with s_rel[j] <= x
+__device__ __forceinline__ int demo_find_lds(const int32_t* s_rel, int x) {
+    int j = 0;
+#pragma unroll
+    for (int step = DEMO_SLICE / 2; step > 0; step >>= 1)
+        if (s_rel[j + step] <= x) j += step;
+    return j;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_demo_spans : lane = stream (babyai_amd/demos.py scan_chunk, which stays this kernel's oracle).  done / gave_up / reward
+// are [chunk][n]: at every t a wave reads 64 consecutive streams.  Carry per stream: last_done (global index of the latest
+// episode end), open (still looking), span (first and last global step of the first solved episode).  open_count receives
+// the number of streams still open after this chunk: one add per wave that has any (nobody waits for the sum).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_demo_spans(int64_t n, int chunk, const uint8_t* __restrict__ done, const uint8_t* __restrict__ gave_up,
+                                                   const float* __restrict__ reward, int g0, int filter_steps, int32_t* __restrict__ last_done,
+                                                   uint8_t* __restrict__ open, int32_t* __restrict__ span, unsigned long long* __restrict__ open_count) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    bool still = false;
+    if (i < n) {
+        int32_t last = last_done[i];
+        const bool was_open = open[i] != 0;
+        bool found = false;
+        int32_t first = 0, at = 0;
+        for (int t = 0; t < chunk; ++t) {
+            const int64_t k = (int64_t)t * n + i;
+            if (!done[k]) continue;
+            const int32_t g = g0 + t;
+            bool ok = gave_up[k] == 0 && reward[k] > 0.0f;
+            if (filter_steps) ok = ok && (g - last) <= filter_steps;       // episode length = g - (last + 1) + 1
+            if (ok && !found) { found = true; first = last + 1; at = g; }
+            last = g;
+        }
+        last_done[i] = last;
+        if (was_open && found) { span[2 * i] = first; span[2 * i + 1] = at; open[i] = 0; }
+        still = was_open && !found;
+    }
+    const unsigned long long bal = __ballot(still);
+    if (bal != 0ull && threadIdx.x == 0) atomicAdd(open_count, (unsigned long long)__popcll(bal));
+}
+
+// ------------------------------------------------------------------------------------------
+// k_demo_pack : blocks [0, img_blocks) copy the frames (8 KiB of the store's image array each), the blocks behind them
+// write direction / action (lane = 4 frames, one aligned dword of each) and the token rows (lane = 8 of a row's 72 bytes).
+// Frame f of the store = history row g = span[k][0] + (f - offset[k]) of stream k, i.e. row g % T of chunk g / T.
+// ------------------------------------------------------------------------------------------
+struct DemoPackArgs {
+    int64_t n, frames; int T; int64_t img_blocks, meta_blocks;
+    const DemoChunkPtrs* __restrict__ chunks; const int32_t* __restrict__ span; const int64_t* __restrict__ offset;
+    uint8_t* image; uint8_t* dir; uint8_t* action; uint8_t* tokens;
+};
+
+__device__ __forceinline__ int64_t demo_pack_row(const DemoPackArgs& a, int64_t k, int64_t g, int& c) {
+    c = (int)(g / a.T);
+    return (g - (int64_t)c * a.T) * a.n + k;
+}
+
+// source address of frame `rel` (relative to the block's first frame) in the history
+__device__ __forceinline__ const uint8_t* demo_pack_src(const DemoPackArgs& a, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo, int rel) {
+    const int j = demo_find_lds(s_rel, rel);
+    int c;
+    const int64_t row = demo_pack_row(a, k_lo + j, (int64_t)s_g0[j] + (rel - s_rel[j]), c);
+    return a.chunks[c].image + row * DEMO_ROW;
+}
+
+// the piece of the chunk at byte x relative to the block's first frame f_lo
+__device__ __forceinline__ void demo_pack_piece(const DemoPackArgs& a, DemoPiece& p, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo,
+                                                int64_t f_lo, uint32_t x) {
+    const uint32_t fr = __umulhi(x, DEMO_DIV147), r = x - fr * DEMO_ROW;
+    const uint8_t* s0 = demo_pack_src(a, s_rel, s_g0, k_lo, (int)fr);
+    if (r + 16 <= DEMO_ROW) { p.load(s0 + r, nullptr, 0); return; }
+    const uint8_t* tail = s0 + DEMO_ROW - 16;
+    const uint8_t* s1 = f_lo + fr + 1 < a.frames ? demo_pack_src(a, s_rel, s_g0, k_lo, (int)fr + 1) : tail;      // (behind the store's last frame: filler, never stored)
+    p.load(tail, s1, 16 - (DEMO_ROW - r));
+}
+
+__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
+    __shared__ int32_t s_rel[DEMO_SLICE + 1];   // first frame of the block's demos, relative to the block's first frame
+    __shared__ int32_t s_g0[DEMO_SLICE];        // span[k][0] of those demos
+    __shared__ int64_t s_klo;                   // the first of them
+    const int tid = threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    if (blk >= a.img_blocks + a.meta_blocks) {  // token rows: 9 pieces of 8 bytes per demo (both sides are 8-byte aligned)
+        const int64_t p = (blk - a.img_blocks - a.meta_blocks) * DEMO_BLOCK + tid;
+        const int64_t k = p / 9;
+        if (k >= a.n) return;
+        int c;
+        const int64_t row = demo_pack_row(a, k, a.span[2 * k], c);
+        const int piece = (int)(p - k * 9);
+        ((uint2*)a.tokens)[p] = ((const uint2*)(a.chunks[c].tokens + row * 72))[piece];
+        return;
+    }
+    if (blk >= a.img_blocks) {                  // direction / action: 4 frames per lane
+        const int64_t f0 = ((blk - a.img_blocks) * DEMO_BLOCK + tid) * 4;
+        if (f0 >= a.frames) return;
+        int64_t k = demo_find(a.offset, a.n, f0);
+        uint32_t d = 0, act = 0;
+        const int cnt = (int)(a.frames - f0 < 4 ? a.frames - f0 : 4);
+        for (int i = 0; i < cnt; ++i) {
+            const int64_t f = f0 + i;
+            while (a.offset[k + 1] <= f) ++k;
+            int c;
+            const int64_t row = demo_pack_row(a, k, a.span[2 * k] + (f - a.offset[k]), c);
+            d |= (uint32_t)a.chunks[c].dir[row] << (8 * i);
+            act |= (uint32_t)a.chunks[c].action[row] << (8 * i);
+        }
+        if (cnt == 4) { ((uint32_t*)a.dir)[f0 >> 2] = d; ((uint32_t*)a.action)[f0 >> 2] = act; }
+        else for (int i = 0; i < cnt; ++i) { a.dir[f0 + i] = (uint8_t)(d >> (8 * i)); a.action[f0 + i] = (uint8_t)(act >> (8 * i)); }
+        return;
+    }
+    const int64_t total = a.frames * (int64_t)DEMO_ROW;
+    const int64_t byte0 = blk * DEMO_BLOCK_BYTES;
+    const int64_t f_lo = byte0 / DEMO_ROW;
+    const uint32_t r_lo = (uint32_t)(byte0 - f_lo * DEMO_ROW);
+    if (tid < 64) {                             // the block's slice of `offset` (wave 0; the search is wave-uniform)
+        const int64_t k0 = demo_find(a.offset, a.n, f_lo);
+        const int64_t k = k0 + tid;
+        const int64_t rel = k <= a.n ? a.offset[k] - f_lo : (int64_t)0x7fffffff;
+        s_rel[tid] = (int32_t)(rel < 0x7fffffff ? rel : 0x7fffffff);
+        s_g0[tid] = k < a.n ? a.span[2 * k] : 0;
+        if (tid == 0) { s_rel[DEMO_SLICE] = 0x7fffffff; s_klo = k0; }
+    }
+    __syncthreads();
+    const int64_t k_lo = s_klo;
+    // the two chunks of a lane as two named pieces (no arrays: everything stays in registers); both pieces' loads are issued
+    // before the first store
+    const int64_t q0 = blk * (DEMO_BLOCK * DEMO_UNROLL) + tid, q1 = q0 + DEMO_BLOCK;
+    const bool v0 = q0 * 16 < total, v1 = q1 * 16 < total;
+    DemoPiece p0, p1;
+    if (v0) demo_pack_piece(a, p0, s_rel, s_g0, k_lo, f_lo, r_lo + (uint32_t)tid * 16u);
+    if (v1) demo_pack_piece(a, p1, s_rel, s_g0, k_lo, f_lo, r_lo + (uint32_t)(DEMO_BLOCK + tid) * 16u);
+    if (v0) demo_store(a.image, q0, p0.get(), total);
+    if (v1) demo_store(a.image, q1, p1.get(), total);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_demo_batch : the batch gather.  order[b] = the store's demo that comes b-th, dst_start[b] its first frame in the result
+// (int64[B + 1], the last entry = the result's frame count), offset = the store's.  Blocks [0, img_blocks) copy the images
+// (the bytes of demo order[b] are one contiguous run on both sides, at any byte phase on both sides); the blocks behind them
+// write the per-frame fields, 4 frames per lane: batch form (action int64, done, mask float32, episode_ids int64 non-null:
+// imitation.py:240-250) or store form (dir / action uint8: DemoStore.select).
+// ------------------------------------------------------------------------------------------
+struct DemoBatchArgs {
+    int64_t B, frames, img_blocks;
+    const int64_t* __restrict__ order; const int64_t* __restrict__ dst_start; const int64_t* __restrict__ offset;
+    const uint8_t* __restrict__ src_image; const uint8_t* __restrict__ src_dir; const uint8_t* __restrict__ src_action;
+    uint8_t* image; int64_t* action64; uint8_t* done; float* mask; int64_t* episode; uint8_t* dir8; uint8_t* action8;
+};
+
+// the piece of the chunk at byte x relative to the block's first frame f_lo (destination byte `base`)
+__device__ __forceinline__ void demo_batch_piece(const DemoBatchArgs& a, DemoPiece& p, const int32_t* s_rel, const int64_t* s_delta, int64_t f_lo,
+                                                 int64_t base, uint32_t x) {
+    const int fr = (int)__umulhi(x, DEMO_DIV147);
+    const int j = demo_find_lds(s_rel, fr);
+    const int64_t end_rel = (int64_t)s_rel[j + 1] * DEMO_ROW;              // where demo j ends, relative to frame f_lo (int64: the sentinel is large)
+    const uint8_t* sa = a.src_image + base + s_delta[j] * (int64_t)DEMO_ROW;      // source byte of "relative byte 0" for demo j
+    if ((int64_t)x + 16 <= end_rel) { p.load(sa + x, nullptr, 0); return; }
+    const uint8_t* tail = sa + end_rel - 16;
+    const bool next = s_rel[j + 1] + f_lo < a.frames;                      // (behind the result's last demo: filler, never stored)
+    p.load(tail, next ? a.src_image + base + s_delta[j + 1] * (int64_t)DEMO_ROW + end_rel : tail, (uint32_t)(16 - (end_rel - x)));
+}
+
+__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_batch(DemoBatchArgs a) {
+    __shared__ int32_t s_rel[DEMO_SLICE + 1];   // first frame of the block's demos in the result, relative to the block's first frame
+    __shared__ int64_t s_delta[DEMO_SLICE];     // source frame - destination frame of those demos
+    const int tid = threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    if (blk >= a.img_blocks) {
+        const int64_t f0 = ((blk - a.img_blocks) * DEMO_BLOCK + tid) * 4;
+        if (f0 >= a.frames) return;
+        int64_t b = demo_find(a.dst_start, a.B, f0);
+        const int cnt = (int)(a.frames - f0 < 4 ? a.frames - f0 : 4);
+        int64_t act[4], ep[4]; float m[4]; uint32_t dn = 0, d8 = 0, a8 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            act[i] = 0; ep[i] = 0; m[i] = 0.0f;
+            if (i >= cnt) continue;
+            const int64_t f = f0 + i;
+            while (a.dst_start[b + 1] <= f) ++b;
+            const int64_t s = a.offset[a.order[b]] + (f - a.dst_start[b]);
+            const uint32_t av = a.src_action[s];
+            act[i] = (int64_t)av; ep[i] = b; m[i] = f == a.dst_start[b] ? 0.0f : 1.0f;
+            dn |= (uint32_t)(f + 1 == a.dst_start[b + 1]) << (8 * i);
+            a8 |= av << (8 * i);
+            if (a.dir8) d8 |= (uint32_t)a.src_dir[s] << (8 * i);
+        }
+        if (cnt == 4) {
+            if (a.action64) {
+                typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                i64x2* ao = (i64x2*)(a.action64 + f0); i64x2* eo = (i64x2*)(a.episode + f0);
+                ao[0] = i64x2{act[0], act[1]}; ao[1] = i64x2{act[2], act[3]};
+                eo[0] = i64x2{ep[0], ep[1]}; eo[1] = i64x2{ep[2], ep[3]};
+                *(f32x4*)(a.mask + f0) = f32x4{m[0], m[1], m[2], m[3]};
+                ((uint32_t*)a.done)[f0 >> 2] = dn;
+            } else {
+                ((uint32_t*)a.dir8)[f0 >> 2] = d8; ((uint32_t*)a.action8)[f0 >> 2] = a8;
+            }
+        } else
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i >= cnt) break;
+            if (a.action64) { a.action64[f0 + i] = act[i]; a.episode[f0 + i] = ep[i]; a.mask[f0 + i] = m[i]; a.done[f0 + i] = (uint8_t)(dn >> (8 * i)); }
+            else { a.dir8[f0 + i] = (uint8_t)(d8 >> (8 * i)); a.action8[f0 + i] = (uint8_t)(a8 >> (8 * i)); }
+        }
+        return;
+    }
+    const int64_t total = a.frames * (int64_t)DEMO_ROW;
+    const int64_t byte0 = blk * DEMO_BLOCK_BYTES;
+    const int64_t f_lo = byte0 / DEMO_ROW;
+    const int64_t base = f_lo * DEMO_ROW;       // destination byte of the block's first frame
+    const uint32_t r_lo = (uint32_t)(byte0 - base);
+    if (tid < 64) {
+        const int64_t b_lo = demo_find(a.dst_start, a.B, f_lo);
+        const int64_t b = b_lo + tid;
+        const int64_t rel = b <= a.B ? a.dst_start[b] - f_lo : (int64_t)0x7fffffff;
+        s_rel[tid] = (int32_t)(rel < 0x7fffffff ? rel : 0x7fffffff);
+        s_delta[tid] = b < a.B ? a.offset[a.order[b]] - a.dst_start[b] : 0;
+        if (tid == 0) s_rel[DEMO_SLICE] = 0x7fffffff;
+    }
+    __syncthreads();
+    const int64_t q0 = blk * (DEMO_BLOCK * DEMO_UNROLL) + tid, q1 = q0 + DEMO_BLOCK;
+    const bool v0 = q0 * 16 < total, v1 = q1 * 16 < total;
+    DemoPiece p0, p1;
+    if (v0) demo_batch_piece(a, p0, s_rel, s_delta, f_lo, base, r_lo + (uint32_t)tid * 16u);
+    if (v1) demo_batch_piece(a, p1, s_rel, s_delta, f_lo, base, r_lo + (uint32_t)(DEMO_BLOCK + tid) * 16u);
+    if (v0) demo_store(a.image, q0, p0.get(), total);
+    if (v1) demo_store(a.image, q1, p1.get(), total);
+}
+
+}  // namespace bbai

@@ -2464,6 +2464,8 @@ __global__ __launch_bounds__(64) void k_gae(int64_t P, int T, const float* __res
     }
 }
 
+#include "bbai_demo.hpp"
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -4092,6 +4094,60 @@ int bbai_gae(int64_t num_envs, int num_frames, const float* rewards, const float
         ARG_FAIL("null pointer or empty rollout");
     hipLaunchKernelGGL(k_gae, dim3((unsigned)((num_envs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, num_envs, num_frames, rewards, values,
                        masks, last_mask, last_value, (float)discount, (float)(discount * gae_lambda), advantage, returnn);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+// The three entries of the demo store (bbai_demo.hpp): handle-free like bbai_gae, launched on the current device.
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+int bbai_demo_spans(int64_t n, int chunk, const uint8_t* done, const uint8_t* gave_up, const float* reward, int64_t g0, int filter_steps,
+                    int32_t* last_done, uint8_t* open, int32_t* span, uint64_t* open_count, void* stream) {
+    if (n <= 0 || chunk <= 0 || !done || !gave_up || !reward || !last_done || !open || !span || !open_count) ARG_FAIL("null pointer or empty chunk");
+    if (g0 < 0 || g0 + chunk > 0x7fffffff || filter_steps < 0) ARG_FAIL("step index out of range");
+    HIP_TRY(hipMemsetAsync(open_count, 0, sizeof(uint64_t), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_demo_spans, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, chunk, done, gave_up, reward, (int)g0,
+                       filter_steps, last_done, open, span, (unsigned long long*)open_count);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+int bbai_demo_pack(int64_t n, int64_t frames, int chunk_steps, const bbai_demo_chunk* chunks, const int32_t* span, const int64_t* offset,
+                   uint8_t* image_out, uint8_t* dir_out, uint8_t* action_out, uint8_t* tokens_out, void* stream) {
+    if (n <= 0 || frames < n || chunk_steps <= 0 || !chunks || !span || !offset || !image_out || !dir_out || !action_out || !tokens_out)
+        ARG_FAIL("null pointer or empty store");
+    if (!aligned16(image_out) || !aligned16(dir_out) || !aligned16(action_out) || !aligned16(tokens_out)) ARG_FAIL("outputs must be 16-byte aligned");
+    static_assert(sizeof(bbai_demo_chunk) == sizeof(DemoChunkPtrs), "bbai_demo_chunk");
+    DemoPackArgs a;
+    a.n = n; a.frames = frames; a.T = chunk_steps;
+    a.img_blocks = (frames * (int64_t)DEMO_ROW + DEMO_BLOCK_BYTES - 1) / DEMO_BLOCK_BYTES;
+    a.meta_blocks = ((frames + 3) / 4 + DEMO_BLOCK - 1) / DEMO_BLOCK;
+    const int64_t tok_blocks = (n * 9 + DEMO_BLOCK - 1) / DEMO_BLOCK;
+    a.chunks = (const DemoChunkPtrs*)chunks; a.span = span; a.offset = offset;
+    a.image = image_out; a.dir = dir_out; a.action = action_out; a.tokens = tokens_out;
+    if (a.img_blocks + a.meta_blocks + tok_blocks > 0x7fffffff) ARG_FAIL("store too large for one launch");
+    hipLaunchKernelGGL(k_demo_pack, dim3((unsigned)(a.img_blocks + a.meta_blocks + tok_blocks)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+int bbai_demo_batch(int64_t count, int64_t frames, const int64_t* order, const int64_t* dst_start, const int64_t* offset, const uint8_t* src_image,
+                    const uint8_t* src_dir, const uint8_t* src_action, uint8_t* image_out, int64_t* action_out, uint8_t* done_out, float* mask_out,
+                    int64_t* episode_ids_out, uint8_t* dir8_out, uint8_t* action8_out, void* stream) {
+    if (count <= 0 || frames < count || !order || !dst_start || !offset || !src_image || !src_action || !image_out) ARG_FAIL("null pointer or empty batch");
+    const bool batch_form = action_out && done_out && mask_out && episode_ids_out && !dir8_out && !action8_out;
+    const bool store_form = !action_out && !done_out && !mask_out && !episode_ids_out && dir8_out && action8_out && src_dir;
+    if (!batch_form && !store_form) ARG_FAIL("pass either action / done / mask / episode_ids or dir8 / action8 (with src_dir)");
+    if (!aligned16(src_image) || !aligned16(image_out) || !aligned16(action_out) || !aligned16(done_out) || !aligned16(mask_out) ||
+        !aligned16(episode_ids_out) || !aligned16(dir8_out) || !aligned16(action8_out)) ARG_FAIL("src_image and the outputs must be 16-byte aligned");
+    DemoBatchArgs a;
+    a.B = count; a.frames = frames;
+    a.img_blocks = (frames * (int64_t)DEMO_ROW + DEMO_BLOCK_BYTES - 1) / DEMO_BLOCK_BYTES;
+    const int64_t meta_blocks = ((frames + 3) / 4 + DEMO_BLOCK - 1) / DEMO_BLOCK;
+    a.order = order; a.dst_start = dst_start; a.offset = offset; a.src_image = src_image; a.src_dir = src_dir; a.src_action = src_action;
+    a.image = image_out; a.action64 = action_out; a.done = done_out; a.mask = mask_out; a.episode = episode_ids_out; a.dir8 = dir8_out; a.action8 = action8_out;
+    if (a.img_blocks + meta_blocks > 0x7fffffff) ARG_FAIL("batch too large for one launch");
+    hipLaunchKernelGGL(k_demo_batch, dim3((unsigned)(a.img_blocks + meta_blocks)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }

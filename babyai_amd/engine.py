@@ -92,6 +92,10 @@ def load_library():
         lib.bbai_step_tap_set.argtypes = [P, P, I64]
         lib.bbai_step_tapped.argtypes = [P, P, P, P, P, P, P, I32, P, P, P, P, P]
     lib.bbai_gae.argtypes = [I64, I32, P, P, P, P, P, ctypes.c_double, ctypes.c_double, P, P, P]
+    if hasattr(lib, "bbai_demo_spans"):
+        lib.bbai_demo_spans.argtypes = [I64, I32, P, P, P, I64, I32, P, P, P, P, P]
+        lib.bbai_demo_pack.argtypes = [I64, I64, I32, P, P, P, P, P, P, P, P]
+        lib.bbai_demo_batch.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]
     lib.bbai_set_call_events.argtypes = [P, I32]
     lib.bbai_profile.argtypes = [P, I32]
     lib.bbai_profile_read.argtypes = [P, P, P]
@@ -121,6 +125,7 @@ EXPORTED_SYMBOLS = (
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
     "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
+    "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch",
 )
 
 

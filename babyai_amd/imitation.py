@@ -1,0 +1,407 @@
+"""Demonstrations that stay on the device: the imitation loop's twin of `rollout.DeviceRollout`.
+
+The reference trains on demonstrations in `babyai/imitation.py`: a list of `(mission, packed images, directions, actions)`
+tuples (scripts/make_agent_demos.py:111-112) that every batch unpacks into Python lists of `(obs dict, action, done)`
+(`utils/demos.py:38-64 transform_demos`), sorts, flattens into a numpy object array and re-tokenises with a regex on every
+model call (`format.py:59-119`).  Here the same data never becomes Python objects:
+
+    store = DemoStore.collect("BabyAI-GoToLocal-v0", 100000, seed=0)          # the device expert; or DemoStore.from_reference(demos)
+    train, valid = store.select(perm[:90000]), store.select(perm[90000:])
+    log = run_epoch(acmodel, train, torch.randperm(len(train)), batch_size=256, recurrence=20, entropy_coef=0.01, optimizer=opt)
+
+`DemoStore` keeps D demonstrations with F frames as flat tensors (image uint8[F,7,7,3], direction / action uint8[F], tokens
+uint8[D,72] in `missions.VOCAB` ids, offset int64[D+1] on the device and mirrored on the host); `store.batch(indices)` builds
+the flat batch of imitation.py:226-251 and `run_batch` / `run_epoch` are `run_epoch_recurrence_one_batch` / `run_epoch_recurrence`
+over it (pinned to the reference's own functions by tests/test_imitation_host.py).  ROCm tensors go through the kernels of
+babyai_amd/csrc/bbai_demo.hpp (include/bbai.h bbai_demo_spans / bbai_demo_pack / bbai_demo_batch); host tensors take the same
+steps in torch ops, as `rollout.gae_env_major` does, so that the pin tests run without a GPU.
+"""
+import ctypes
+
+import numpy as np
+
+from . import missions
+from .preprocess import TensorDict, remap_table
+
+TOK_MAX = 72
+
+
+def _lib_stream(device):
+    import torch
+    from .engine import load_library
+    return load_library(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def demo_spans(done, gave_up, reward, g0, filter_steps, last_done, open_, span, open_count=None):
+    """`demos.scan_chunk` on tensors: one chunk of rollout history ([chunk, n] uint8 / uint8 / float32) and the carry
+    (last_done int32[n], open_ uint8[n], span int32[n, 2]), updated in place.  ROCm tensors: k_demo_spans, and the number of
+    streams still open is left in `open_count` (int64[1] on the device) and returned as that tensor -- reading it is the one
+    synchronisation of a chunk.  Host tensors: the same scan in torch ops, returns a 0-d tensor."""
+    import torch
+    chunk, n = done.shape
+    if done.is_cuda:
+        from .engine import _check
+        for t, dt in ((done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), (last_done, torch.int32), (open_, torch.uint8), (span, torch.int32)):
+            assert t.is_contiguous() and t.dtype == dt and t.device == done.device
+        with torch.cuda.device(done.device):
+            if open_count is None:
+                open_count = torch.zeros(1, dtype=torch.int64, device=done.device)
+            lib, stream = _lib_stream(done.device)
+            _check(lib, lib.bbai_demo_spans(n, chunk, done.data_ptr(), gave_up.data_ptr(), reward.data_ptr(), int(g0), int(filter_steps),
+                                            last_done.data_ptr(), open_.data_ptr(), span.data_ptr(), open_count.data_ptr(), stream), "bbai_demo_spans")
+        return open_count
+    done_b = done != 0
+    idx = torch.arange(g0, g0 + chunk, dtype=torch.int32).unsqueeze(1)                       # [chunk, 1]
+    ends = torch.cummax(torch.where(done_b, idx, torch.full_like(idx, -1)), dim=0).values   # latest episode end at or before each step
+    ends = torch.maximum(ends, last_done.unsqueeze(0))
+    before = torch.cat([last_done.unsqueeze(0), ends[:-1]], dim=0)                           # ... before each step
+    ok = done_b & (gave_up == 0) & (reward > 0)
+    if filter_steps:
+        ok &= (idx - before) <= filter_steps
+    found = ok.any(dim=0) & (open_ != 0)
+    first = ok.to(torch.uint8).argmax(dim=0)
+    cols = found.nonzero().reshape(-1)
+    span[cols, 0] = before[first[cols], cols] + 1
+    span[cols, 1] = (g0 + first[cols]).to(torch.int32)
+    open_[cols] = 0
+    last_done.copy_(ends[-1])
+    return (open_ != 0).sum()
+
+
+def _gather(offset, order, dst_start, frames, src_image, src_dir, src_action, batch_form):
+    """The segmented copy behind `batch` and `select`: demos `order` (int64[B] on the store's device) of a store laid end to
+    end.  Returns (image, action int64, done, mask, episode_ids) or (image, direction, action uint8)."""
+    import torch
+    dev = src_image.device
+    B = int(order.shape[0])
+    image = torch.empty((frames, 7, 7, 3), dtype=torch.uint8, device=dev)
+    if batch_form:
+        out = [torch.empty(frames, dtype=torch.int64, device=dev), torch.empty(frames, dtype=torch.bool, device=dev),
+               torch.empty((frames, 1), dtype=torch.float32, device=dev), torch.empty(frames, dtype=torch.int64, device=dev)]
+    else:
+        out = [torch.empty(frames, dtype=torch.uint8, device=dev), torch.empty(frames, dtype=torch.uint8, device=dev)]
+    if src_image.is_cuda:
+        from .engine import _check
+        for t in (offset, order, dst_start, src_image, src_dir, src_action):
+            assert t.is_contiguous() and t.device == dev
+        ptrs = [t.data_ptr() for t in out]
+        args = ptrs + [None, None] if batch_form else [None] * 4 + ptrs
+        with torch.cuda.device(dev):
+            lib, stream = _lib_stream(dev)
+            _check(lib, lib.bbai_demo_batch(B, frames, order.data_ptr(), dst_start.data_ptr(), offset.data_ptr(), src_image.data_ptr(),
+                                            src_dir.data_ptr(), src_action.data_ptr(), image.data_ptr(), *(args + [stream])), "bbai_demo_batch")
+        return [image] + out
+    lens = dst_start[1:] - dst_start[:-1]
+    episode = torch.repeat_interleave(torch.arange(B), lens)
+    within = torch.arange(frames) - dst_start[:-1][episode]
+    src = offset[order][episode] + within
+    image.copy_(src_image[src])
+    if batch_form:
+        out[0].copy_(src_action[src])
+        out[1].copy_(within == lens[episode] - 1)
+        out[2].copy_((within != 0).to(torch.float32).unsqueeze(1))
+        out[3].copy_(episode)
+    else:
+        out[0].copy_(src_dir[src])
+        out[1].copy_(src_action[src])
+    return [image] + out
+
+
+class DemoBatch(object):
+    """The flat batch of imitation.py:226-251: demos longest first (stable), frames of demo b at `inds[b] : inds[b] + lengths[b]`.
+    image uint8[Fb,7,7,3], action int64[Fb], done bool[Fb], mask float32[Fb,1], episode_ids int64[Fb], inds int64[B],
+    instr int64[B,L'] on the device; order (the store's demo numbers in batch order), lengths and counts on the host."""
+
+    def __init__(self, image, action, done, mask, episode_ids, inds, instr, order, lengths):
+        self.image, self.action, self.done, self.mask, self.episode_ids = image, action, done, mask, episode_ids
+        self.inds, self.instr, self.order, self.lengths = inds, instr, order, lengths
+        self.num_frames = int(lengths.sum())
+        # counts[t] = demos with more than t frames = how many of the sorted demos the reference's first loop still visits at step t
+        self.counts = np.searchsorted(-lengths, -np.arange(int(lengths[0])), side="left") if len(lengths) else np.zeros(0, np.int64)
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def active(self, t):
+        """Flat indices of step t of every demo that has one (imitation.py:257-278): longest first, so a prefix of `inds`."""
+        return self.inds[:int(self.counts[t])] + t
+
+    def starting_indexes(self, recurrence):
+        """imitation.py:183-187"""
+        import torch
+        idx = torch.arange(0, self.num_frames, recurrence, device=self.image.device)
+        return idx if self.num_frames % recurrence == 0 else idx[:-1]
+
+
+class DemoStore(object):
+    def __init__(self, image, direction, action, tokens, offset_host):
+        import torch
+        self.image, self.direction, self.action, self.tokens = image, direction, action, tokens
+        self.offset_host = np.ascontiguousarray(offset_host, dtype=np.int64)
+        self.offset = torch.as_tensor(self.offset_host, device=image.device)
+        self.device = image.device
+        assert image.shape[0] == direction.shape[0] == action.shape[0] == int(self.offset_host[-1])
+        assert tokens.shape[0] == len(self.offset_host) - 1
+        self._ntok = None
+
+    def __len__(self):
+        return len(self.offset_host) - 1
+
+    @property
+    def num_frames(self):
+        return int(self.offset_host[-1])
+
+    @property
+    def lengths(self):
+        return np.diff(self.offset_host)
+
+    # ---- ways in ----
+    @classmethod
+    def _from_arrays(cls, image, direction, action, tokens, offset, device="cpu"):
+        import torch
+        t = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.uint8), device=device) for a in (image, direction, action, tokens)]
+        return cls(t[0].reshape(-1, 7, 7, 3), t[1].reshape(-1), t[2].reshape(-1), t[3].reshape(-1, TOK_MAX), offset)
+
+    @classmethod
+    def from_reference(cls, demos, device="cpu", unpack=None):
+        """From the reference's list of (mission, images, directions, actions); `unpack=blosc.unpack_array` for packed images."""
+        images = [np.asarray(unpack(d[1]) if unpack else d[1], dtype=np.uint8).reshape(-1, 7, 7, 3) for d in demos]
+        lens = [len(d[3]) for d in demos]
+        for im, d, n in zip(images, demos, lens):
+            assert im.shape[0] == len(d[2]) == n, "error transforming demos"       # utils/demos.py:55
+        tokens = np.zeros((len(demos), TOK_MAX), dtype=np.uint8)
+        for k, d in enumerate(demos):
+            ids = missions.tokenize(d[0])
+            tokens[k, :len(ids)] = ids
+        cat = np.concatenate
+        return cls._from_arrays(cat(images) if images else np.zeros((0, 7, 7, 3), np.uint8), cat([np.asarray(d[2], np.uint8) for d in demos]),
+                               cat([np.asarray(d[3], np.uint8) for d in demos]), tokens, np.concatenate([[0], np.cumsum(lens)]), device)
+
+    @classmethod
+    def load(cls, path, device="cpu"):
+        with np.load(path) as f:
+            return cls._from_arrays(f["image"], f["direction"], f["action"], f["tokens"], f["offset"], device)
+
+    @classmethod
+    def collect(cls, env_name, n_episodes, seed, device="cuda:0", batch=32768, filter_steps=0, max_steps=None):
+        """The contract of `demos.generate_demos` (demo k = the first episode of stream seed + k that the expert solves), with the
+        result left on the device: per chunk of rollout history one counter crosses PCIe, per batch of streams its lengths."""
+        import torch
+        parts = [_collect_batch(env_name, seed + start, min(batch, n_episodes - start), device, filter_steps, max_steps)
+                 for start in range(0, n_episodes, batch)]
+        if len(parts) == 1:
+            return cls(*parts[0])
+        lens = np.concatenate([np.diff(p[4]) for p in parts])
+        return cls(*[torch.cat([p[i] for p in parts]) for i in range(4)], np.concatenate([[0], np.cumsum(lens)]))
+
+    # ---- ways out ----
+    def to_reference(self, pack=None):
+        """The reference's tuples; with `DemoStore.collect` in front of it, interchangeable with `demos.generate_demos`."""
+        img, dirs, acts = self.image.cpu().numpy(), self.direction.cpu().numpy().tolist(), self.action.cpu().numpy().tolist()
+        toks, ends = self.tokens.cpu().numpy(), self.offset_host.tolist()
+        text, out = {}, []
+        for k in range(len(self)):
+            key = toks[k].tobytes()
+            mission = text.get(key)
+            if mission is None:
+                mission = text[key] = missions.detokenize(key)
+            lo, hi = ends[k], ends[k + 1]
+            stack = img[lo:hi]
+            out.append((mission, pack(stack) if pack else stack, dirs[lo:hi], acts[lo:hi]))
+        return out
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, image=self.image.cpu().numpy(), direction=self.direction.cpu().numpy(), action=self.action.cpu().numpy(),
+                     tokens=self.tokens.cpu().numpy(), offset=self.offset_host)
+
+    def _indices(self, indices):
+        """(host int64 array, device int64 tensor) of demo numbers from a host sequence or a tensor"""
+        import torch
+        if isinstance(indices, torch.Tensor):
+            dev = indices.to(device=self.device, dtype=torch.int64).contiguous()
+            host = indices.cpu().numpy().astype(np.int64)        # (a device tensor is read back here, B numbers: the sort by length and the
+                                                                 #  frame count of the result are the host's; pass host indices to avoid the wait)
+        else:
+            host = np.ascontiguousarray(indices, dtype=np.int64)
+            dev = torch.as_tensor(host, device=self.device)
+        if host.size and (host.min() < 0 or host.max() >= len(self)):
+            raise IndexError("demo index out of range")
+        return host, dev
+
+    def select(self, indices):
+        """A new store holding demos `indices` in that order (device copy): the train / validation split."""
+        import torch
+        host, order = self._indices(indices)
+        start = np.concatenate([[0], np.cumsum(self.lengths[host])]).astype(np.int64)
+        if host.size == 0:
+            return DemoStore(self.image[:0], self.direction[:0], self.action[:0], self.tokens[:0], start)
+        image, direction, action = _gather(self.offset, order, torch.as_tensor(start, device=self.device), int(start[-1]),
+                                           self.image, self.direction, self.action, False)
+        return DemoStore(image, direction, action, self.tokens[order], start)
+
+    def _token_counts(self):
+        """Tokens per mission, on the host (one read of D numbers, cached)."""
+        if self._ntok is None:
+            self._ntok = (self.tokens != 0).sum(dim=1).cpu().numpy()
+        return self._ntok
+
+    def batch(self, indices, vocab=None):
+        """The flat batch of demos `indices` (imitation.py:226-251).  `vocab`: None = the engine's fixed ids; a reference vocabulary
+        ({word: id} or the path of a vocab.json) = ids remapped as `TensorObssPreprocessor(env, vocab=...)` does."""
+        import torch
+        host, _ = self._indices(indices)
+        if host.size == 0:
+            raise ValueError("empty batch")
+        lens = self.lengths[host]
+        rank = np.argsort(-lens, kind="stable")                  # batch.sort(key=len, reverse=True) keeps the given order among equals
+        order_h, lens = host[rank], lens[rank]
+        start = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        order = torch.as_tensor(order_h, device=self.device)
+        start_d = torch.as_tensor(start, device=self.device)
+        image, action, done, mask, episode = _gather(self.offset, order, start_d, int(start[-1]), self.image, self.direction, self.action, True)
+        width = max(int(self._token_counts()[order_h].max()), 0)
+        instr = self.tokens[order][:, :width].to(torch.int64)    # padded to the batch's longest mission (format.py:59-75)
+        if vocab is not None:
+            if not isinstance(vocab, dict):
+                import json
+                with open(vocab) as f:
+                    vocab = json.load(f)
+            instr = torch.as_tensor(remap_table(vocab)[0], dtype=torch.int64, device=self.device)[instr]
+        return DemoBatch(image, action, done, mask, episode, start_d[:-1], instr, order_h, lens)
+
+
+def _collect_batch(env_name, seed, n, device, filter_steps, max_steps):
+    """One batch of streams of `DemoStore.collect` (demos._generate_batch with the scan and the gather left on the device)."""
+    import torch
+    from .engine import BatchedBabyAIEnv, _check
+    env = BatchedBabyAIEnv(env_name, n, device=device, seeds=[seed + k for k in range(n)], auto_reset=True)
+    try:
+        env.enable_instr_tokens()
+        env.reset()
+        dev = env.device
+        budget = max_steps if max_steps is not None else 64 * env.max_steps_bound
+        chunk = max(1, min(128, max(16, env.max_steps_bound // 4), budget))
+        free_b, _ = torch.cuda.mem_get_info(dev)
+        chunk_bytes = chunk * n * (147 + 72 + 6 + 4)
+        max_chunks = max(2, int(free_b // 2 // max(1, chunk_bytes)))          # the history's memory bound of generate_demos
+        with torch.cuda.device(dev):
+            last_done = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            open_ = torch.ones(n, dtype=torch.uint8, device=dev)
+            span = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+            counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        hist, g0, still = [], 0, n
+        while still and g0 < budget:
+            if len(hist) >= max_chunks:
+                raise RuntimeError("no solvable episode found for %d stream(s) within the history memory budget (%d chunks of %d steps x %d "
+                                   "streams = %.1f GB on the device): use a smaller `batch`" % (still, len(hist), chunk, n, len(hist) * chunk_bytes / 1e9))
+            r = env.bot_rollout(chunk, tokens=True)
+            hist.append(r)
+            demo_spans(r["done"], r["gave_up"], r["reward"], g0, filter_steps, last_done, open_, span, counter)
+            still = int(counter.item())                                        # 8 bytes per chunk
+            g0 += chunk
+        if still:
+            raise RuntimeError("no solvable episode found for %d stream(s) within the step budget" % still)
+        return _pack(hist, span, chunk)
+    finally:
+        env.close()
+
+
+def _pack(hist, span, chunk):
+    """The spans of a batch of streams (int32[n, 2] on the device) in the history chunks `hist` (bot_rollout results of `chunk` steps each)
+    -> (image, direction, action, tokens, offset_host): k_demo_pack."""
+    import torch
+    from .engine import _check
+    dev, n = span.device, int(span.shape[0])
+    lens = (span[:, 1] - span[:, 0] + 1).to(torch.int64)
+    offset = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=offset[1:])
+    offset_host = offset.cpu().numpy()                                     # the batch's lengths: the one other read
+    frames = int(offset_host[-1])
+    # k_demo_pack fetches the aligned 16-byte words around the history rows it needs (include/bbai.h): every chunk array must start
+    # 16-byte aligned in an allocation padded to a multiple of 16 bytes.  torch's caching allocator hands out blocks that start
+    # 512-byte aligned and are rounded up to 512 bytes, whatever chunk * n * 147 is.
+    for r in hist:
+        for k in ("image", "direction", "action", "tokens"):
+            assert r[k].data_ptr() % 16 == 0
+    table = torch.as_tensor(np.array([[r[k].data_ptr() for k in ("image", "direction", "action", "tokens")] for r in hist], dtype=np.int64), device=dev)
+    with torch.cuda.device(dev):
+        u8 = dict(dtype=torch.uint8, device=dev)
+        image, direction = torch.empty((frames, 7, 7, 3), **u8), torch.empty(frames, **u8)
+        action, tokens = torch.empty(frames, **u8), torch.empty((n, TOK_MAX), **u8)
+        lib, stream = _lib_stream(dev)
+        _check(lib, lib.bbai_demo_pack(n, frames, chunk, table.data_ptr(), span.data_ptr(), offset.data_ptr(), image.data_ptr(),
+                                       direction.data_ptr(), action.data_ptr(), tokens.data_ptr(), stream), "bbai_demo_pack")
+        torch.cuda.current_stream(dev).synchronize()                       # the history may be freed (and the env closed) after this
+    return image, direction, action, tokens, offset_host
+
+
+def run_batch(acmodel, batch, recurrence, entropy_coef, optimizer=None):
+    """`ImitationLearning.run_epoch_recurrence_one_batch` (imitation.py:225-321) over a DemoBatch: the same two phases, the model
+    called the same way, the same log.  `optimizer` given = a training batch (is_training)."""
+    import torch
+    dev = batch.image.device
+    B, F = len(batch), batch.num_frames
+    memories = torch.zeros([F, acmodel.memory_size], device=dev)
+    memory = torch.zeros([B, acmodel.memory_size], device=dev)
+    instr_embedding = acmodel._get_instr_embedding(batch.instr)
+    # phase 1: the memories of every frame, no gradient; step t visits the demos that have a frame t
+    for t in range(int(batch.lengths[0])):
+        c = int(batch.counts[t])
+        idx = batch.active(t)
+        obs = TensorDict(image=batch.image[idx].to(torch.float32), instr=batch.instr[:c])
+        with torch.no_grad():
+            new_memory = acmodel(obs, memory[:c, :], instr_embedding[:c])["memory"]
+        memories[idx, :] = memory[:c, :]
+        memory[:c, :] = new_memory
+    # phase 2: back-propagation through `recurrence` steps from every starting index
+    final_loss, final_entropy, final_policy_loss = 0, 0, 0
+    indexes = batch.starting_indexes(recurrence)
+    memory = memories[indexes]
+    total_frames = len(indexes) * recurrence
+    hits = []
+    for _ in range(recurrence):
+        ep = batch.episode_ids[indexes]
+        obs = TensorDict(image=batch.image[indexes].to(torch.float32), instr=batch.instr[ep])
+        action_step = batch.action[indexes]
+        res = acmodel(obs, memory * batch.mask[indexes], instr_embedding[ep])
+        dist, memory = res["dist"], res["memory"]
+        entropy = dist.entropy().mean()
+        policy_loss = -dist.log_prob(action_step).mean()
+        loss = policy_loss - entropy_coef * entropy
+        action_pred = dist.probs.max(1, keepdim=True)[1]
+        hits.append((action_pred == action_step.unsqueeze(1)).sum())
+        final_loss += loss
+        final_entropy += entropy
+        final_policy_loss += policy_loss
+        indexes = indexes + 1
+    final_loss /= recurrence
+    if optimizer is not None:
+        optimizer.zero_grad()
+        final_loss.backward()
+        optimizer.step()
+    accuracy = 0
+    for h in torch.stack(hits).cpu().tolist():                   # (one read for all steps; summed as the reference sums them)
+        accuracy += float(h) / total_frames
+    return {"entropy": float((final_entropy / recurrence).detach()), "policy_loss": float((final_policy_loss / recurrence).detach()),
+            "accuracy": float(accuracy)}
+
+
+def run_epoch(acmodel, store, indices, batch_size, recurrence, entropy_coef, optimizer=None, vocab=None):
+    """`run_epoch_recurrence` (imitation.py:189-223): batches of `batch_size` demos taken from `indices` in order (a shuffled
+    permutation for training), a trailing partial batch dropped.  Without an optimizer the model is put in eval mode for the epoch."""
+    batch_size = min(batch_size, len(store))
+    if optimizer is None:
+        acmodel.eval()
+    log = {"entropy": [], "policy_loss": [], "accuracy": []}
+    frames = 0
+    for b in range(len(indices) // batch_size):
+        batch = store.batch(indices[b * batch_size:(b + 1) * batch_size], vocab=vocab)
+        frames += batch.num_frames
+        one = run_batch(acmodel, batch, recurrence, entropy_coef, optimizer)
+        for k in log:
+            log[k].append(one[k])
+    log["total_frames"] = frames
+    if optimizer is None:
+        acmodel.train()
+    return log

@@ -284,6 +284,40 @@ int bbai_gae(int64_t num_envs, int num_frames, const float* rewards_dev, const f
              const float* last_mask_dev, const float* last_value_dev, double discount, double gae_lambda,
              float* advantage_dev, float* returnn_dev, void* stream);
 
+/* Demonstrations that stay on the device (babyai_amd/imitation.py DemoStore / DemoBatch).  Handle-free like bbai_gae: caller's
+ * buffers, caller's stream, launched on the CURRENT device.  Every buffer that is read as images (the history chunks'
+ * image arrays, src_image) must start 16-byte aligned in an allocation that is a multiple of 16 bytes long -- true of anything
+ * hipMalloc returns: the kernels fetch the aligned 16-byte words around the bytes they need.
+ *
+ * bbai_demo_spans replaces the host scan of a rollout chunk (scripts/make_agent_demos.py:84-88,112-123: keep an episode iff
+ * it ended done with reward > 0 and the bot did not crash, at most filter_steps long if that is non-zero; otherwise go on with the
+ * stream's next level).  done / gave_up / reward are one bbai_bot_rollout call's outputs, [chunk][n]; g0 = the global step index of
+ * row 0.  Carry per stream, updated in place: last_done int32[n] (global index of the latest episode end, -1 at first), open
+ * uint8[n] (1 = still looking), span int32[n][2] (first and last global step of the first solved episode).  *open_count_dev
+ * (8 bytes on the device, zeroed by the call) receives the number of streams still open. */
+int bbai_demo_spans(int64_t n, int chunk, const uint8_t* done_dev, const uint8_t* gave_up_dev, const float* reward_dev, int64_t g0,
+                    int filter_steps, int32_t* last_done_dev, uint8_t* open_dev, int32_t* span_dev, uint64_t* open_count_dev, void* stream);
+
+/* The spans of a batch of streams -> flat demonstrations (what scripts/make_agent_demos.py:111-112 appends per episode, kept as
+ * arrays): frames of stream k = rows offset[k] .. offset[k + 1] of image_out uint8[frames][147] / dir_out / action_out uint8[frames],
+ * taken from history rows span[k][0] .. span[k][1]; tokens_out uint8[n][72] = the token row of the episode's first step.
+ * chunks_dev: device table of the bbai_bot_rollout outputs that make up the history, chunk_steps rows [t][n] each (global step
+ * g = row g % chunk_steps of chunk g / chunk_steps); offset_dev int64[n + 1] = exclusive prefix sum of the span lengths, frames =
+ * offset[n].  Outputs 16-byte aligned. */
+typedef struct bbai_demo_chunk { const uint8_t* image; const uint8_t* dir; const uint8_t* action; const uint8_t* tokens; } bbai_demo_chunk;
+int bbai_demo_pack(int64_t n, int64_t frames, int chunk_steps, const bbai_demo_chunk* chunks_dev, const int32_t* span_dev,
+                   const int64_t* offset_dev, uint8_t* image_out, uint8_t* dir_out, uint8_t* action_out, uint8_t* tokens_out, void* stream);
+
+/* A list of demonstrations of a store -> one flat batch (babyai/imitation.py:226-251 without transform_demos' Python lists): demo
+ * order_dev[b] of the store (offset_dev int64[D + 1], src_image / src_action) becomes frames dst_start_dev[b] .. dst_start_dev[b + 1]
+ * (int64[count + 1], last entry = frames).  Batch form: action_out int64[frames], done_out uint8[frames] (1 on a demo's last frame),
+ * mask_out float32[frames] (0 on its first), episode_ids_out int64[frames] (= b); dir8_out / action8_out NULL.  Store form (a
+ * sub-store: the train / validation split): dir8_out / action8_out uint8[frames] and src_dir given, the four batch outputs NULL.
+ * src_image and every output 16-byte aligned. */
+int bbai_demo_batch(int64_t count, int64_t frames, const int64_t* order_dev, const int64_t* dst_start_dev, const int64_t* offset_dev,
+                    const uint8_t* src_image, const uint8_t* src_dir, const uint8_t* src_action, uint8_t* image_out, int64_t* action_out,
+                    uint8_t* done_out, float* mask_out, int64_t* episode_ids_out, uint8_t* dir8_out, uint8_t* action8_out, void* stream);
+
 /* Per-kernel timing for measurements (bench.py's roofline): while enabled, every k_step / k_consume / k_render launch is
  * bracketed by a HIP event pair ON THE STREAM IT IS LAUNCHED ON; bbai_profile_read returns the summed milliseconds and the
  * launch counts in that order.  enable: 1 = start from zero, 2 = resume (totals kept), 0 = pause (totals stay readable).
