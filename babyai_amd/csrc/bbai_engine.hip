@@ -19,8 +19,9 @@
 //   k_tokens       lane = env: mission text as fixed-vocabulary token ids of the envs that started a new episode.
 //   k_render_q / k_render   RGBImgPartialObsWrapper as a pure tile-atlas gather: atlas + per-cell tile ids in LDS, 16 bytes per lane per
 //                  store, a wave writes 1 KiB of contiguous pixels; persistent blocks fed by ONE ticket counter from 262 144 envs
-//                  (k_render_q), one-shot (512, 2) blocks below.  Into the registered target (bbai_set_render_target): k_render_delta,
-//                  the delta render -- only the 128-byte lines whose cells changed since the frame the buffer holds are stored.
+//                  (k_render_q), one-shot (512, 2) blocks below.  Into the registered target (bbai_set_render_target): k_render_delta /
+//                  k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
+//                  the buffer holds are stored.  All four live in bbai_render.hpp; their launches (render_launch) are here.
 //   k_bot<W>       lane = env: one decision of the reference's GOFAI expert (babyai/bot.py) per env, W = occupancy target
 //                  (bbai_bot.hpp); only launched by bbai_bot_act / bbai_bot_rollout.
 //
@@ -920,7 +921,8 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
 // table for AGENT_CELL), the changed ones written back to the shadow (the chunk whole, where one differs), and per env a 64-bit dirty mask
 // (bit = cell) into `dmask`: gathered by LDS atomics in the first 512 bytes of the row area, which nothing reads any more.
 constexpr int CELLS = VIEW * VIEW;
-constexpr int AGENT_CELL = 3 * VIEW + 6;
+constexpr int AGENT_CELL = 3 * VIEW + 6;                        // the agent's own cell of the view: (3, 6) (tile_id, bbai_render.hpp)
+static_assert(AGENT_CELL == 3 * VIEW + 6, "the agent stands in the middle of the view's last row");
 constexpr int DIRTY_CHUNKS = (STEP_BLOCK * CELLS / 16 + STEP_BLOCK - 1) / STEP_BLOCK;      // 16-byte shadow chunks per lane: 196 per block -> 4
 static_assert(STEP_BLOCK * CELLS % 16 == 0 && OBS_BYTES == 3 * CELLS, "a block's shadow rows are whole 16-byte chunks; a row is 3 bytes per cell");
 __device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __restrict__ shadow /* [n][49] */, uint64_t* __restrict__ dmask /* [n] */,
@@ -1616,518 +1618,7 @@ __global__ void k_init_hot(int64_t n, Hot* __restrict__ hots, Hot* __restrict__ 
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// k_render : encoded obs -> 56x56x3 pixels through the tile atlas
-// ------------------------------------------------------------------------------------------
-constexpr int RENDER_QUEUE_DEFAULT = 1;         // queue shape of render_launch used from RENDER_QUEUE_MIN_ENVS up
-constexpr int RENDER_QUEUE_PACED = 3;           // ... with time-paced tickets: (1024, 8) blocks, two interleaved counters
-constexpr int64_t RENDER_QUEUE_MIN_ENVS = 262144;
-
-constexpr int CHUNKS_PER_ROW = PIX * 3 / 8;       // 21 eight-byte chunks per pixel row
-constexpr int VEC_PER_ENV = PIX_BYTES / 16;       // 588 sixteen-byte stores per env
-
-// One 8-byte piece of the env's pixel image: chunk id -> (tile, row in tile, third of the row).
-__device__ __forceinline__ uint64_t render_chunk(const uint8_t* s_atlas, const uint8_t* tiles49, int ch) {
-    const int py = ch / CHUNKS_PER_ROW, cx = ch - py * CHUNKS_PER_ROW;
-    const int ti = cx / 3, part = cx - ti * 3;        // tile column (view x), 8-byte third of the tile row
-    const int tj = py >> 3, ty = py & 7;              // tile row (view y), row inside the tile
-    const int tile = tiles49[ti * VIEW + tj];
-    return *(const uint64_t*)(s_atlas + tile * TILE_BYTES + ty * 24 + part * 8);
-}
-
-// (Round 3's alternative input -- a fused tile plane, one masked appearance byte per cell, left behind by k_step -- was measured
-// once more with the ticket queue in round 4 (profiles/r04/render_queue_counters_1M_lease_d.jsonl: k_render 1.503 vs 1.505 ms, k_step
-// + 0.02 ms) and removed.)
-template <int RENDER_GROUP, int RENDER_BLOCK>     // envs per block iteration (between two barriers); threads per block
-__global__ __launch_bounds__(RENDER_BLOCK) void k_render(int64_t n, const uint8_t* __restrict__ image,
-                                                         uint8_t* __restrict__ pixels, const uint8_t* __restrict__ atlas,
-                                                         const uint8_t* __restrict__ lut, int n_tiles,
-                                                         uint8_t* __restrict__ shadow /* NULL, or the registered target's tile ids [n][49] (k_render_delta) */) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ uint8_t s_lut[512];
-    __shared__ uint8_t s_tile[RENDER_GROUP * VIEW * VIEW + 8];
-    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += RENDER_BLOCK)
-        ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    for (int k = threadIdx.x; k < 512; k += RENDER_BLOCK) s_lut[k] = lut[k];
-    const int64_t ngroups = (n + RENDER_GROUP - 1) / RENDER_GROUP;
-    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int64_t env0 = grp * RENDER_GROUP;
-        const int ne = (int)(n - env0 < RENDER_GROUP ? n - env0 : RENDER_GROUP);
-        __syncthreads();                               // atlas loaded / previous group's tiles consumed
-        // encoded cell -> atlas tile, once per cell (49 per env)
-        for (int c = threadIdx.x; c < ne * VIEW * VIEW; c += RENDER_BLOCK) {
-            const int e = c / (VIEW * VIEW), cell = c - e * (VIEW * VIEW);
-            const uint8_t* o = image + (env0 + e) * OBS_BYTES + cell * 3;
-            const int key = o[0] | (o[1] << 3) | (o[2] << 6);
-            s_tile[c] = s_lut[(cell == 3 * VIEW + 6 ? 256 : 0) + key];
-            if (shadow) shadow[env0 * (VIEW * VIEW) + c] = s_tile[c];
-        }
-        __syncthreads();
-        // 16 bytes per lane per store: a wave writes 1 KiB of contiguous pixels
-        u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
-        for (int q = threadIdx.x; q < ne * VEC_PER_ENV; q += RENDER_BLOCK) {
-            const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
-            const uint8_t* t49 = s_tile + e * (VIEW * VIEW);
-            const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
-            const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
-            u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-            __builtin_nontemporal_store(v, out + q);   // streaming output: keep it out of L2/MALL
-        }
-    }
-}
-
-// k_render_q: the same render from PERSISTENT blocks (the atlas is loaded into LDS once per block) that take their work from an
-// atomic ticket counter, so that the chip's stores advance through the output as ONE compact, evenly paced window -- the order
-// in which the pure store stream is fastest (render_launch has the measurements).
-//   * a ticket = K consecutive G-env groups; the next ticket is taken while the first group of the current one is being
-//     staged, so its latency rides under the stores;
-//   * NC counters, 256 bytes apart, INTERLEAVED: ticket t of counter c is super-group t * NC + c, a block uses counter
-//     blockIdx % NC (= its XCD for NC = 8).  Shipped: NC = 1, K = 1 -- more counters or bigger tickets relieve the ticket rate
-//     (~88 M/s per address) and measure SLOWER: the counters drift apart, the window widens;
-//   * the counters clean up after themselves: the last block to leave (a departure counter) zeroes them for the next launch,
-//     so the step path carries no memset.
-// Tile rows and tickets are double-buffered: one barrier per group.
-// (The counters are the handle's: two renders of one handle never overlap -- every entry point orders a call on another stream behind the
-// handle's previous call, enter_call -- and a launch that was aborted by a device fault leaves a handle that is unusable anyway.)
-template <int RENDER_GROUP, int RENDER_BLOCK, int NC, int K>
-__global__ __launch_bounds__(RENDER_BLOCK) void k_render_q(int64_t n, const uint8_t* __restrict__ image,
-                                                           uint8_t* __restrict__ pixels, const uint8_t* __restrict__ atlas,
-                                                           const uint8_t* __restrict__ lut, int n_tiles, unsigned int* __restrict__ counters,
-                                                           int pace_x16 /* experiment: 0, or 1/16 ns of wall clock per ticket (render_launch) */,
-                                                           uint8_t* __restrict__ shadow /* NULL, or the registered target's tile ids [n][49] (k_render_delta) */) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ uint8_t s_lut[512];
-    __shared__ uint8_t s_tile[2][RENDER_GROUP * VIEW * VIEW + 8];
-    __shared__ unsigned int s_ticket[2];
-    __shared__ unsigned long long s_origin;
-    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += RENDER_BLOCK)
-        ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    for (int k = threadIdx.x; k < 512; k += RENDER_BLOCK) s_lut[k] = lut[k];
-    const int64_t all_groups = (n + RENDER_GROUP - 1) / RENDER_GROUP;
-    const int64_t n_super = (all_groups + K - 1) / K;
-    const unsigned int cidx = blockIdx.x % NC;
-    unsigned int* counter = counters + 64 * cidx;
-    int buf = 0, tp = 0;
-    if (threadIdx.x == 0) {
-        const unsigned int t0 = atomicAdd(counter, 1u);
-        s_ticket[0] = t0;
-        // time-paced tickets (experiment): ticket sg is not started before origin + sg x pace; the 100-MHz constant clock in 1/16 ns
-        s_origin = __builtin_amdgcn_s_memrealtime() * 160ull - ((unsigned long long)t0 * NC + cidx) * (unsigned long long)pace_x16;
-    }
-    __syncthreads();
-    for (;;) {
-        const int64_t sg = (int64_t)s_ticket[tp] * NC + cidx;
-        if (sg >= n_super) break;
-        if (pace_x16) {
-            const unsigned long long due = s_origin + (unsigned long long)sg * (unsigned long long)pace_x16;
-            while (__builtin_amdgcn_s_memrealtime() * 160ull < due) __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int kk = 0; kk < K; ++kk) {
-            const int64_t grp = sg * K + kk;
-            if (grp >= all_groups) break;
-            const int64_t env0 = grp * RENDER_GROUP;
-            const int ne = (int)(n - env0 < RENDER_GROUP ? n - env0 : RENDER_GROUP);
-            for (int c = threadIdx.x; c < ne * VIEW * VIEW; c += RENDER_BLOCK) {
-                const int e = c / (VIEW * VIEW), cell = c - e * (VIEW * VIEW);
-                const uint8_t* o = image + (env0 + e) * OBS_BYTES + cell * 3;
-                const int key = o[0] | (o[1] << 3) | (o[2] << 6);
-                s_tile[buf][c] = s_lut[(cell == 3 * VIEW + 6 ? 256 : 0) + key];
-                if (shadow) shadow[env0 * (VIEW * VIEW) + c] = s_tile[buf][c];
-            }
-            if (kk == 0 && threadIdx.x == 0) s_ticket[tp ^ 1] = atomicAdd(counter, 1u);      // the next ticket rides under this one's stores
-            __syncthreads();
-            u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
-            for (int q = threadIdx.x; q < ne * VEC_PER_ENV; q += RENDER_BLOCK) {
-                const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
-                const uint8_t* t49 = s_tile[buf] + e * (VIEW * VIEW);
-                const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
-                const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
-                u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-                __builtin_nontemporal_store(v, out + q);
-            }
-            buf ^= 1;
-        }
-        tp ^= 1;
-    }
-    // every block has taken its last ticket before it arrives here (the failing ticket was read through LDS behind a barrier);
-    // the last one to arrive leaves all counters at zero for the next launch
-    if (threadIdx.x == 0) {
-        unsigned int* departed = counters + 64 * NC;
-        if (atomicAdd(departed, 1u) == gridDim.x - 1) {
-            for (int c = 0; c <= NC; ++c) atomicExch(counters + 64 * c, 0u);
-        }
-    }
-}
-
-// ---- delta render into the registered target (bbai_set_render_target) ----------------------------------------------------------
-// The registered buffer holds the previous frame of every env, and the handle's shadow plane holds the atlas tile id of every cell
-// of that frame (uint8[n][49]).  A frame cell whose tile id is unchanged has unchanged bytes, so only the parts of the frame that
-// touch a changed cell are stored: 64-byte pieces by default (render_piece_bytes; store_dirty_pieces below), or, with the option at
-// 128, whole 128-byte lines -- the line form this paragraph describes.  8 envs are 8 x 9408 = 588 x 128 bytes: a unit of 8 envs
-// starts on a line boundary whenever the buffer does (render_launch checks the alignment), and a line belongs to one unit; inside
-// it a line touches one env or two (9408 = 73.5 lines).  Per G-env group of a block iteration:
-//   A   one wave per env, one lane per cell: the new tile id (s_lut, as k_render), its old id from the shadow, a ballot gives the
-//       env's 49-bit dirty mask; the changed cells' ids go back to the shadow;
-//   B1  one lane per line: (dirty mask of its env(s)) & (the cells the line touches: a per-block table) -> a compacted line list;
-//   B2  8 lanes per listed line, 16 bytes each (render_chunk, as k_render): one full 128-byte line per 8 lanes.
-// Work is assigned statically (no ticket counter: one counter serves ~88 M tickets/s, which is the full render's own time at
-// 8-env tickets), so the next group's encoding and shadow bytes are loaded before the current group's stores.  SCHED 0: block b
-// takes groups b, b + grid, ... (the chip's stores advance as one window); 1: a contiguous range of groups per block.
-// Tables and tiles are double-buffered: two barriers per group.  While the shadow is not valid, render_launch runs the full render
-// (k_render_q / k_render) instead, which writes every byte and, given the shadow, every tile id.
-constexpr int LINE_BYTES = 128;
-constexpr int DELTA_UNIT = 8;                                          // envs per line-aligned unit
-constexpr int UNIT_LINES = DELTA_UNIT * PIX_BYTES / LINE_BYTES;        // 588
-static_assert(DELTA_UNIT * PIX_BYTES % LINE_BYTES == 0 && PIX_BYTES % 64 == 0, "8-env units are whole 128-byte lines");
-constexpr int RENDER_PIECE_DEFAULT = 64;                               // option "render_piece_bytes" (render_launch)
-
-// The cells of one env that bytes [s, t) of its 56x56x3 image come from (s, t multiples of 8: one 8-byte chunk per tile row piece).
-__device__ __forceinline__ uint64_t line_cells(int s, int t) {
-    uint64_t m = 0;
-    for (int b = s; b < t; b += 8) {
-        const int ch = b >> 3, py = ch / CHUNKS_PER_ROW, cx = ch - py * CHUNKS_PER_ROW;
-        m |= 1ull << ((cx / 3) * VIEW + (py >> 3));
-    }
-    return m;
-}
-
-// ---- piece-granular stores (render_piece_bytes P < 128) --------------------------------------------------------------------------
-// A P-byte piece (P divides 9408, so no piece crosses an env boundary and every env starts on the piece grid when the buffer does) is
-// stored when a cell it is drawn from changed.  Stores are byte-masked and the memory side does not read a partial line back (FETCH_SIZE
-// stays flat), but the store RATE falls with the piece: tools/ubench_sector_store.hip, 1 048 576 frames, a BossLevel-like dirty mix,
-// ms against whole lines: 64 B 0.96, 32 B 1.81, 16 B 2.32 (WRITE_SIZE 0.87 / 0.74 / 0.74).  64-byte pieces ship: in the step loop they
-// cut the headline's render by 3 % (profiles/render_pieces/); 32 and below lose more in rate than they save in bytes.
-// Per env the cells of every piece come from a per-block table (s_pm: NP 49-bit masks), and ONE wave handles a dirty env: a lane per
-// piece tests (dirty mask & piece cells), a ballot compacts the dirty pieces into the wave's own LDS list, and the wave stores them
-// 16 bytes per lane, consecutive lanes on consecutive chunks.  The list is the wave's: no LDS atomic, no workgroup barrier.
-template <int P>
-struct Pieces {
-    static_assert(P == 16 || P == 32 || P == 64, "pieces of 16, 32 or 64 bytes");
-    static_assert(PIX_BYTES % P == 0, "whole pieces per env");
-    static constexpr int NP = PIX_BYTES / P;          // pieces per env (147 at P = 64)
-    static constexpr int S = P / 16;                  // 16-byte stores per piece
-};
-
-__device__ __forceinline__ void wave_lds_sync() {     // the wave's own LDS writes are visible to its other lanes (no workgroup barrier)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <int P>
-__device__ __forceinline__ void init_piece_cells(uint64_t* s_pm, int tid, int nthreads) {
-    for (int p = tid; p < Pieces<P>::NP; p += nthreads) s_pm[p] = line_cells(p * P, p * P + P);
-}
-
-// Stores the pieces of one env whose cells meet the dirty mask `m` (wave-uniform, nonzero).  Called by a whole wave; `wl` is the
-// wave's list (NP entries), `t49` the env's 49 tile ids, `out` the env's first 16-byte chunk.
-template <int P>
-__device__ __forceinline__ void store_dirty_pieces(uint64_t m, const uint64_t* s_pm, uint16_t* wl, const uint8_t* s_atlas, const uint8_t* t49,
-                                                   u32x4* out, int lane) {
-    constexpr int NP = Pieces<P>::NP, S = Pieces<P>::S;
-    int cnt = 0;
-    for (int p0 = 0; p0 < NP; p0 += 64) {
-        const int p = p0 + lane;
-        const bool d = p < NP && (m & s_pm[p]) != 0;
-        const uint64_t b = __ballot(d);
-        if (d) wl[cnt + __builtin_popcountll(b & ((1ull << lane) - 1))] = (uint16_t)p;
-        cnt += __builtin_popcountll(b);
-    }
-    wave_lds_sync();
-    for (int i = lane; i < cnt * S; i += 64) {
-        const int k = (int)wl[i / S] * S + (i & (S - 1));
-        const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
-        const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
-        u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-        __builtin_nontemporal_store(v, out + k);
-    }
-    wave_lds_sync();                                  // the list is read before the wave's next env writes it
-}
-
-template <int G, int T, int SCHED, int P>
-__global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __restrict__ image, uint8_t* __restrict__ pixels,
-                                                    uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
-                                                    const uint8_t* __restrict__ atlas, const uint8_t* __restrict__ lut, int n_tiles) {
-    static_assert(G % DELTA_UNIT == 0 && T % 64 == 0 && G % (T / 64) == 0, "whole units per group, whole envs per wave");
-    constexpr int W = T / 64, EPW = G / W, GL = G / DELTA_UNIT * UNIT_LINES;
-    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ uint8_t s_lut[512];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t ngroups = (n + G - 1) / G;
-    int64_t g, gend, gstep;
-    if (SCHED == 0) { g = blockIdx.x; gend = ngroups; gstep = gridDim.x; }
-    else { const int64_t per = (ngroups + gridDim.x - 1) / gridDim.x; g = blockIdx.x * per; gend = g + per < ngroups ? g + per : ngroups; gstep = 1; }
-    // phase A's inputs of group `grp`, loaded ahead: 3 encoding bytes + the old id of this lane's cell in each of the wave's envs
-    uint32_t o0[EPW], o1[EPW], o2[EPW], old[EPW];
-    auto load = [&](int64_t grp) {
-#pragma unroll
-        for (int j = 0; j < EPW; ++j) {
-            const int64_t env = grp * G + wave + j * W;
-            o0[j] = o1[j] = o2[j] = old[j] = 0;
-            if (grp < gend && lane < CELLS && env < n) {
-                const uint8_t* o = image + env * OBS_BYTES + lane * 3;
-                o0[j] = o[0]; o1[j] = o[1]; o2[j] = o[2];
-                old[j] = shadow[env * CELLS + lane];
-            }
-        }
-    };
-    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    for (int k = threadIdx.x; k < 512; k += T) s_lut[k] = lut[k];
-    if constexpr (P < LINE_BYTES) {
-        // Pieces: the wave that finds an env's dirty mask (A) also stores its pieces, from the ids it has just written to LDS -- no
-        // workgroup barrier in the loop, one tile buffer (a wave writes an env's ids again only after it has stored that env).
-        __shared__ uint64_t s_pm[Pieces<P>::NP];
-        __shared__ uint16_t s_wl[W][Pieces<P>::NP];
-        __shared__ uint8_t s_tile1[G * CELLS + 8];
-        init_piece_cells<P>(s_pm, threadIdx.x, T);
-        load(g);
-        __syncthreads();                              // atlas, lut and piece table loaded
-        for (; g < gend; g += gstep) {
-            const int64_t env0 = g * G;
-            const int ne = (int)(n - env0 < G ? n - env0 : G);
-            uint64_t dm[EPW];
-#pragma unroll
-            for (int j = 0; j < EPW; ++j) {
-                const int e = wave + j * W;
-                const bool live = lane < CELLS && e < ne;
-                const int key = o0[j] | (o1[j] << 3) | (o2[j] << 6);
-                const uint32_t id = live ? s_lut[(lane == AGENT_CELL ? 256 : 0) + key] : 0;
-                const bool d = live && id != old[j];
-                dm[j] = __ballot(d);
-                if (live) s_tile1[e * CELLS + lane] = (uint8_t)id;
-                if (d) shadow[(env0 + e) * CELLS + lane] = (uint8_t)id;
-            }
-            load(g + gstep);                          // the next group's inputs ride under this group's stores
-            wave_lds_sync();
-#pragma unroll
-            for (int j = 0; j < EPW; ++j) {
-                const int e = wave + j * W;
-                if (dm[j]) store_dirty_pieces<P>(dm[j], s_pm, s_wl[wave], s_atlas, s_tile1 + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
-            }
-        }
-        return;
-    } else {
-    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];        // cells of the line's first / second env (0: one env)
-    __shared__ uint8_t s_lea[UNIT_LINES];                              // the line's first env in the unit
-    __shared__ uint64_t s_dmask[2][G];
-    __shared__ uint8_t s_tile[2][G * CELLS + 8];
-    __shared__ uint16_t s_list[2][GL];
-    __shared__ unsigned int s_nd[2];
-    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
-        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
-        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
-        s_lea[l] = (uint8_t)ea;
-        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
-        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
-    }
-    load(g);
-    __syncthreads();                                  // atlas, lut and line table loaded
-    int buf = 0;
-    for (; g < gend; g += gstep, buf ^= 1) {
-        const int64_t env0 = g * G;
-        const int ne = (int)(n - env0 < G ? n - env0 : G);
-        // A: new ids, dirty masks, shadow write-back
-#pragma unroll
-        for (int j = 0; j < EPW; ++j) {
-            const int e = wave + j * W;
-            const bool live = lane < CELLS && e < ne;
-            const int key = o0[j] | (o1[j] << 3) | (o2[j] << 6);
-            const uint32_t id = live ? s_lut[(lane == AGENT_CELL ? 256 : 0) + key] : 0;
-            const bool d = live && id != old[j];
-            const uint64_t m = __ballot(d);
-            if (live) s_tile[buf][e * CELLS + lane] = (uint8_t)id;
-            if (d) shadow[(env0 + e) * CELLS + lane] = (uint8_t)id;
-            if (lane == 0) s_dmask[buf][e] = m;
-        }
-        if (threadIdx.x == 0) s_nd[buf] = 0;
-        __syncthreads();
-        // B1: the group's dirty lines as a list (any order: every listed line is stored whole, by 8 lanes)
-        const int nl = (int)(((int64_t)ne * PIX_BYTES + LINE_BYTES - 1) / LINE_BYTES);
-        for (int L0 = threadIdx.x - lane; L0 < nl; L0 += T) {              // (whole waves: the ballot below)
-            const int L = L0 + lane;
-            bool d = false;
-            if (L < nl) {
-                const int u = L / UNIT_LINES, l = L - u * UNIT_LINES, ea = u * DELTA_UNIT + s_lea[l];
-                d = ((s_dmask[buf][ea] & s_lma[l]) | (s_lmb[l] ? s_dmask[buf][ea + 1] & s_lmb[l] : 0)) != 0;
-            }
-            const uint64_t m = __ballot(d);
-            if (!m) continue;
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(&s_nd[buf], (unsigned int)__builtin_popcountll(m));
-            base = __shfl(base, 0);
-            if (d) s_list[buf][base + __builtin_popcountll(m & ((1ull << lane) - 1))] = (uint16_t)L;
-        }
-        __syncthreads();
-        const int64_t gn = g + gstep;
-        load(gn);                                     // the next group's inputs ride under this group's stores
-        // B2: 16 bytes per lane, 8 lanes per listed line
-        const int nq = ne * VEC_PER_ENV, nd8 = (int)s_nd[buf] * 8;
-        u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
-        for (int i = threadIdx.x; i < nd8; i += T) {
-            const int q = (int)s_list[buf][i >> 3] * 8 + (i & 7);
-            if (q >= nq) continue;                    // (past the end of an odd-sized last group: half a line)
-            const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
-            const uint8_t* t49 = s_tile[buf] + e * CELLS;
-            const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
-            const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
-            u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-            __builtin_nontemporal_store(v, out + q);
-        }
-    }
-    }
-}
-
-// k_render_dstore: the delta render of a step whose k_step has already found the dirty cells (step_dirty: the dirty masks in `dmask`, the
-// new tile ids in the shadow).  Stores only: per G-env group it reads the G masks and the ids the stored lines are drawn from -- 8-byte
-// pieces of the group's shadow rows, a piece loaded when a cell of it is drawn: its env is dirty, or the piece holds cells of the one line
-// its env shares with the other env of its pair (envs 2k, 2k + 1 of a unit: line 73 + 147 k) and that line is stored; no encoding, no lut,
-// no shadow write, no per-env phase.  Line list (B1) and stores (B2) as k_render_delta; the same static interleaved groups (SCHED 0).  The inputs are loaded a
-// group ahead (the ids) and two groups ahead (the masks, which decide what ids are loaded), under the current group's stores.
-constexpr int DSTORE_PIECES = 32 * CELLS / 8;                          // 8-byte shadow pieces of a 32-env group
-template <int G, int T, int P>
-__global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restrict__ pixels, const uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
-                                                     const uint64_t* __restrict__ dmask /* [n] */, const uint8_t* __restrict__ atlas, int n_tiles) {
-    static_assert(G == 32 && T >= DSTORE_PIECES && T >= G && T % 64 == 0, "one 8-byte shadow piece per thread and group");
-    constexpr int GL = G / DELTA_UNIT * UNIT_LINES;
-    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
-    __shared__ __attribute__((aligned(8))) uint8_t s_tile[2][G * CELLS + 8];
-    for (int k = threadIdx.x; k < n_tiles * TILE_BYTES / 8; k += T) ((uint64_t*)s_atlas)[k] = ((const uint64_t*)atlas)[k];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t ngroups = (n + G - 1) / G;
-    const int64_t gstep = gridDim.x;
-    int64_t g = blockIdx.x;
-    // the dirty mask of env `tid` of group `grp` (0 past the end)
-    auto load_mask = [&](int64_t grp) -> uint64_t {
-        const int64_t env = grp * G + tid;
-        return (tid < G && grp < ngroups && env < n) ? dmask[env] : 0ull;
-    };
-    // 8 ids of group `grp` from the shadow (bounds-checked at the end of the range)
-    auto load_piece = [&](int64_t grp) -> uint2 {
-        const int64_t base = grp * G * CELLS + 8 * tid, end = n * CELLS;
-        if (base + 8 <= end) return *(const uint2*)(shadow + base);
-        uint32_t w[2] = {0u, 0u};
-        for (int i = 0; i < 8 && base + i < end; ++i) w[i >> 2] |= (uint32_t)shadow[base + i] << (8 * (i & 3));
-        return make_uint2(w[0], w[1]);
-    };
-    if constexpr (P < LINE_BYTES) {
-        // Pieces: only the dirty envs' ids are loaded (a piece of an env draws on that env's cells alone); one wave per dirty env stores
-        // its pieces (store_dirty_pieces).  One workgroup barrier per group: the ids (two buffers) and the masks (three buffers: the
-        // next group's masks are written while a slower wave may still read the current ones) are written in A and read behind it.
-        constexpr int W = T / 64, EPW = G / W;
-        __shared__ uint64_t s_pm[Pieces<P>::NP];
-        __shared__ uint16_t s_wl[W][Pieces<P>::NP];
-        __shared__ uint64_t s_dm3[3][G];
-        const int wave = tid >> 6;
-        init_piece_cells<P>(s_pm, tid, T);
-        auto load_ids = [&](int64_t grp, int b) -> uint2 {
-            if (tid >= DSTORE_PIECES || grp >= ngroups) return make_uint2(0u, 0u);
-            const int ea = (8 * tid) / CELLS, eb = (8 * tid + 7) / CELLS;
-            if (!s_dm3[b][ea] && !s_dm3[b][eb]) return make_uint2(0u, 0u);
-            return load_piece(grp);
-        };
-        if (tid < G) s_dm3[0][tid] = load_mask(g);
-        uint64_t mreg = load_mask(g + gstep);
-        __syncthreads();                              // atlas, piece table and the first group's masks
-        uint2 idr = load_ids(g, 0);
-        int buf = 0, mb = 0;
-        for (; g < ngroups; g += gstep, buf ^= 1, mb = mb == 2 ? 0 : mb + 1) {
-            const int64_t env0 = g * G;
-            const int mn = mb == 2 ? 0 : mb + 1;
-            if (tid < DSTORE_PIECES) *(uint2*)(s_tile[buf] + 8 * tid) = idr;
-            if (tid < G) s_dm3[mn][tid] = mreg;
-            __syncthreads();
-            idr = load_ids(g + gstep, mn);            // the next group's ids and the masks of the one after it ride under the stores
-            mreg = load_mask(g + 2 * gstep);
-#pragma unroll
-            for (int j = 0; j < EPW; ++j) {
-                const int e = wave + j * W;
-                const uint64_t m = s_dm3[mb][e];      // (0 past the end of the range)
-                if (m) store_dirty_pieces<P>(m, s_pm, s_wl[wave], s_atlas, s_tile[buf] + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
-            }
-        }
-        return;
-    } else {
-    __shared__ uint64_t s_lma[UNIT_LINES], s_lmb[UNIT_LINES];
-    __shared__ uint8_t s_lea[UNIT_LINES];
-    __shared__ uint64_t s_dmask[2][G];
-    __shared__ uint16_t s_list[2][GL];
-    __shared__ unsigned int s_nd[2];
-    for (int l = threadIdx.x; l < UNIT_LINES; l += T) {
-        const int b0 = l * LINE_BYTES, b1 = b0 + LINE_BYTES;
-        const int ea = b0 / PIX_BYTES, eb = (b1 - 1) / PIX_BYTES;
-        s_lea[l] = (uint8_t)ea;
-        s_lma[l] = line_cells(b0 - ea * PIX_BYTES, (eb != ea ? (ea + 1) * PIX_BYTES : b1) - ea * PIX_BYTES);
-        s_lmb[l] = eb != ea ? line_cells(0, b1 - eb * PIX_BYTES) : 0;
-    }
-    // the cells of the line an even env shares with the next one (its last 64 bytes), and of the odd env (its first 64)
-    const uint64_t shared_a = line_cells(PIX_BYTES - LINE_BYTES / 2, PIX_BYTES), shared_b = line_cells(0, LINE_BYTES / 2);
-    static_assert(PIX_BYTES % LINE_BYTES == LINE_BYTES / 2, "two envs of a pair share one line");
-    // are the cells [c0, c1] of env e of the group drawn (masks: s_dmask[b]; envs past the end have none)
-    auto drawn = [&](int b, int e, int c0, int c1) -> bool {
-        if (s_dmask[b][e]) return true;
-        const uint64_t pm = (c1 == 63 ? ~0ull : (2ull << c1) - 1) & ~((1ull << c0) - 1);
-        const bool shared_stored = ((s_dmask[b][e & ~1] & shared_a) | (s_dmask[b][e | 1] & shared_b)) != 0;
-        return shared_stored && (pm & ((e & 1) ? shared_b : shared_a)) != 0;
-    };
-    // this thread's 8-byte piece of group `grp`'s ids, if a cell of it is drawn
-    auto load_ids = [&](int64_t grp, int b) -> uint2 {
-        uint2 r = make_uint2(0u, 0u);
-        if (tid >= DSTORE_PIECES || grp >= ngroups) return r;
-        const int b0 = 8 * tid, b1 = b0 + 7, ea = b0 / CELLS, eb = b1 / CELLS;
-        const bool need = eb == ea ? drawn(b, ea, b0 - ea * CELLS, b1 - ea * CELLS) : (drawn(b, ea, b0 - ea * CELLS, CELLS - 1) || drawn(b, eb, 0, b1 - eb * CELLS));
-        if (!need) return r;
-        return load_piece(grp);
-    };
-    if (tid < G) s_dmask[0][tid] = load_mask(g);
-    uint64_t mreg = load_mask(g + gstep);
-    __syncthreads();                                  // atlas, line table and the first group's masks
-    uint2 idr = load_ids(g, 0);
-    int buf = 0;
-    for (; g < ngroups; g += gstep, buf ^= 1) {
-        const int64_t env0 = g * G;
-        const int ne = (int)(n - env0 < G ? n - env0 : G);
-        // A: this group's ids and the next group's masks into LDS
-        if (tid < DSTORE_PIECES) *(uint2*)(s_tile[buf] + 8 * tid) = idr;
-        if (tid < G) s_dmask[buf ^ 1][tid] = mreg;
-        if (tid == 0) s_nd[buf] = 0;
-        __syncthreads();
-        // B1: the group's dirty lines as a list (as k_render_delta)
-        const int nl = (int)(((int64_t)ne * PIX_BYTES + LINE_BYTES - 1) / LINE_BYTES);
-        for (int L0 = tid - lane; L0 < nl; L0 += T) {
-            const int L = L0 + lane;
-            bool d = false;
-            if (L < nl) {
-                const int u = L / UNIT_LINES, l = L - u * UNIT_LINES, ea = u * DELTA_UNIT + s_lea[l];
-                d = ((s_dmask[buf][ea] & s_lma[l]) | (s_lmb[l] ? s_dmask[buf][ea + 1] & s_lmb[l] : 0)) != 0;
-            }
-            const uint64_t m = __ballot(d);
-            if (!m) continue;
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(&s_nd[buf], (unsigned int)__builtin_popcountll(m));
-            base = __shfl(base, 0);
-            if (d) s_list[buf][base + __builtin_popcountll(m & ((1ull << lane) - 1))] = (uint16_t)L;
-        }
-        // the next group's ids (its masks are in LDS since the barrier above) and the masks of the one after it ride under the stores
-        idr = load_ids(g + gstep, buf ^ 1);
-        mreg = load_mask(g + 2 * gstep);
-        __syncthreads();
-        // B2: 16 bytes per lane, 8 lanes per listed line (as k_render_delta)
-        const int nq = ne * VEC_PER_ENV, nd8 = (int)s_nd[buf] * 8;
-        u32x4* out = (u32x4*)(pixels + env0 * PIX_BYTES);
-        for (int i = tid; i < nd8; i += T) {
-            const int q = (int)s_list[buf][i >> 3] * 8 + (i & 7);
-            if (q >= nq) continue;
-            const int e = q / VEC_PER_ENV, k = q - e * VEC_PER_ENV;
-            const uint8_t* t49 = s_tile[buf] + e * CELLS;
-            const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
-            const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
-            u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-            __builtin_nontemporal_store(v, out + q);
-        }
-    }
-    }
-}
+#include "bbai_render.hpp"
 
 // ------------------------------------------------------------------------------------------
 // k_render_grid : the full-grid picture, MiniGridEnv.render('rgb_array', highlight, tile_size), of listed envs (bbai_render_grid)
@@ -3286,118 +2777,144 @@ static bool delta_target(const bbai_env* e, const uint8_t* pixels, int64_t env_o
     const bool on_target = rt && pixels == rt + env_off * (int64_t)PIX_BYTES && env_off >= 0 && env_off + nr <= e->n;
     return on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
 }
+// What a render of envs [env_off, env_off + nr) into `pixels` means for the registered target (bbai_set_render_target), and the path it takes.
+// Envs of the target are rendered by the delta render, which stores only what changed -- or, while the shadow is not valid, by the full
+// render, which then also writes every tile id (`shadow`).  Any other render that writes into the registered buffer leaves a frame the
+// shadow does not describe: it is invalidated.  A render elsewhere leaves it alone.
+struct RenderPlan {
+    enum Path { DELTA, QUEUE, ONESHOT } path;
+    uint8_t* shadow;      // full render (QUEUE / ONESHOT) of target envs whose shadow is not valid: their rows of it, else NULL
+    int queue, pace;      // QUEUE: the queue shape (launch_render_queue) and the option "render_pace"
+};
+static RenderPlan plan_render(bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
+    RenderPlan p = {RenderPlan::ONESHOT, nullptr, 0, 0};
+    uint8_t* const rt = e->rt_pixels;
+    const int64_t pb = PIX_BYTES;
+    const bool delta = delta_target(e, pixels, env_off, nr);
+    if (rt && !delta && pixels < rt + e->n * pb && pixels + nr * pb > rt) { e->rt_valid = false; e->rt_filled = 0; }
+    // the shadow is not valid: the full render writes every byte of the range and, given `shadow`, every tile id of it
+    p.shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
+    if (p.shadow && env_off == e->rt_filled) e->rt_filled = env_off + nr;        // (recorded before the launch: a failed launch fails the call)
+    if (p.shadow && e->rt_filled >= e->n) e->rt_valid = true;
+    if (delta && !p.shadow) { p.path = RenderPlan::DELTA; return p; }
+    // BBAI_RENDER_QUEUE / option "render_queue": -1 = by batch size (default), 0 = never, m > 0 = queue shape m (launch_render_queue).
+    p.queue = e->render_queue;
+    p.pace = e->render_pace;
+    if (p.queue < 0) {
+        p.queue = e->n >= RENDER_QUEUE_MIN_ENVS ? RENDER_QUEUE_DEFAULT : 0;
+        if (p.queue == RENDER_QUEUE_DEFAULT && p.pace > 0) p.queue = RENDER_QUEUE_PACED;        // (a pace needs tickets served faster than it admits them: two counters)
+    }
+    if (p.pace < 0) p.pace = 0;
+    if (p.queue > 0) p.path = RenderPlan::QUEUE;
+    return p;
+}
+
+// One render's range: envs [env_off, env_off + nr) of the batch, `input` and `pixels` at its first env
+struct RenderRange { const uint8_t* input; uint8_t* pixels; int64_t nr, env_off; hipStream_t stream; };
+
+// The delta render of target envs whose shadow is valid: k_render_dstore behind a step that found the dirty cells, else k_render_delta.
+// 1 048 576 BossLevel envs, random actions, settings alternated in one process (tools/ab.py; profiles/render_delta/ab.jsonl),
+// k_render ms per launch: (1024 threads, 1 block per CU) interleaved 0.813, contiguous ranges 0.795, 2 blocks per CU 0.795;
+// (512, 1) 0.795; (512, 3) 0.665 <- default: three independent blocks per CU hide one another's encoding / shadow loads and
+// barriers (42 KB of LDS each: three fit).  Full render (k_render_q) 1.507.
+template <int T, int SCHED>
+static void launch_delta_ts(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
+    if (e->render_piece_bytes == 128) hipLaunchKernelGGL((k_render_delta<32, T, SCHED, 128>), dim3(blocks), dim3(T), 0, r.stream, r.nr, r.input, r.pixels, sh, e->atlas, e->lut, e->n_tiles);
+    else hipLaunchKernelGGL((k_render_delta<32, T, SCHED, 64>), dim3(blocks), dim3(T), 0, r.stream, r.nr, r.input, r.pixels, sh, e->atlas, e->lut, e->n_tiles);
+}
+template <int T>
+static void launch_delta_t(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
+    if (e->render_delta_sched == 1) launch_delta_ts<T, 1>(e, r, blocks, sh); else launch_delta_ts<T, 0>(e, r, blocks, sh);
+}
+template <int P>
+static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
+    hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->rt_dmask + r.env_off, e->atlas, e->n_tiles);
+}
+static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool from_step) {
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
+    constexpr int G = 32;
+    const int64_t groups = (r.nr + G - 1) / G;
+    const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
+    uint8_t* sh = e->rt_shadow + r.env_off * CELLS;
+    if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
+    else if (T == 512) launch_delta_t<512>(e, r, blocks, sh);
+    else launch_delta_t<1024>(e, r, blocks, sh);
+}
+
+// From 262 144 envs up: k_render_q -- ONE persistent 1024-thread block per CU, 8-env groups handed out by ONE ticket
+// counter.  Everything below was measured inside the step loop, settings alternated in one process (tools/ab.py),
+// 1 048 576 BossLevel envs, k_render ms per launch (profiles/r04/render_queue_*.jsonl; four leases = four boxes):
+//   one-shot (1024, 8) blocks (rounds 2-3)                         1.64 - 1.72
+//   queue, two blocks per CU, one counter (round 3's lead)         1.60 - 1.61
+//   queue, ONE block per CU (256 blocks), one counter              1.50            <- shipped: 6.67 TB/s, 0.83 of peak
+//   ... 192 / 224 / 320 / 512 blocks                               1.66 / 1.53 / 1.51 / 1.64;   128: 2.14
+//   ... two / eight interleaved counters                           1.56 / 1.69 - 1.77
+//   ... 2 groups per ticket, 12- / 16-env groups                   1.60 / 1.55 - 1.58 / 1.61
+//   ... 512- / 256-thread blocks (8-env groups)                    1.61 - 1.63 / 1.57 (512 blocks)
+// One counter serves ~88 M tickets/s (131 072 tickets = 1.49 ms): the shipped shape runs AT the ticket rate, and every
+// way of relieving it (more counters, bigger tickets) is slower -- the single counter is what keeps the chip's stores one
+// compact, evenly paced window.  By batch size (queue vs the one-shot shape of that size, ms per step): 131 072 envs
+// 0.221 vs 0.214, 262 144 0.414 vs 0.418, 393 216 0.614 vs 0.639, 524 288 0.809 vs 0.848 -- below 262 144 the whole
+// encoding is still in the memory-side cache and short-lived (512, 2) blocks win.
+template <int G, int T, int NC, int K>
+static void launch_queue_shape(const bbai_env* e, const RenderRange& r, const RenderPlan& p) {
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const int64_t tickets = ((r.nr + G - 1) / G + K - 1) / K;
+    const int64_t want = e->render_queue_blocks > 0 ? e->render_queue_blocks : (e->render_queue_bpc > 0 ? (int64_t)cus * e->render_queue_bpc : (int64_t)cus * 1024 / T);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, tickets));
+    hipLaunchKernelGGL((k_render_q<G, T, NC, K>), dim3(blocks), dim3(T), 0, r.stream, r.nr, r.input, r.pixels, e->atlas, e->lut, e->n_tiles, e->render_tickets, p.pace, p.shadow);
+}
+static void launch_render_queue(const bbai_env* e, const RenderRange& r, const RenderPlan& p) {
+    switch (p.queue) {     // (shapes other than 1 stay for measurements: tests/test_gpu_parity.py checks every one byte for byte)
+    default:
+    case 1: launch_queue_shape<8, 1024, 1, 1>(e, r, p); break;       // shipped
+    case 2: launch_queue_shape<8, 1024, 8, 1>(e, r, p); break;       // eight / two interleaved counters
+    case 3: launch_queue_shape<8, 1024, 2, 1>(e, r, p); break;
+    case 4: launch_queue_shape<8, 1024, 1, 2>(e, r, p); break;       // two groups per ticket
+    case 5: launch_queue_shape<12, 1024, 1, 1>(e, r, p); break;      // bigger groups
+    case 6: launch_queue_shape<16, 1024, 1, 1>(e, r, p); break;
+    case 7: launch_queue_shape<8, 512, 1, 1>(e, r, p); break;        // smaller blocks
+    case 8: launch_queue_shape<8, 256, 1, 1>(e, r, p); break;
+    case 9: launch_queue_shape<2, 512, 8, 1>(e, r, p); break;        // small groups need more counters (524 288 tickets)
+    case 10: launch_queue_shape<9, 1024, 1, 1>(e, r, p); break;      // just above the shipped group: a little more work per ticket
+    case 11: launch_queue_shape<10, 1024, 1, 1>(e, r, p); break;
+    }
+}
+
+// ONE G-env group per one-shot block of T threads, (512, 2) (round 2: profiles/r02/render_shape_*.jsonl; (1024, 8) from
+// 786 432 envs when the queue is switched off).  BBAI_RENDER_GROUP / BBAI_RENDER_TPB override (experiments).
+template <int G>
+static void launch_oneshot_g(const bbai_env* e, const RenderRange& r, int T, uint8_t* shadow) {
+    const dim3 grid((unsigned)((r.nr + G - 1) / G));
+    if (T == 1024) hipLaunchKernelGGL((k_render<G, 1024>), grid, dim3(1024), 0, r.stream, r.nr, r.input, r.pixels, e->atlas, e->lut, e->n_tiles, shadow);
+    else if (T == 512) hipLaunchKernelGGL((k_render<G, 512>), grid, dim3(512), 0, r.stream, r.nr, r.input, r.pixels, e->atlas, e->lut, e->n_tiles, shadow);
+    else hipLaunchKernelGGL((k_render<G, 256>), grid, dim3(256), 0, r.stream, r.nr, r.input, r.pixels, e->atlas, e->lut, e->n_tiles, shadow);
+}
+static void launch_render_oneshot(const bbai_env* e, const RenderRange& r, uint8_t* shadow) {
+    const bool big = e->n >= 786432;
+    int G = e->render_group, T = e->render_tpb;
+    if (G != 2 && G != 4 && G != 8) G = big ? 8 : 2;
+    if (T != 256 && T != 512 && T != 1024) T = big ? 1024 : 512;
+    if (G == 2) launch_oneshot_g<2>(e, r, T, shadow); else if (G == 4) launch_oneshot_g<4>(e, r, T, shadow); else launch_oneshot_g<8>(e, r, T, shadow);
+}
+
 static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, void* stream, int64_t n_render = -1 /* envs input / pixels hold (default: the batch); the shape follows the BATCH size */,
                          int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */,
                          bool from_step = false /* the step in front found the dirty cells (step_dirty): store them (k_render_dstore) */) {
     CallScope call(e, (hipStream_t)stream);
     if (call.rc != BBAI_OK) return call.rc;
-    const int64_t nr = n_render < 0 ? e->n : n_render;
+    const RenderRange r = {input, pixels, n_render < 0 ? e->n : n_render, env_off, (hipStream_t)stream};
     {
-    ProfScope prof_(e, 2, (hipStream_t)stream);
-    // The registered target (bbai_set_render_target): envs [env_off, env_off + nr) of it are rendered by k_render_delta, which stores
-    // only the lines whose cells changed -- or, while the shadow is not valid, by the full render below, which then also writes every
-    // tile id.  Any other render that writes into the registered buffer leaves a frame the shadow does not describe: it is invalidated.
-    // A render elsewhere leaves it alone.
-    uint8_t* const rt = e->rt_pixels;
-    const int64_t pb = PIX_BYTES;
-    const bool delta = delta_target(e, pixels, env_off, nr);
-    if (rt && !delta && pixels < rt + e->n * pb && pixels + nr * pb > rt) { e->rt_valid = false; e->rt_filled = 0; }
-    // the shadow is not valid: the full render below writes every byte of the range and, given `shadow`, every tile id of it
-    uint8_t* const shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
-    if (shadow && env_off == e->rt_filled) e->rt_filled = env_off + nr;        // (recorded before the launch: a failed launch fails the call)
-    if (shadow && e->rt_filled >= e->n) e->rt_valid = true;
-    if (delta && !shadow) {
-        const int cus = e->n_cus > 0 ? e->n_cus : 256;
-        // 1 048 576 BossLevel envs, random actions, settings alternated in one process (tools/ab.py; profiles/render_delta/ab.jsonl),
-        // k_render ms per launch: (1024 threads, 1 block per CU) interleaved 0.813, contiguous ranges 0.795, 2 blocks per CU 0.795;
-        // (512, 1) 0.795; (512, 3) 0.665 <- default: three independent blocks per CU hide one another's encoding / shadow loads and
-        // barriers (42 KB of LDS each: three fit).  Full render (k_render_q) 1.507.
-        const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
-        constexpr int G = 32;
-        const int64_t groups = (nr + G - 1) / G;
-        const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
-        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
-        uint8_t* sh = e->rt_shadow + env_off * CELLS;
-        const int pb = e->render_piece_bytes;
-        if (from_step) {
-#define RENDER_S(PP) hipLaunchKernelGGL((k_render_dstore<G, 512, PP>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, nr, pixels, sh, e->rt_dmask + env_off, \
-                                        e->atlas, e->n_tiles)
-            if (pb == 128) RENDER_S(128); else RENDER_S(64);
-#undef RENDER_S
-            HIP_TRY(hipGetLastError());
-            return call.leave();
-        }
-#define RENDER_D(TT, SS, PP) hipLaunchKernelGGL((k_render_delta<G, TT, SS, PP>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, sh, \
-                                                e->atlas, e->lut, e->n_tiles)
-#define RENDER_DP(TT, SS) do { if (pb == 128) RENDER_D(TT, SS, 128); else RENDER_D(TT, SS, 64); } while (0)
-        if (T == 512) { if (e->render_delta_sched == 1) RENDER_DP(512, 1); else RENDER_DP(512, 0); }
-        else { if (e->render_delta_sched == 1) RENDER_DP(1024, 1); else RENDER_DP(1024, 0); }
-#undef RENDER_DP
-#undef RENDER_D
+    ProfScope prof_(e, 2, r.stream);
+    const RenderPlan p = plan_render(e, pixels, env_off, r.nr);
+    if (p.path != RenderPlan::ONESHOT) {
+        if (p.path == RenderPlan::DELTA) launch_render_delta(e, r, from_step); else launch_render_queue(e, r, p);
         HIP_TRY(hipGetLastError());
         return call.leave();
     }
-    // From 262 144 envs up: k_render_q -- ONE persistent 1024-thread block per CU, 8-env groups handed out by ONE ticket
-    // counter.  Everything below was measured inside the step loop, settings alternated in one process (tools/ab.py),
-    // 1 048 576 BossLevel envs, k_render ms per launch (profiles/r04/render_queue_*.jsonl; four leases = four boxes):
-    //   one-shot (1024, 8) blocks (rounds 2-3)                         1.64 - 1.72
-    //   queue, two blocks per CU, one counter (round 3's lead)         1.60 - 1.61
-    //   queue, ONE block per CU (256 blocks), one counter              1.50            <- shipped: 6.67 TB/s, 0.83 of peak
-    //   ... 192 / 224 / 320 / 512 blocks                               1.66 / 1.53 / 1.51 / 1.64;   128: 2.14
-    //   ... two / eight interleaved counters                           1.56 / 1.69 - 1.77
-    //   ... 2 groups per ticket, 12- / 16-env groups                   1.60 / 1.55 - 1.58 / 1.61
-    //   ... 512- / 256-thread blocks (8-env groups)                    1.61 - 1.63 / 1.57 (512 blocks)
-    // One counter serves ~88 M tickets/s (131 072 tickets = 1.49 ms): the shipped shape runs AT the ticket rate, and every
-    // way of relieving it (more counters, bigger tickets) is slower -- the single counter is what keeps the chip's stores one
-    // compact, evenly paced window.  By batch size (queue vs the one-shot shape of that size, ms per step): 131 072 envs
-    // 0.221 vs 0.214, 262 144 0.414 vs 0.418, 393 216 0.614 vs 0.639, 524 288 0.809 vs 0.848 -- below 262 144 the whole
-    // encoding is still in the memory-side cache and short-lived (512, 2) blocks win.
-    // BBAI_RENDER_QUEUE / option "render_queue": -1 = by batch size (default), 0 = never, m > 0 = queue shape m of the table below.
-    const bool big = e->n >= 786432;
-    int qm = e->render_queue;
-    int pace = e->render_pace;
-    if (qm < 0) {
-        qm = e->n >= RENDER_QUEUE_MIN_ENVS ? RENDER_QUEUE_DEFAULT : 0;
-        if (qm == RENDER_QUEUE_DEFAULT && pace > 0) qm = RENDER_QUEUE_PACED;        // (a pace needs tickets served faster than it admits them: two counters)
-    }
-    if (pace < 0) pace = 0;
-    if (qm > 0) {
-        const int cus = e->n_cus > 0 ? e->n_cus : 256;
-#define RENDER_Q(GG, TT, NC, KK) do { \
-            const int64_t tickets = ((nr + GG - 1) / GG + KK - 1) / KK; \
-            const int64_t want = e->render_queue_blocks > 0 ? e->render_queue_blocks : (e->render_queue_bpc > 0 ? (int64_t)cus * e->render_queue_bpc : (int64_t)cus * 1024 / TT); \
-            const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, tickets)); \
-            hipLaunchKernelGGL((k_render_q<GG, TT, NC, KK>), dim3(blocks), dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, \
-                               e->atlas, e->lut, e->n_tiles, e->render_tickets, pace, shadow); } while (0)
-        switch (qm) {          // (shapes other than 1 stay for measurements: tests/test_gpu_parity.py checks every one byte for byte)
-        default:
-        case 1: RENDER_Q(8, 1024, 1, 1); break;       // shipped
-        case 2: RENDER_Q(8, 1024, 8, 1); break;       // eight / two interleaved counters
-        case 3: RENDER_Q(8, 1024, 2, 1); break;
-        case 4: RENDER_Q(8, 1024, 1, 2); break;       // two groups per ticket
-        case 5: RENDER_Q(12, 1024, 1, 1); break;      // bigger groups
-        case 6: RENDER_Q(16, 1024, 1, 1); break;
-        case 7: RENDER_Q(8, 512, 1, 1); break;        // smaller blocks
-        case 8: RENDER_Q(8, 256, 1, 1); break;
-        case 9: RENDER_Q(2, 512, 8, 1); break;        // small groups need more counters (524 288 tickets)
-        case 10: RENDER_Q(9, 1024, 1, 1); break;      // just above the shipped group: a little more work per ticket
-        case 11: RENDER_Q(10, 1024, 1, 1); break;
-        }
-#undef RENDER_Q
-        HIP_TRY(hipGetLastError());
-        return call.leave();
-    }
-    // Below: ONE G-env group per one-shot block of T threads, (512, 2) (round 2: profiles/r02/render_shape_*.jsonl; (1024, 8) from
-    // 786 432 envs when the queue is switched off).  BBAI_RENDER_GROUP / BBAI_RENDER_TPB override (experiments).
-    int G = e->render_group, T = e->render_tpb;
-    if (G != 2 && G != 4 && G != 8) G = big ? 8 : 2;
-    if (T != 256 && T != 512 && T != 1024) T = big ? 1024 : 512;
-    const dim3 grid((unsigned)((nr + G - 1) / G));
-#define RENDER_LAUNCH(GG, TT) hipLaunchKernelGGL((k_render<GG, TT>), grid, dim3(TT), 0, (hipStream_t)stream, nr, input, pixels, e->atlas, e->lut, e->n_tiles, shadow)
-#define RENDER_G(GG) do { if (T == 1024) RENDER_LAUNCH(GG, 1024); else if (T == 512) RENDER_LAUNCH(GG, 512); else RENDER_LAUNCH(GG, 256); } while (0)
-    if (G == 2) RENDER_G(2); else if (G == 4) RENDER_G(4); else RENDER_G(8);
-#undef RENDER_G
-#undef RENDER_LAUNCH
+    launch_render_oneshot(e, r, p.shadow);
     }
     HIP_TRY(hipGetLastError());
     return call.leave();

@@ -1,6 +1,6 @@
 // bbai_kernels.hpp -- what the engine's translation units share on the device side: the look-ahead ring's addressing, the refill list's
-// shape, the lane-group context of the generators.  (bbai_engine.hip: every kernel but one; bbai_genlane.hip: k_pregen_lane, compiled
-// with its own flags -- see there.)
+// shape, the lane-group context of the generators.  (bbai_engine.hip: every kernel but one, with the headers it includes
+// for a kernel family each -- bbai_render.hpp, bbai_demo.hpp; bbai_genlane.hip: k_pregen_lane, compiled with its own flags -- see there.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbai_types.hpp"

@@ -16,6 +16,7 @@ static bool g_bot_aligned_ok = true;         // hs_bot_set_aligned(0): _find_obj
 #include <ucontext.h>
 #include <cstdlib>
 #include "../../babyai_amd/csrc/bbai_seed.hpp"
+#include "../../babyai_amd/csrc/bbai_render.hpp"
 
 using namespace bbai;
 
@@ -33,6 +34,9 @@ struct HostCtx {
 extern "C" {
 
 int hs_fill_layout(LevelCfg* cfg) { return fill_layout(*cfg); }
+
+// the delta render's geometry (bbai_render.hpp): the cells bytes [s, t) of an env's pixel image are drawn from
+uint64_t hs_line_cells(int s, int t) { return line_cells(s, t); }
 
 void hs_seed(uint64_t seed, uint32_t* mt) { seed_env(seed, mt); }
 

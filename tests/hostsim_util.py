@@ -38,6 +38,8 @@ def lib():
         L.hs_observe_cpl.argtypes = [P, P, P, ctypes.c_int, P, P]
         L.hs_cid_lookup.argtypes = [P, ctypes.c_int, ctypes.c_int]
         L.hs_fill_layout.argtypes = [P]
+        L.hs_line_cells.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.hs_line_cells.restype = ctypes.c_uint64
         L.hs_start_carry.argtypes = [P, P, P, P]
         L.hs_bot_decide.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.hs_bot_set_eager.argtypes = [ctypes.c_int]

@@ -1,4 +1,4 @@
-"""The delta render's line rule on the host (babyai_amd/csrc/bbai_engine.hip, k_render_delta): a 128-byte line of the pixel
+"""The delta render's line rule on the host (babyai_amd/csrc/bbai_render.hpp, k_render_delta): a 128-byte line of the pixel
 buffer is stored iff a cell it draws from changed its atlas tile id.  Checked against the reference's own frames (the golden pixel
 traces) laid out back to back as the device buffer holds them: every line whose bytes differ from the previous frame is marked,
 and storing only the marked lines over the previous frame gives the new frame -- across env boundaries (9408 = 73.5 lines)."""
@@ -7,6 +7,8 @@ import os
 
 import numpy as np
 import pytest
+
+from hostsim_util import lib
 
 PIX_BYTES, LINE, UNIT = 9408, 128, 8
 GOLDEN = [p for p in sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))]
@@ -49,6 +51,19 @@ def test_line_table_covers_every_byte_once():
         env, off = buf // PIX_BYTES, buf % PIX_BYTES
         assert {(int(e), int(c)) for e, c in zip(env, cob[off])} == {(lea[l], c) for c in ma[l]} | {(lea[l] + 1, c) for c in mb[l]}
     assert sum(1 for m in mb if m) == 4       # an odd env starts mid-line: 4 lines of a unit span two envs
+
+
+def test_line_table_is_the_headers():
+    """The numpy table above against line_cells of bbai_render.hpp, called as init_line_table calls it: all 588 lines of a unit."""
+    L = lib()
+    lea, ma, mb = line_table()
+    bits = lambda cells: sum(1 << c for c in cells)
+    for l in range(588):
+        b0, b1 = l * LINE, l * LINE + LINE
+        ea, eb = b0 // PIX_BYTES, (b1 - 1) // PIX_BYTES
+        assert ea == lea[l]
+        assert L.hs_line_cells(b0 - ea * PIX_BYTES, ((ea + 1) * PIX_BYTES if eb != ea else b1) - ea * PIX_BYTES) == bits(ma[l]), l
+        assert (L.hs_line_cells(0, b1 - eb * PIX_BYTES) if eb != ea else 0) == bits(mb[l]), l
 
 
 @pytest.mark.parametrize("path", [p for p in GOLDEN if os.path.basename(p) in ("BossLevel.npz", "GoToLocal.npz")])      # (the traces with pixel frames)

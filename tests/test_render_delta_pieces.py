@@ -1,4 +1,4 @@
-"""The delta render's piece rule on the host (babyai_amd/csrc/bbai_engine.hip, store_dirty_pieces; option "render_piece_bytes", default
+"""The delta render's piece rule on the host (babyai_amd/csrc/bbai_render.hpp, store_dirty_pieces; option "render_piece_bytes", default
 64): a 64-byte piece of an env's image is stored iff a cell it draws from changed its atlas tile id.  Checked against the reference's own
 frames (the golden pixel traces) laid out back to back as the device buffer holds them: storing only the marked pieces over the previous
 frame gives the new frame -- 64 divides 9408, so every piece lies inside one env and the rule needs no env pairs; the traces cross resets."""
@@ -7,6 +7,8 @@ import os
 
 import numpy as np
 import pytest
+
+from hostsim_util import lib
 
 PIX_BYTES, PIECE = 9408, 64
 GOLDEN = [p for p in sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))]
@@ -42,6 +44,14 @@ def test_piece_table():
     cob = cell_of_byte()
     for p in range(len(t)):                                    # the marked cells are exactly the cells of the piece's bytes
         assert set(np.nonzero(t[p])[0].tolist()) == set(cob[p * PIECE:(p + 1) * PIECE].tolist())
+
+
+def test_piece_table_is_the_headers():
+    """The numpy table above against line_cells of bbai_render.hpp, called as init_piece_cells calls it: all 147 pieces of an env."""
+    L = lib()
+    t = piece_table()
+    for p in range(len(t)):
+        assert L.hs_line_cells(p * PIECE, p * PIECE + PIECE) == sum(1 << int(c) for c in np.nonzero(t[p])[0]), p
 
 
 @pytest.mark.parametrize("path", [p for p in GOLDEN if os.path.basename(p) in ("BossLevel.npz", "GoToLocal.npz")])      # (the traces with pixel frames)
