@@ -61,6 +61,12 @@ static thread_local char g_err[512] = "";
             return BBAI_ERR_HIP;                                                              \
         }                                                                                     \
     } while (0)
+// ... and for the helpers below that return a BBAI_* code (g_err was written where it failed)
+#define BBAI_TRY(expr)                                                                        \
+    do {                                                                                      \
+        int rc_ = (expr);                                                                     \
+        if (rc_ != BBAI_OK) return rc_;                                                       \
+    } while (0)
 
 #define ARG_FAIL(msg)                                                                        \
     do {                                                                                      \
@@ -92,7 +98,7 @@ constexpr int MAX_SIDES = 8;            // look-ahead streams a window's refill 
 constexpr int MAX_PERIOD = 96;          // refill period B (ticks per look-ahead refill); ring depth D = 2B (+ 1 in place): slot numbers and per-window counts stay bytes
 constexpr int NWIN = 34;                // window buffers (see "the windows' bookkeeping" below): at most 33 refills outstanding, whatever B
 
-struct bbai_env {
+struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defaults and clamps: KNOBS, below the kernels)
     LevelCfg cfg;
     int64_t n;
     int device;
@@ -134,15 +140,15 @@ struct bbai_env {
     hipStream_t mark_stream;
     hipEvent_t ev_part[MAX_SIDES];
     int side_prio;
-    int n_sides;          // BBAI_LOOKAHEAD_STREAMS / option "lookahead_streams"
+    int n_sides;          // look-ahead streams in use (set_sides)
     int32_t* gen_lists[MAX_SIDES];      // sides >= 1 (side 0: gen_list / gen_count below)
     uint32_t* gen_counts[MAX_SIDES];
     hipStream_t split;    // bbai_step_render: the second half-batch's k_step runs here, under the first half's render
     hipEvent_t ev_split0, ev_splitB;
-    int step_render_split;   // BBAI_STEP_RENDER_SPLIT / option "step_render_split": 1 = split (from STEP_RENDER_SPLIT_MIN envs), 0 = never, -1 = default
+    int step_render_split;   // 1 = split (from STEP_RENDER_SPLIT_MIN envs), 0 = never, -1 = default
     hipEvent_t ev_consumed;
     hipEvent_t ev_refill[NWIN];     // recorded behind every window's refill; only waited for in strict mode (below) -- k_gate reads flow[FLOW_REFILLED]
-    int gate_strict;      // BBAI_GATE_STRICT / option "gate_strict": 1 = rounds 1-4's rule as well: the stream waits (an event) for the refill of window
+    int gate_strict;      // 1 = rounds 1-4's rule as well: the stream waits (an event) for the refill of window
                           // x - 2 before window x starts, so k_gate never has to wait (A/B runs; a fallback should a profiler serialise the two streams)
     // The relaxed gate is a device-side spin on a value the look-ahead stream's k_mark stores: it relies on kernels of the two streams making
     // progress CONCURRENTLY, which HIP does not promise (streams can share a hardware queue; a profiler can serialise launches).  So:
@@ -155,27 +161,27 @@ struct bbai_env {
     hipStream_t probed[8];            // caller streams already probed ...
     bool probed_ok[8];                // ... and what the probe said
     int n_probed;
-    int gate_probe;                   // BBAI_GATE_PROBE (default 1): 0 = trust the streams (no probe), 2 = treat every probe as failed (tests)
+    int gate_probe;                   // 1 (default) = probe, 0 = trust the streams (no probe), 2 = treat every probe as failed (tests)
     int gate_forced;                  // the current caller stream failed the probe: strict rule
     hipStream_t last_stream;   // the caller's stream of the previous call (compared, never used): a handle follows ONE stream
     bool have_stream;          // at a time; a call on another stream waits for ev_switch = end of the previous call
     hipEvent_t ev_switch;      // (enter_call / leave_call)
     bool call_events;
-    int render_tpb;       // BBAI_RENDER_TPB: 256 / 512 / 1024 threads per render block; anything else = by batch size
-    int render_group;     // BBAI_RENDER_GROUP: 2, 4 or 8 envs per one-shot render block; anything else = by batch size (bbai_render)
-    int pregen_cap;       // BBAI_PREGEN_BLOCKS: upper bound on look-ahead lane groups per launch (experiments)
-    int pregen_per_group; // BBAI_PREGEN_PER_GROUP / option "pregen_per_group": single-room levels: list entries per working lane group of a refill (default 32 = one per tick of the longest window)
-    int pregen_min;       // BBAI_PREGEN_MIN / option "pregen_min": single-room levels: lane groups that work on a refill at least (k_pregen: entries / 32 otherwise); 0 = the whole grid, as mazes always get
-    int pregen_group;     // BBAI_PREGEN_GROUP: lanes per env in k_pregen: 32 (default: two envs per wave), 16 or 64
+    int render_tpb;       // 256 / 512 / 1024 threads per render block; anything else = by batch size
+    int render_group;     // 2, 4 or 8 envs per one-shot render block; anything else = by batch size (bbai_render)
+    int pregen_cap;       // "pregen_blocks": upper bound on look-ahead lane groups per launch (experiments)
+    int pregen_per_group; // single-room levels: list entries per working lane group of a refill
+    int pregen_min;       // single-room levels: lane groups that work on a refill at least (k_pregen: entries / 32 otherwise); 0 = the whole grid, as mazes always get
+    int pregen_group;     // lanes per env in k_pregen: 32 (two envs per wave), 16 or 64
     // the lane = level generator (bbai_genl.hpp, k_pregen_lane): every LevelGen parameterisation and the single-instruction levels without a lock-first prologue
     unsigned long long* tap_mask; uint32_t* tap_rank0; int32_t* tap_perm; int64_t* tap_ids; int64_t tap_count;     // bbai_step_tap_set: the envs bbai_step_tapped logs
     uint32_t* mtt;        // [n][2][MT_N] tempered outputs of the latest and the previous MT19937 generation of every env (NULL: kind not covered)
     uint8_t* mtpar;       // [n] which half holds the latest generation
     uint8_t* lane_tmpl;   // the kind's record template + C plane (lane_build_template)
     int lane_words;       // LDS words per lane (lane_layout)
-    int pregen_lane;      // BBAI_PREGEN_LANE / option "pregen_lane": 1 (default where covered) = k_pregen_lane generates, 0 = the lane-group kernel k_pregen
-    int lane_blocks;      // BBAI_LANE_BLOCKS / option "lane_blocks": upper bound on its waves per launch
-    int step_prio;        // BBAI_STEP_PRIO: s_setprio level of the step-path kernels' waves (they share CUs with k_pregen)
+    int pregen_lane;      // BBAI_PREGEN_LANE: 1 (default where covered) = k_pregen_lane generates, 0 = the lane-group kernel k_pregen
+    int lane_blocks;      // upper bound on its waves per launch
+    int step_prio;        // s_setprio level of the step-path kernels' waves (they share CUs with k_pregen)
     // optional per-kernel timing (bbai_profile): HIP event pairs on the launch stream around k_step / k_consume / k_render
     bool prof_on;
     struct ProfSlot { hipEvent_t a, b; bool used; } prof[3][PROF_RING];
@@ -183,7 +189,7 @@ struct bbai_env {
     double prof_ms[3];
     int64_t prof_n[3];
     int64_t prof_step_ticks;   // steps the bracketed k_step launches took (a bbai_rollout launch takes up to a window's worth): option "profile_step_ticks"
-    int rollout_multi;    // BBAI_ROLLOUT_MULTI / option "rollout_multi": bbai_rollout steps up to a look-ahead window per k_step launch (1, default) or one step per launch (0)
+    int rollout_multi;    // bbai_rollout steps up to a look-ahead window per k_step launch (1, default) or one step per launch (0)
     int64_t tick;         // number of consume_and_refill calls so far
     uint8_t* vplane;      // [n][v_bytes] window plane (bbai_types.hpp): one 128-byte line per window-origin class; BBAI_VPLANE=0: none
     uint16_t* fcache;     // [n] appearance of the front cell (low byte) and of the carried object (high byte) after the last step
@@ -191,27 +197,27 @@ struct bbai_env {
     uint8_t* lsm;         // [n] done-action verifier mode only (BABYAI_DONE_ACTIONS / bbai_set_done_actions): bit k = leaf k's
                           //     lastStepMatch (babyai/levels/verifier.py:213-230); NULL = the normal mode
     unsigned int* render_tickets;   // [64][64] ticket counters of k_render_q + its departure counter; zero between launches (the kernel leaves them so)
-    int render_queue;     // BBAI_RENDER_QUEUE / option "render_queue": -1 = by batch size (default), 0 = one-shot blocks only, m = queue shape m (render_launch)
-    int render_queue_bpc; // option "render_queue_bpc": persistent render blocks per CU (0 = 1024 threads' worth: ONE 1024-thread block per CU --
+    int render_queue;     // -1 = by batch size (default), 0 = one-shot blocks only, m = queue shape m (render_launch)
+    int render_queue_bpc; // persistent render blocks per CU (0 = 1024 threads' worth: ONE 1024-thread block per CU --
                           // profiles/r04/render_queue_ab_1M_b.jsonl: k_render 1.50 ms against 1.61 with two)
-    int render_queue_blocks;   // option "render_queue_blocks": their total number (0 = by render_queue_bpc)
-    int render_pace;      // option "render_pace" (experiment): 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
+    int render_queue_blocks;   // their total number (0 = by render_queue_bpc)
+    int render_pace;      // (experiment) 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
                           // one counter serves them
     // delta rendering (bbai_set_render_target): the registered buffer, and the atlas tile ids of the frame it holds
     uint8_t* rt_pixels;   // the registered caller-owned uint8[n][9408] buffer (NULL: none); only this handle's renders write there
     uint8_t* rt_shadow;   // [n][49] tile id of every cell of the frame in rt_pixels (allocated at the first registration)
     bool rt_valid;        // rt_shadow describes rt_pixels; false after registration / bbai_set_atlas / bbai_render_invalidate / a full render into it
     int64_t rt_filled;    // while not valid: envs [0, rt_filled) rewritten by full renders with shadow ids since (a split render's halves)
-    int render_delta;     // BBAI_RENDER_DELTA / option "render_delta": 1 (default) = renders into the registered buffer store only changed lines
-    int render_delta_sched;    // option "render_delta_sched": 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
-    int render_delta_tpb;      // option "render_delta_tpb": 512 (default, also for 0) or 1024 threads per delta render block
-    int render_delta_bpc;      // option "render_delta_bpc": delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
+    int render_delta;     // 1 (default) = renders into the registered buffer store only changed lines
+    int render_delta_sched;    // 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
+    int render_delta_tpb;      // 512 (default, also for 0) or 1024 threads per delta render block
+    int render_delta_bpc;      // delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
     uint64_t* rt_dmask;   // [n] the dirty-cell mask of every env, left by k_step for the store-only render (k_render_dstore); allocated with rt_shadow
-    int render_piece_bytes;    // option "render_piece_bytes": the delta render's store unit, 64-byte pieces (default) or 128 (whole lines)
-    int render_delta_from_step;   // option "render_delta_from_step": 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
+    int render_piece_bytes;    // the delta render's store unit, 64-byte pieces (default) or 128 (whole lines)
+    int render_delta_from_step;   // 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
-    int done_action_enum; // option "done_action_enum": done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
-    int consume_fused;    // BBAI_CONSUME_FUSED / option "consume_fused": -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
+    int done_action_enum; // done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
+    int consume_fused;    // -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
     int inplace;          // BBAI_INPLACE: the in-place layout (live_slot below): an env's live record IS the look-ahead slot its episode was generated into
     uint8_t* atlas;       // [n_tiles][192]
     uint8_t* lut;         // [2][256]
@@ -219,13 +225,13 @@ struct bbai_env {
     uint8_t* grid_atlas[3];   // full-grid picture (bbai_set_grid_atlas), tile sizes 8 / 16 / 32: [GRID_MAX_TILES + 1][ts][ts][3]
     uint8_t* grid_lut[3];     // [2][5][256]
     int grid_tiles[3];        // installed tiles (0: none)
-    int grid_bpc;             // option "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
+    int grid_bpc;             // "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
     bool seeded, live;
     uint8_t* bot_state;   // [n][bot_state_bytes(bot_stack)] the expert's per-env plan (bbai_bot_act; allocated on first use)
     int bot_stack;        // subgoal stack capacity per env (BBAI_BOT_STACK, default 48)
     uint16_t* bot_work;   // [bot_threads][BOT_WORK_WORDS] BFS scratch per resident thread
     uint32_t* bot_rows;   // [bot_threads][2 * MAX_W] row masks of the second (through-blockers) search
-    int bot_group;        // lanes per env of the expert kernel: 0 = lane = env (k_bot), 16 = one 16-lane group per env (k_botg); BBAI_BOT_GROUP / option
+    int bot_group;        // lanes per env of the expert kernel: 0 = lane = env (k_bot), 16 = one 16-lane group per env (k_botg)
     int bot_eager;        // BBAI_BOT_EAGER (default 1): expand the first search tree at the top of every decision
     int64_t bot_threads;
     uint64_t* bot_stats;  // [2] decisions that ended in a dead bot: by the reference's rules / by our capacity limits
@@ -2021,21 +2027,21 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
     bbai_env* e = new bbai_env();
     memset(e, 0, sizeof(*e));
     e->cfg = c; e->n = n_envs; e->device = device;
-    { const char* ev = getenv("BBAI_BOT_GROUP"); if (ev) e->bot_group = atoi(ev); }
     hipError_t err = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) { if (err == hipSuccess) err = hipMalloc(p, bytes); };
-    alloc((void**)&e->rec, (size_t)n_envs * c.rec_bytes);
-    alloc((void**)&e->hot, (size_t)n_envs * sizeof(Hot));
+    auto zalloc = [&](void** p, size_t bytes) { alloc(p, bytes); if (err == hipSuccess) err = hipMemset(*p, 0, bytes); };      // starts zeroed
+    zalloc((void**)&e->rec, (size_t)n_envs * c.rec_bytes);
+    zalloc((void**)&e->hot, (size_t)n_envs * sizeof(Hot));        // (slot 0 before any seed: an in-place handle that is only imported into keeps its live records in slot depth - 1)
     alloc((void**)&e->stale, (size_t)n_envs * 8);
     alloc((void**)&e->mt, (size_t)n_envs * MT_N * 4);
     alloc((void**)&e->mti, (size_t)n_envs * 4);
-    alloc((void**)&e->vhead, (size_t)n_envs * 4);
-    alloc((void**)&e->vset, (size_t)n_envs * 8 * 8);
-    alloc((void**)&e->pending, NWIN * (size_t)n_envs);
-    alloc((void**)&e->first_slot, NWIN * (size_t)n_envs);
-    alloc((void**)&e->win_meta, NWIN * META_U32 * 4);
-    alloc((void**)&e->totals, SHARDS * SHARD_U64 * 8);
-    alloc((void**)&e->flow, FLOW_WORDS * 8);
+    zalloc((void**)&e->vhead, (size_t)n_envs * 4);
+    zalloc((void**)&e->vset, (size_t)n_envs * 8 * 8);
+    zalloc((void**)&e->pending, NWIN * (size_t)n_envs);
+    zalloc((void**)&e->first_slot, NWIN * (size_t)n_envs);
+    zalloc((void**)&e->win_meta, NWIN * META_U32 * 4);
+    zalloc((void**)&e->totals, SHARDS * SHARD_U64 * 8);
+    zalloc((void**)&e->flow, FLOW_WORDS * 8);
     alloc((void**)&e->gen_list, (size_t)SHARDS * (size_t)gen_sublist_cap(n_envs) * 4);
     alloc((void**)&e->gen_count, SHARDS * GEN_COUNT_U32 * 4);
     e->gen_lists[0] = e->gen_list; e->gen_counts[0] = e->gen_count;         // (further look-ahead streams' lists: set_sides)
@@ -2047,13 +2053,13 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
     {
         const char* vv = getenv("BBAI_VPLANE");              // 0: round 2's record-only step path (A/B runs)
         if (!(vv && atoi(vv) == 0) && !e->inplace) {
-            alloc((void**)&e->vplane, (size_t)n_envs * v_bytes(c));
-            alloc((void**)&e->fcache, (size_t)n_envs * 2);
+            zalloc((void**)&e->vplane, (size_t)n_envs * v_bytes(c));
+            zalloc((void**)&e->fcache, (size_t)n_envs * 2);
         }
         const char* cv = getenv("BBAI_CPLANE");              // 0: the in-place step path of rounds 4-5 (window out of the record; A/B runs)
         if (e->inplace && cpl_ok(c) && !(cv && atoi(cv) == 0)) {
-            alloc((void**)&e->cplane, (size_t)n_envs * cpl_bytes(c));
-            alloc((void**)&e->fcache, (size_t)n_envs * 2);
+            zalloc((void**)&e->cplane, (size_t)n_envs * cpl_bytes(c));
+            zalloc((void**)&e->fcache, (size_t)n_envs * 2);
         }
     }
     if (lane_gen_ok(c) && (!e->inplace || cpl_ok(c))) {
@@ -2062,18 +2068,14 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
         // lasts milliseconds as ONE level per lane where the lane-group kernel needs a third of that -- the mazes keep k_pregen.
         const char* lv = getenv("BBAI_PREGEN_LANE");
         e->pregen_lane = lv ? (atoi(lv) != 0) : (c.num_rows * c.num_cols == 1);
-        const char* lb = getenv("BBAI_LANE_BLOCKS");
-        e->lane_blocks = lb ? std::max(1, atoi(lb)) : 16384;
         e->lane_words = lane_layout(c).words;
-        alloc((void**)&e->mtt, (size_t)n_envs * 2 * MT_N * 4);
-        alloc((void**)&e->mtpar, (size_t)n_envs);
+        zalloc((void**)&e->mtt, (size_t)n_envs * 2 * MT_N * 4);
+        zalloc((void**)&e->mtpar, (size_t)n_envs);
         alloc((void**)&e->lane_tmpl, (size_t)lane_template_bytes(c));
         if (err == hipSuccess) {
             std::vector<uint8_t> t((size_t)lane_template_bytes(c));
             lane_build_template(c, t.data());
             err = hipMemcpy(e->lane_tmpl, t.data(), t.size(), hipMemcpyHostToDevice);
-            if (err == hipSuccess) err = hipMemset(e->mtpar, 0, (size_t)n_envs);
-            if (err == hipSuccess) err = hipMemset(e->mtt, 0, (size_t)n_envs * 2 * MT_N * 4);
         }
     }
     {
@@ -2103,11 +2105,16 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
             e->period = b;
             e->depth = 2 * b + e->inplace;         // (in-place: the live slot + the 2B look-ahead levels)
             const size_t D = (size_t)e->depth;
+            const size_t obs_bytes = e->inplace ? D * (size_t)n_envs * OBS_SLOT : 0;
             hipError_t r1 = hipMalloc((void**)&e->next_rec, D * slot_bytes);
             hipError_t r2 = r1 == hipSuccess ? hipMalloc((void**)&e->next_hot, D * (size_t)n_envs * sizeof(Hot)) : r1;
             hipError_t r3 = r2;
-            if (r3 == hipSuccess && e->inplace) r3 = hipMalloc((void**)&e->next_obs, D * (size_t)n_envs * OBS_SLOT);
-            if (r3 == hipSuccess) break;
+            if (r3 == hipSuccess && obs_bytes) r3 = hipMalloc((void**)&e->next_obs, obs_bytes);
+            if (r3 == hipSuccess) {                        // (the ring that fits starts zeroed; next_hot is written by bbai_seed)
+                err = hipMemset(e->next_rec, 0, D * slot_bytes);
+                if (err == hipSuccess && obs_bytes) err = hipMemset(e->next_obs, 0, obs_bytes);
+                break;
+            }
             (void)hipGetLastError();                       // clear the sticky out-of-memory error before retrying
             if (e->next_rec) { (void)hipFree(e->next_rec); e->next_rec = nullptr; }
             if (e->next_hot) { (void)hipFree(e->next_hot); e->next_hot = nullptr; }
@@ -2118,13 +2125,13 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
     {
         // babyai/levels/verifier.py:17 `use_done_actions = os.environ.get('BABYAI_DONE_ACTIONS', False)`: any non-empty value
         const char* dv = getenv("BABYAI_DONE_ACTIONS");
-        if (dv && dv[0]) alloc((void**)&e->lsm, (size_t)n_envs);
+        if (dv && dv[0]) zalloc((void**)&e->lsm, (size_t)n_envs);
     }
     alloc((void**)&e->reset_list, (size_t)n_envs * 4);
     alloc((void**)&e->reset_slot, (size_t)n_envs);
-    alloc((void**)&e->counters, 128);
+    zalloc((void**)&e->counters, 128);
     alloc((void**)&e->atlas, MAX_TILES * TILE_BYTES);
-    alloc((void**)&e->render_tickets, 64 * 64 * 4);
+    zalloc((void**)&e->render_tickets, 64 * 64 * 4);
     alloc((void**)&e->lut, 512);
     if (err == hipSuccess) {
         void* hf = nullptr;
@@ -2150,6 +2157,56 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
 
 }  // extern "C"
 
+// The performance knobs (include/bbai.h: bbai_set_option), one row each: the option's name, the BBAI_* variable bbai_create reads (or none), the
+// field, the default, and how a raw value -- from the variable or from bbai_set_option alike -- becomes the stored one.  The read-only rows
+// at the end are looked up by bbai_get_option alone (their fields are set elsewhere).  Never semantics: every setting produces the same bytes.
+enum KnobNorm { AS_IS, FLAG /* v != 0 */, AT_LEAST /* max(lo, v) */, TRI /* v < 0: -1, else v != 0 */ };
+struct Knob { const char* name; const char* var; int bbai_env::*field; int def; KnobNorm norm; int lo; bool read_only; };
+static const Knob KNOBS[] = {
+    {"render_queue", "BBAI_RENDER_QUEUE", &bbai_env::render_queue, -1},
+    {"render_queue_bpc", nullptr, &bbai_env::render_queue_bpc, 0},
+    {"render_queue_blocks", nullptr, &bbai_env::render_queue_blocks, 0},
+    {"render_pace", "BBAI_RENDER_PACE", &bbai_env::render_pace, 0, AT_LEAST, 0},
+    {"render_group", "BBAI_RENDER_GROUP", &bbai_env::render_group, 0},
+    {"render_tpb", "BBAI_RENDER_TPB", &bbai_env::render_tpb, 0},
+    {"render_delta", "BBAI_RENDER_DELTA", &bbai_env::render_delta, 1, FLAG},                  // (a set also drops the shadow)
+    {"render_delta_sched", nullptr, &bbai_env::render_delta_sched, 0},
+    {"render_delta_tpb", nullptr, &bbai_env::render_delta_tpb, 0},
+    {"render_delta_bpc", nullptr, &bbai_env::render_delta_bpc, 0, AT_LEAST, 0},
+    {"render_delta_from_step", nullptr, &bbai_env::render_delta_from_step, -1, TRI},
+    {"render_piece_bytes", nullptr, &bbai_env::render_piece_bytes, RENDER_PIECE_DEFAULT},   // (64 or 128: bbai_set_option refuses the rest)
+    {"grid_render_bpc", nullptr, &bbai_env::grid_bpc, 0, AT_LEAST, 0},
+    {"step_prio", "BBAI_STEP_PRIO", &bbai_env::step_prio, 1},                          // (never slower, GoTo 131 072 envs -2 %: profiles/r03/step_prio_ab.jsonl)
+    {"pregen_group", "BBAI_PREGEN_GROUP", &bbai_env::pregen_group, 32},
+    // lane groups of a refill launch at most: 16 384 = two generator waves per SIMD of the part, the other half of every SIMD stays with the step
+    // kernels (profiles/r05/pregen_residency_cap_ab.jsonl, ms per step at 32 768 / 16 384 / 8 192 / 4 096 groups: GoTo 131 072 envs 0.0438 / 0.0390 /
+    // 0.0395 / 0.0478; BossLevel encoded 1 048 576 0.110 / 0.104 / 0.104; BossLevel pixels 131 072: no difference).  bbai_seed's first fill
+    // (nothing else runs) takes the whole part: 32 768.
+    {"pregen_blocks", "BBAI_PREGEN_BLOCKS", &bbai_env::pregen_cap, 16384, AT_LEAST, 64},
+    {"pregen_min", "BBAI_PREGEN_MIN", &bbai_env::pregen_min, 6144, AT_LEAST, 0},
+    {"pregen_per_group", "BBAI_PREGEN_PER_GROUP", &bbai_env::pregen_per_group, 12, AT_LEAST, 1},
+    {"lane_blocks", "BBAI_LANE_BLOCKS", &bbai_env::lane_blocks, 16384, AT_LEAST, 1},            // (0 on a handle without the lane generator: create_finish)
+    {"consume_fused", "BBAI_CONSUME_FUSED", &bbai_env::consume_fused, -1},
+    {"gate_strict", "BBAI_GATE_STRICT", &bbai_env::gate_strict, 0, FLAG},
+    {"gate_probe", "BBAI_GATE_PROBE", &bbai_env::gate_probe, 1},                       // (a set also forgets the verdicts)
+    {"bot_group", "BBAI_BOT_GROUP", &bbai_env::bot_group, 0},
+    {"step_render_split", "BBAI_STEP_RENDER_SPLIT", &bbai_env::step_render_split, -1},
+    {"rollout_multi", "BBAI_ROLLOUT_MULTI", &bbai_env::rollout_multi, 1},
+    {"done_action_enum", nullptr, &bbai_env::done_action_enum, 0, FLAG},                      // (the one SEMANTIC switch in this list: include/bbai.h bbai_set_done_actions)
+    {"pregen_lane", nullptr, &bbai_env::pregen_lane, 0, AS_IS, 0, true},                              // (set: bbai_set_option converts the generator state)
+    {"lookahead_streams", nullptr, &bbai_env::n_sides, 0, AS_IS, 0, true},                            // (set: set_sides)
+    {"gate_forced_strict", nullptr, &bbai_env::gate_forced, 0, AS_IS, 0, true},                       // 1: the caller's stream failed the concurrency probe
+    {"inplace", nullptr, &bbai_env::inplace, 0, AS_IS, 0, true},
+    {"lookahead_period", nullptr, &bbai_env::period, 0, AS_IS, 0, true},                              // the refill period the handle chose
+};
+static const Knob* find_knob(const char* name) {
+    for (const Knob& k : KNOBS) if (!strcmp(name, k.name)) return &k;
+    return nullptr;
+}
+static int knob_value(const Knob& k, int v) {
+    return k.norm == FLAG ? v != 0 : k.norm == AT_LEAST ? std::max(k.lo, v) : k.norm == TRI ? (v < 0 ? -1 : v != 0) : v;
+}
+
 // The look-ahead streams beyond the first, and the stream k_mark needs once there are several, exist only while asked for: every HIP stream
 // is a hardware queue, and a dozen of them made EVERY dispatch of a handle that used two wait its turn (k_step 10 -> 50 us whenever a refill ran,
 // profiles/r06/NOTES.md section 9).
@@ -2171,35 +2228,10 @@ static int set_sides(bbai_env* e, int want) {
     return BBAI_OK;
 }
 static int create_finish(bbai_env* e) {
-    const LevelCfg& c = e->cfg;
-    const int64_t n_envs = e->n;
-    const size_t D = (size_t)e->depth;
-    HIP_TRY(hipMemset(e->rec, 0, (size_t)n_envs * c.rec_bytes));
-    HIP_TRY(hipMemset(e->hot, 0, (size_t)n_envs * sizeof(Hot)));       // (slot 0 before any seed: an in-place handle that is only imported into keeps its live records in slot depth - 1)
-    HIP_TRY(hipMemset(e->next_rec, 0, D * (size_t)n_envs * c.rec_bytes));
-    if (e->next_obs) HIP_TRY(hipMemset(e->next_obs, 0, D * (size_t)n_envs * OBS_SLOT));
-    HIP_TRY(hipMemset(e->pending, 0, NWIN * (size_t)n_envs));
-    HIP_TRY(hipMemset(e->first_slot, 0, NWIN * (size_t)n_envs));
-    HIP_TRY(hipMemset(e->win_meta, 0, NWIN * META_U32 * 4));
-    HIP_TRY(hipMemset(e->totals, 0, SHARDS * SHARD_U64 * 8));
-    HIP_TRY(hipMemset(e->flow, 0, FLOW_WORDS * 8));
-    HIP_TRY(hipMemset(e->vhead, 0, (size_t)n_envs * 4));
-    HIP_TRY(hipMemset(e->vset, 0, (size_t)n_envs * 64));
-    HIP_TRY(hipMemset(e->counters, 0, 128));
-    HIP_TRY(hipMemset(e->render_tickets, 0, 64 * 64 * 4));
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess) cus = 0;
         e->n_cus = cus;
-    }
-    if (e->lsm) HIP_TRY(hipMemset(e->lsm, 0, (size_t)n_envs));
-    if (e->vplane) {
-        HIP_TRY(hipMemset(e->vplane, 0, (size_t)n_envs * v_bytes(c)));
-        HIP_TRY(hipMemset(e->fcache, 0, (size_t)n_envs * 2));
-    }
-    if (e->cplane) {
-        HIP_TRY(hipMemset(e->cplane, 0, (size_t)n_envs * cpl_bytes(c)));
-        HIP_TRY(hipMemset(e->fcache, 0, (size_t)n_envs * 2));
     }
     {
         // The look-ahead stream.  (Confining it to a subset of the CUs with a CU mask was measured in round 3 --
@@ -2215,7 +2247,7 @@ static int create_finish(bbai_env* e) {
         HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, e->side_prio));
         e->sides[0] = e->side;
         const char* ls = getenv("BBAI_LOOKAHEAD_STREAMS");
-        { int rc = set_sides(e, ls ? atoi(ls) : LOOKAHEAD_STREAMS_DEFAULT); if (rc != BBAI_OK) return rc; }
+        BBAI_TRY(set_sides(e, ls ? atoi(ls) : LOOKAHEAD_STREAMS_DEFAULT));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_consumed, hipEventDisableTiming));
         HIP_TRY(hipStreamCreateWithFlags(&e->split, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_split0, hipEventDisableTiming));
@@ -2226,42 +2258,11 @@ static int create_finish(bbai_env* e) {
     {
         const char* cv = getenv("BBAI_CALL_EVENTS");
         e->call_events = cv && atoi(cv) != 0;
-        const char* ev = getenv("BBAI_PREGEN_BLOCKS");
-        // lane groups of a refill launch at most: 16 384 = two generator waves per SIMD of the part, the other half of every SIMD stays with the step
-        // kernels (profiles/r05/pregen_residency_cap_ab.jsonl, ms per step at 32 768 / 16 384 / 8 192 / 4 096 groups: GoTo 131 072 envs 0.0438 / 0.0390 /
-        // 0.0395 / 0.0478; BossLevel encoded 1 048 576 0.110 / 0.104 / 0.104; BossLevel pixels 131 072: no difference).  bbai_seed's first fill
-        // (nothing else runs) takes the whole part: 32 768.
-        e->pregen_cap = ev ? std::max(64, atoi(ev)) : 16384;
-        const char* mv = getenv("BBAI_PREGEN_MIN");
-        e->pregen_min = mv ? std::max(0, atoi(mv)) : 6144;
-        const char* pp = getenv("BBAI_PREGEN_PER_GROUP");
-        e->pregen_per_group = pp ? std::max(1, atoi(pp)) : 12;
-        const char* pg = getenv("BBAI_PREGEN_GROUP");
-        e->pregen_group = pg ? atoi(pg) : 32;
-        const char* sp = getenv("BBAI_STEP_PRIO");
-        e->step_prio = sp ? atoi(sp) : 1;        // (never slower, GoTo 131 072 envs -2 %: profiles/r03/step_prio_ab.jsonl)
-        const char* rv = getenv("BBAI_RENDER_GROUP");
-        e->render_group = rv ? atoi(rv) : 0;
-        const char* qv = getenv("BBAI_RENDER_QUEUE");
-        e->render_queue = qv ? atoi(qv) : -1;
-        const char* pv2 = getenv("BBAI_RENDER_PACE");
-        e->render_pace = pv2 ? std::max(0, atoi(pv2)) : 0;
-        const char* ss = getenv("BBAI_STEP_RENDER_SPLIT");
-        e->step_render_split = ss ? atoi(ss) : -1;
-        const char* rm = getenv("BBAI_ROLLOUT_MULTI");
-        e->rollout_multi = rm ? atoi(rm) : 1;
-        const char* gs = getenv("BBAI_GATE_STRICT");
-        e->gate_strict = gs ? atoi(gs) != 0 : 0;
-        const char* gp = getenv("BBAI_GATE_PROBE");
-        e->gate_probe = gp ? atoi(gp) : 1;
-        const char* cf = getenv("BBAI_CONSUME_FUSED");
-        e->consume_fused = cf ? atoi(cf) : -1;
-        const char* tv = getenv("BBAI_RENDER_TPB");
-        e->render_tpb = tv ? atoi(tv) : 0;
-        const char* dv = getenv("BBAI_RENDER_DELTA");
-        e->render_delta = dv ? atoi(dv) != 0 : 1;
-        e->render_delta_from_step = -1;
-        e->render_piece_bytes = RENDER_PIECE_DEFAULT;
+        for (const Knob& k : KNOBS) if (!k.read_only) {
+            const char* kv = k.var ? getenv(k.var) : nullptr;
+            e->*k.field = kv ? knob_value(k, atoi(kv)) : k.def;
+        }
+        if (!e->mtt) e->lane_blocks = 0;        // (no lane generator on this handle)
     }
     return BBAI_OK;
 }
@@ -2450,7 +2451,7 @@ static int window_begin(bbai_env* e, hipStream_t s) {
         bool strict = e->gate_strict != 0;
         if (!strict) {
             bool ok = true;
-            { int rc = probe_stream(e, s, &ok); if (rc != BBAI_OK) return rc; }
+            BBAI_TRY(probe_stream(e, s, &ok));
             e->gate_forced = ok ? 0 : 1;
             strict = !ok;
         }
@@ -2505,7 +2506,7 @@ static int window_end(bbai_env* e, hipStream_t s, int tokens_mode /* k_tokens: 0
 }
 // main stream: slots -> live state (+ first obs) by k_consume; side stream: refill the consumed slots.
 static int consume_and_refill(bbai_env* e, hipStream_t s, uint8_t* image, uint8_t* dirs, int all) {
-    { int rc = window_begin(e, s); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(window_begin(e, s));
     const TickPos tp = tick_pos(e);
     const int wb = tp.wb;
     const int64_t hint = all ? e->n : std::max<int64_t>(e->n / 64, 64);
@@ -2564,9 +2565,8 @@ int bbai_reset(bbai_env* e, uint8_t* image, uint8_t* dirs, void* stream) {
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
-    int rc = consume_and_refill(e, s, image, dirs, 1);
-    if (rc != BBAI_OK) return rc;
+    BBAI_TRY(call.rc);
+    BBAI_TRY(consume_and_refill(e, s, image, dirs, 1));
     e->live = true;
     return call.leave();
 }
@@ -2587,6 +2587,8 @@ static bool use_fused_consume(const bbai_env* e) {
 //   step_prepare  the window gate (fused: the slots this step's waves consume must be there) + what the kernel needs to know about the window
 //   step_kernel   k_step over the 64-env blocks [block0, block0 + nblocks) on stream `ks`
 //   step_finish   k_consume (unfused) / mission tokens / the window's close + refill -- on the caller's stream, behind EVERY k_step of the step
+// what the caller of one step hands over (device pointers); bbai_rollout moves `actions` on from tick to tick
+struct StepIO { const uint8_t* actions; uint8_t* image; uint8_t* dirs; float* rewards; double* rewards64; uint8_t* dones; int auto_reset, enum_done; };
 struct StepPlan { FuseArgs fa; bool fused; uint32_t* counter; TapArgs tap = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
                   bool dirty = false;      // k_step finds the dirty cells of the registered target for its render (step_render_launch, step_dirty)
 };
@@ -2596,7 +2598,7 @@ static int step_prepare(bbai_env* e, int auto_reset, hipStream_t s, StepPlan& p)
     memset(&p.fa, 0, sizeof(p.fa));
     FuseArgs& fa = p.fa;
     if (p.fused) {
-        { int rc = window_begin(e, s); if (rc != BBAI_OK) return rc; }        // the slots this step's waves consume have landed
+        BBAI_TRY(window_begin(e, s));        // the slots this step's waves consume have landed
         const TickPos tp = tick_pos(e);
         fa.next_recs = e->next_rec; fa.next_hots = e->next_hot; fa.next_obs = e->next_obs; fa.depth = e->depth;
         fa.pending = e->pending + (size_t)tp.wb * e->n; fa.first_slot = e->first_slot + (size_t)tp.wb * e->n;
@@ -2613,14 +2615,13 @@ static int step_prepare(bbai_env* e, int auto_reset, hipStream_t s, StepPlan& p)
     }
     return BBAI_OK;
 }
-static int step_kernel(bbai_env* e, const StepPlan& p, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
-                       uint8_t* dones, int auto_reset, hipStream_t ks, int enum_done, int64_t block0, int64_t nblocks, int ticks = 1) {
+static int step_kernel(bbai_env* e, const StepPlan& p, const StepIO& io, hipStream_t ks, int64_t block0, int64_t nblocks, int ticks = 1) {
     ProfScope prof_(e, 0, ks);
     if (e->prof_on) e->prof_step_ticks += ticks;
     StepArgs a;
-    a.c = e->cfg; a.n = e->n; a.recs = e->rec; a.hots = e->hot; a.stales = e->stale; a.vheads = e->vhead; a.vsets = e->vset; a.actions = actions; a.image = image; a.dirs = dirs;
-    a.rewards = rewards; a.rewards64 = rewards64; a.dones = dones; a.auto_reset = auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
-    a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = enum_done; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
+    a.c = e->cfg; a.n = e->n; a.recs = e->rec; a.hots = e->hot; a.stales = e->stale; a.vheads = e->vhead; a.vsets = e->vset; a.actions = io.actions; a.image = io.image; a.dirs = io.dirs;
+    a.rewards = io.rewards; a.rewards64 = io.rewards64; a.dones = io.dones; a.auto_reset = io.auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
+    a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = io.enum_done; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
     a.tap = p.tap; a.ticks = ticks;
     a.dshadow = p.dirty && ticks == 1 ? e->rt_shadow : nullptr; a.dmask = e->rt_dmask; a.lut = e->lut;
 #define STEP_LAUNCH(VV, FF, CC) do { if (ticks > 1) hipLaunchKernelGGL((k_step_ticks<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); \
@@ -2633,26 +2634,37 @@ static int step_kernel(bbai_env* e, const StepPlan& p, const uint8_t* actions, u
     HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }
-static int step_finish(bbai_env* e, const StepPlan& p, uint8_t* image, uint8_t* dirs, const uint8_t* dones, int auto_reset, hipStream_t s) {
+static int step_finish(bbai_env* e, const StepPlan& p, const StepIO& io, hipStream_t s) {
     // the number of finished envs is only known on the device: fixed grids, device-side count
-    if (auto_reset) return p.fused ? window_end(e, s, 2, dones) : consume_and_refill(e, s, image, dirs, 0);
+    if (io.auto_reset) return p.fused ? window_end(e, s, 2, io.dones) : consume_and_refill(e, s, io.image, io.dirs, 0);
     return BBAI_OK;
 }
 static int64_t step_blocks(const bbai_env* e) { return (e->n + STEP_BLOCK - 1) / STEP_BLOCK; }
 struct TapRows { uint8_t* image_out; uint8_t* dir_out; double* rew_out; uint8_t* done_out; };
-static int step_launch(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
-                       uint8_t* dones, int auto_reset, hipStream_t s, int enum_done, const TapRows* rows = nullptr) {
+static TapArgs tap_args(const bbai_env* e, const TapRows& r) {       // the rows of bbai_step_tap_set's envs, written by the stepping lanes
+    return TapArgs{e->tap_mask, e->tap_rank0, e->tap_perm, r.image_out, r.dir_out, r.rew_out, r.done_out, e->tap_count};
+}
+// What every stepping entry point asks of the handle first (`what`: "step", or "rollout" in bbai_rollout's messages).
+static int step_ready(const bbai_env* e, int auto_reset, const char* what) {
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "%s before reset", what); return BBAI_ERR_STATE; }
+    if (auto_reset && !e->seeded) {     // live through import_state only: there is no level stream to reset from
+        snprintf(g_err, sizeof(g_err), "auto-reset %s before seed", what);
+        return BBAI_ERR_STATE;
+    }
+    return BBAI_OK;
+}
+static int step_launch(bbai_env* e, const StepIO& io, hipStream_t s, const TapRows* rows = nullptr) {
     StepPlan p;
-    { int rc = step_prepare(e, auto_reset, s, p); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(step_prepare(e, io.auto_reset, s, p));
     // Inside the stepping waves wherever the step leaves the final outputs behind (fused consume, in-place layout, no auto-reset);
     // an unfused auto-resetting step writes the new episodes' first observations in k_consume: the tap is then a launch behind it.
-    const bool in_kernel = rows && (p.fused || e->inplace || !auto_reset);
-    if (in_kernel) p.tap = TapArgs{e->tap_mask, e->tap_rank0, e->tap_perm, rows->image_out, rows->dir_out, rows->rew_out, rows->done_out, e->tap_count};
-    { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, enum_done, 0, step_blocks(e)); if (rc != BBAI_OK) return rc; }
-    { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
+    const bool in_kernel = rows && (p.fused || e->inplace || !io.auto_reset);
+    if (in_kernel) p.tap = tap_args(e, *rows);
+    BBAI_TRY(step_kernel(e, p, io, s, 0, step_blocks(e)));
+    BBAI_TRY(step_finish(e, p, io, s));
     if (rows && !in_kernel) {
-        hipLaunchKernelGGL(k_tap, dim3((unsigned)std::min<int64_t>((e->tap_count * OBS_BYTES + 255) / 256, 2048)), dim3(256), 0, s, e->tap_count, (int64_t)0, e->tap_ids, image, dirs,
-                           rewards64, dones, (const uint8_t*)nullptr, rows->image_out, rows->dir_out, rows->rew_out, rows->done_out, (uint8_t*)nullptr);
+        hipLaunchKernelGGL(k_tap, dim3((unsigned)std::min<int64_t>((e->tap_count * OBS_BYTES + 255) / 256, 2048)), dim3(256), 0, s, e->tap_count, (int64_t)0, e->tap_ids, io.image, io.dirs,
+                           io.rewards64, io.dones, (const uint8_t*)nullptr, rows->image_out, rows->dir_out, rows->rew_out, rows->done_out, (uint8_t*)nullptr);
         HIP_TRY(hipGetLastError());
     }
     return BBAI_OK;
@@ -2661,16 +2673,12 @@ static int step_launch(bbai_env* e, const uint8_t* actions, uint8_t* image, uint
 int bbai_step(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
               uint8_t* dones, int auto_reset, void* stream) {
     if (!e || !actions || !image || !dirs || !rewards || !dones) ARG_FAIL("null handle or buffer");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "step before reset"); return BBAI_ERR_STATE; }
-    if (auto_reset && !e->seeded) {     // live through import_state only: there is no level stream to reset from
-        snprintf(g_err, sizeof(g_err), "auto-reset step before seed");
-        return BBAI_ERR_STATE;
-    }
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
-    { int rc = step_launch(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(call.rc);
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s));
     return call.leave();
 }
 
@@ -2713,14 +2721,13 @@ int bbai_step_tapped(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_
                      int auto_reset, uint8_t* image_out, uint8_t* dir_out, double* reward64_out, uint8_t* done_out, void* stream) {
     if (!e || !actions || !image || !dirs || !rewards || !rewards64 || !dones || !image_out || !dir_out || !reward64_out || !done_out) ARG_FAIL("null handle or buffer");
     if (!e->tap_count) { snprintf(g_err, sizeof(g_err), "bbai_step_tapped before bbai_step_tap_set"); return BBAI_ERR_STATE; }
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "step before reset"); return BBAI_ERR_STATE; }
-    if (auto_reset && !e->seeded) { snprintf(g_err, sizeof(g_err), "auto-reset step before seed"); return BBAI_ERR_STATE; }
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
+    BBAI_TRY(call.rc);
     const TapRows rows = {image_out, dir_out, reward64_out, done_out};
-    { int rc = step_launch(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum, &rows); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s, &rows));
     return call.leave();
 }
 
@@ -2756,7 +2763,7 @@ int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
+    BBAI_TRY(call.rc);
     HIP_TRY(hipMemcpyAsync(out, e->rt_shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
     return call.leave();
 }
@@ -2904,7 +2911,7 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
                          int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */,
                          bool from_step = false /* the step in front found the dirty cells (step_dirty): store them (k_render_dstore) */) {
     CallScope call(e, (hipStream_t)stream);
-    if (call.rc != BBAI_OK) return call.rc;
+    BBAI_TRY(call.rc);
     const RenderRange r = {input, pixels, n_render < 0 ? e->n : n_render, env_off, (hipStream_t)stream};
     {
     ProfScope prof_(e, 2, r.stream);
@@ -2994,7 +3001,7 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
+    BBAI_TRY(call.rc);
     if (k == 0) render_grid_launch<8>(e, highlight, ids, count, out, s);
     else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
     else render_grid_launch<32>(e, highlight, ids, count, out, s);
@@ -3041,8 +3048,8 @@ int bbai_observe_full(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* o
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
-    { int rc = full_launch(e, ids, count, out, s); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(call.rc);
+    BBAI_TRY(full_launch(e, ids, count, out, s));
     return call.leave();
 }
 
@@ -3050,14 +3057,13 @@ int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
                    uint8_t* dones, int auto_reset, uint8_t* full, void* stream) {
     if (!e || !actions || !image || !dirs || !rewards || !dones || !full) ARG_FAIL("null handle or buffer");
     if ((uintptr_t)full & 15) ARG_FAIL("full observation buffer not 16-byte aligned");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "step before reset"); return BBAI_ERR_STATE; }
-    if (auto_reset && !e->seeded) { snprintf(g_err, sizeof(g_err), "auto-reset step before seed"); return BBAI_ERR_STATE; }
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
-    { int rc = step_launch(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum); if (rc != BBAI_OK) return rc; }
-    { int rc = full_launch(e, nullptr, e->n, full, s); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(call.rc);
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s));
+    BBAI_TRY(full_launch(e, nullptr, e->n, full, s));
     return call.leave();
 }
 
@@ -3085,51 +3091,49 @@ constexpr int64_t STEP_RENDER_SPLIT_MIN = 262144;
 // memory-side cache, k_render_delta's input stage is nearly free and the render does not gain (82 / 153 / 288 us either way) while k_step
 // pays 11-22 us.
 constexpr int64_t RENDER_FROM_STEP_MIN_ENVS = 786432;
-static int step_render_launch_(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
-                               int auto_reset, uint8_t* pixels, hipStream_t s, int enum_done, bool& dirty) {
+static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, hipStream_t s, bool& dirty) {
     StepPlan p;
     {
         CallScope call(e, s);
-        if (call.rc != BBAI_OK) return call.rc;
-        { int rc = step_prepare(e, auto_reset, s, p); if (rc != BBAI_OK) return rc; }
+        BBAI_TRY(call.rc);
+        BBAI_TRY(step_prepare(e, io.auto_reset, s, p));
         // The render is a delta render of the registered target with a valid shadow, and k_step's LDS rows are the step's final observations
         // (fused / in-place consume, or no auto-reset; an unfused k_consume rewrites the finished envs' rows later): k_step finds the dirty
         // cells and updates the shadow (step_dirty), the render only stores (k_render_dstore).  From the step kernel on, the shadow is ahead
         // of the frame until the render has been launched: a failure in between invalidates it (step_render_launch).
         const bool from_step = e->render_delta_from_step < 0 ? e->n >= RENDER_FROM_STEP_MIN_ENVS : e->render_delta_from_step != 0;
-        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !auto_reset) && delta_target(e, pixels, 0, e->n) && e->rt_valid;
+        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !io.auto_reset) && delta_target(e, pixels, 0, e->n) && e->rt_valid;
         const int want = e->step_render_split < 0 ? (STEP_RENDER_SPLIT_DEFAULT && e->n >= STEP_RENDER_SPLIT_MIN) : e->step_render_split;      // (an explicit 1: any size)
         const int64_t nb = step_blocks(e), hb = nb / 2;
-        const bool split = want && pixels && (p.fused || !auto_reset) && hb > 0;
+        const bool split = want && pixels && (p.fused || !io.auto_reset) && hb > 0;
         if (!split) {
-            { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, enum_done, 0, nb); if (rc != BBAI_OK) return rc; }
-            { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
-            { int rc = call.leave(); if (rc != BBAI_OK) return rc; }
-            return pixels ? render_launch(e, image, pixels, s, -1, 0, p.dirty) : BBAI_OK;
+            BBAI_TRY(step_kernel(e, p, io, s, 0, nb));
+            BBAI_TRY(step_finish(e, p, io, s));
+            BBAI_TRY(call.leave());
+            return pixels ? render_launch(e, io.image, pixels, s, -1, 0, p.dirty) : BBAI_OK;
         }
         const int64_t na = hb * STEP_BLOCK;                   // envs of the first half (a multiple of every render group size)
         // the second half's k_step, on the split stream, behind everything the caller's stream holds so far (the gate included)
         HIP_TRY(hipEventRecord(e->ev_split0, s));
         HIP_TRY(hipStreamWaitEvent(e->split, e->ev_split0, 0));
-        { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, e->split, enum_done, hb, nb - hb); if (rc != BBAI_OK) return rc; }
+        BBAI_TRY(step_kernel(e, p, io, e->split, hb, nb - hb));
         HIP_TRY(hipEventRecord(e->ev_splitB, e->split));
-        { int rc = step_kernel(e, p, actions, image, dirs, rewards, rewards64, dones, auto_reset, s, enum_done, 0, hb); if (rc != BBAI_OK) return rc; }
-        { int rc = call.leave(); if (rc != BBAI_OK) return rc; }
-        { int rc = render_launch(e, image, pixels, s, na, 0, p.dirty); if (rc != BBAI_OK) return rc; }
+        BBAI_TRY(step_kernel(e, p, io, s, 0, hb));
+        BBAI_TRY(call.leave());
+        BBAI_TRY(render_launch(e, io.image, pixels, s, na, 0, p.dirty));
         HIP_TRY(hipStreamWaitEvent(s, e->ev_splitB, 0));
         {
             CallScope call2(e, s);
-            if (call2.rc != BBAI_OK) return call2.rc;
-            { int rc = step_finish(e, p, image, dirs, dones, auto_reset, s); if (rc != BBAI_OK) return rc; }
-            { int rc = call2.leave(); if (rc != BBAI_OK) return rc; }
+            BBAI_TRY(call2.rc);
+            BBAI_TRY(step_finish(e, p, io, s));
+            BBAI_TRY(call2.leave());
         }
-        return render_launch(e, image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na, na, p.dirty);
+        return render_launch(e, io.image + na * OBS_BYTES, pixels + na * (int64_t)PIX_BYTES, s, e->n - na, na, p.dirty);
     }
 }
-static int step_render_launch(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
-                              int auto_reset, uint8_t* pixels, hipStream_t s, int enum_done) {
+static int step_render_launch(bbai_env* e, const StepIO& io, uint8_t* pixels, hipStream_t s) {
     bool dirty = false;
-    const int rc = step_render_launch_(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, pixels, s, enum_done, dirty);
+    const int rc = step_render_launch_(e, io, pixels, s, dirty);
     if (rc != BBAI_OK && dirty) { e->rt_valid = false; e->rt_filled = 0; }
     return rc;
 }
@@ -3139,11 +3143,10 @@ extern "C" {
 int bbai_step_render(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
                      uint8_t* dones, int auto_reset, uint8_t* pixels, void* stream) {
     if (!e || !actions || !image || !dirs || !rewards || !dones || !pixels) ARG_FAIL("null handle or buffer");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "step before reset"); return BBAI_ERR_STATE; }
-    if (auto_reset && !e->seeded) { snprintf(g_err, sizeof(g_err), "auto-reset step before seed"); return BBAI_ERR_STATE; }
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
     if (e->n_tiles <= 0) { snprintf(g_err, sizeof(g_err), "render before set_atlas"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
-    return step_render_launch(e, actions, image, dirs, rewards, rewards64, dones, auto_reset, pixels, (hipStream_t)stream, e->done_action_enum);
+    return step_render_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, pixels, (hipStream_t)stream);
 }
 
 // Register (or clear with NULL) a caller-owned uint8[n][72] device buffer that the engine keeps filled with the
@@ -3176,7 +3179,7 @@ int bbai_export_state(bbai_env* e, int64_t first, int64_t count, uint8_t* rec, u
     if (!e || first < 0 || count < 0 || first + count > e->n) ARG_FAIL("null handle or env range out of bounds");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
-    if (rec && count > 0) { int rc = live_copy(e, first, count, 0); if (rc != BBAI_OK) return rc; }
+    if (rec && count > 0) BBAI_TRY(live_copy(e, first, count, 0));
     if (rec) HIP_TRY(hipMemcpy(rec, e->rec + first * e->cfg.rec_bytes, (size_t)count * e->cfg.rec_bytes, hipMemcpyDeviceToHost));
     if (hot) HIP_TRY(hipMemcpy(hot, e->hot + first, (size_t)count * sizeof(Hot), hipMemcpyDeviceToHost));
     if (stale) HIP_TRY(hipMemcpy(stale, e->stale + first, (size_t)count * 8, hipMemcpyDeviceToHost));
@@ -3216,7 +3219,7 @@ int bbai_import_state(bbai_env* e, int64_t first, int64_t count, const uint8_t* 
         HIP_TRY(r);
     }
     if (stale) HIP_TRY(hipMemcpy(e->stale + first, stale, (size_t)count * 8, hipMemcpyHostToDevice));
-    if (rec && count > 0) { int rc = live_copy(e, first, count, 1); if (rc != BBAI_OK) return rc; }
+    if (rec && count > 0) BBAI_TRY(live_copy(e, first, count, 1));
     if (e->lsm && count > 0) HIP_TRY(hipMemset(e->lsm + first, 0, (size_t)count));     // (not part of the exported state: lastStepMatch = False)
     if (rec && count > 0) {
         hipLaunchKernelGGL(k_sync_prog, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, e->cfg, e->n, first, count, e->rec,
@@ -3225,8 +3228,8 @@ int bbai_import_state(bbai_env* e, int64_t first, int64_t count, const uint8_t* 
         HIP_TRY(hipDeviceSynchronize());
     }
     // (a hot / stale-only import: the C plane rows are rebuilt from the staging records, which must then hold the LIVE ones)
-    if (!rec && e->cplane && count > 0) { int rc = live_copy(e, first, count, 0); if (rc != BBAI_OK) return rc; }
-    if (count > 0) { int rc = sync_view(e, first, count); if (rc != BBAI_OK) return rc; }
+    if (!rec && e->cplane && count > 0) BBAI_TRY(live_copy(e, first, count, 0));
+    if (count > 0) BBAI_TRY(sync_view(e, first, count));
     e->live = true;
     return BBAI_OK;
 }
@@ -3286,9 +3289,9 @@ int bbai_checkpoint_save(bbai_env* e, void* host_buf, int64_t bytes) {
     if (!e || !host_buf || bytes != bbai_checkpoint_bytes(e)) ARG_FAIL("null pointer or buffer size != bbai_checkpoint_bytes()");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());             // both streams idle: the ring and the windows' bookkeeping are at rest, every refill has landed
-    { int rc = live_copy(e, 0, e->n, 0); if (rc != BBAI_OK) return rc; }       // (in-place layout: the blob's record segment = the live slots)
-    { int rc = mt_canon(e); if (rc != BBAI_OK) return rc; }                    // (the blob holds the canonical MT19937 form: every position in [0, 624])
-    { int rc = mt_sync(e); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(live_copy(e, 0, e->n, 0));       // (in-place layout: the blob's record segment = the live slots)
+    BBAI_TRY(mt_canon(e));                    // (the blob holds the canonical MT19937 form: every position in [0, 624])
+    BBAI_TRY(mt_sync(e));
     CkptHeader h;
     memset(&h, 0, sizeof(h));
     h.magic = 0x42424149434b5054ull; h.version = CKPT_VERSION; h.period = e->period; h.n = e->n; h.cfg = e->cfg; h.depth = e->depth;
@@ -3330,8 +3333,7 @@ int bbai_checkpoint_load(bbai_env* e, const void* host_buf, int64_t bytes) {
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
     if (h.bot_stack && !e->bot_state) {          // (allocates only; on failure the handle is unchanged)
-        int rc = bot_alloc(e, h.bot_stack);
-        if (rc != BBAI_OK) return rc;
+        BBAI_TRY(bot_alloc(e, h.bot_stack));
     }
     if (h.period != e->period) {
         // The handle chose its look-ahead period from the memory that was free when it was created (bbai_create); the blob's
@@ -3373,7 +3375,7 @@ int bbai_checkpoint_load(bbai_env* e, const void* host_buf, int64_t bytes) {
     // (the saved run was idle: every refill it had launched has landed, and flow[FLOW_REFILLED] in the blob says so)
     for (int i = 0; i < NWIN; ++i) HIP_TRY(hipEventRecord(e->ev_refill[i], e->side));
     HIP_TRY(hipDeviceSynchronize());
-    { int rc = mt_sync(e); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(mt_sync(e));
     return sync_view(e, 0, e->n);
 }
 
@@ -3381,7 +3383,7 @@ int bbai_get_programs(bbai_env* e, int64_t first, int64_t count, uint8_t* prog) 
     if (!e || !prog || first < 0 || count < 0 || first + count > e->n) ARG_FAIL("null pointer or env range out of bounds");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
-    { int rc = live_copy(e, first, count, 0); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(live_copy(e, first, count, 0));
     HIP_TRY(hipMemcpy2D(prog, sizeof(Prog), e->rec + first * e->cfg.rec_bytes + e->cfg.off_prog, (size_t)e->cfg.rec_bytes,
                         sizeof(Prog), (size_t)count, hipMemcpyDeviceToHost));
     return BBAI_OK;
@@ -3416,8 +3418,7 @@ static int bot_launch(bbai_env* e, const uint8_t* prev_actions, uint8_t* actions
         // rare bot that loops without progress grows its stack until max_steps and fails the episode -- here it gives up
         // when the stack is full, counted in bbai_bot_stats().capacity).  Raise it to follow such a bot further.
         const char* ev = getenv("BBAI_BOT_STACK");
-        int rc = bot_alloc(e, ev ? std::max(8, std::min(atoi(ev), 4096)) : BOT_STACK);
-        if (rc != BBAI_OK) return rc;
+        BBAI_TRY(bot_alloc(e, ev ? std::max(8, std::min(atoi(ev), 4096)) : BOT_STACK));
     }
     // Occupancy target, measured (profiles/r01/bot_bench.jsonl): the fully inlined expert wants ~400
     // registers; capping it at 256 (2 waves/SIMD, spills to scratch) is +35 % on maze levels (BossLevel 1M envs 22.8 ->
@@ -3459,8 +3460,8 @@ int bbai_bot_act(bbai_env* e, const uint8_t* prev_actions, uint8_t* actions, voi
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
-    { int rc = bot_launch(e, prev_actions, actions, BOT_DEAD, nullptr, s); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(call.rc);
+    BBAI_TRY(bot_launch(e, prev_actions, actions, BOT_DEAD, nullptr, s));
     return call.leave();
 }
 
@@ -3474,18 +3475,16 @@ int bbai_bot_rollout(bbai_env* e, int T, uint8_t* image, uint8_t* dirs, uint8_t*
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
-    if (call.rc != BBAI_OK) return call.rc;
+    BBAI_TRY(call.rc);
     const size_t n = (size_t)e->n;
     for (int t = 0; t < T; ++t) {
         // what the expert decides on: the observation (and mission) BEFORE the step
         HIP_TRY(hipMemcpyAsync(images_out + (size_t)t * n * OBS_BYTES, image, n * OBS_BYTES, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(dirs_out + (size_t)t * n, dirs, n, hipMemcpyDeviceToDevice, s));
         if (tokens_out) HIP_TRY(hipMemcpyAsync(tokens_out + (size_t)t * n * TOK_MAX, e->tokens, n * TOK_MAX, hipMemcpyDeviceToDevice, s));
-        int rc = bot_launch(e, nullptr, actions_out + (size_t)t * n, A_RESET_ENV, gave_up_out + (size_t)t * n, s);
-        if (rc != BBAI_OK) return rc;
-        rc = step_launch(e, actions_out + (size_t)t * n, image, dirs, rewards_out + (size_t)t * n, nullptr, dones_out + (size_t)t * n, 1, s,
-                         1 /* the expert's `done` is the enum member (bot.py:593) */);
-        if (rc != BBAI_OK) return rc;
+        BBAI_TRY(bot_launch(e, nullptr, actions_out + (size_t)t * n, A_RESET_ENV, gave_up_out + (size_t)t * n, s));
+        BBAI_TRY(step_launch(e, StepIO{actions_out + (size_t)t * n, image, dirs, rewards_out + (size_t)t * n, nullptr, dones_out + (size_t)t * n, 1,
+                                       1 /* the expert's `done` is the enum member (bot.py:593) */}, s));
     }
     return call.leave();
 }
@@ -3544,8 +3543,7 @@ int bbai_tap_ids(int64_t count, int64_t pix_count, const int64_t* ids_dev, const
 int bbai_rollout(bbai_env* e, int T, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones,
                  int auto_reset, uint8_t* pixels, const bbai_tap_log* tap, void* stream) {
     if (!e || T < 1 || !actions || !image || !dirs || !rewards || !dones) ARG_FAIL("null handle or buffer, or T < 1");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "rollout before reset"); return BBAI_ERR_STATE; }
-    if (auto_reset && !e->seeded) { snprintf(g_err, sizeof(g_err), "auto-reset rollout before seed"); return BBAI_ERR_STATE; }
+    BBAI_TRY(step_ready(e, auto_reset, "rollout"));
     if (pixels && e->n_tiles <= 0) { snprintf(g_err, sizeof(g_err), "rollout with pixels before set_atlas"); return BBAI_ERR_STATE; }
     if (tap && (!rewards64 || tap->count <= 0 || tap->pix_count < 0 || tap->pix_count > tap->count || !tap->image_out || !tap->dir_out ||
                 !tap->reward64_out || !tap->done_out || (tap->pix_count && (!pixels || !tap->pixels_out))))
@@ -3554,6 +3552,11 @@ int bbai_rollout(bbai_env* e, int T, const uint8_t* actions, uint8_t* image, uin
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)e->n;
     const bool own_tap = tap && !tap->ids_dev;          // the envs of bbai_step_tap_set, logged by the stepping lanes
+    StepIO io = {actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum};
+    auto tap_rows = [&](int t) {                        // the tap log's rows of tick t
+        const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
+        return TapRows{tap->image_out + orow * c * OBS_BYTES, tap->dir_out + orow * c, tap->reward64_out + row * c, tap->done_out + row * c};
+    };
     if (own_tap && (tap->count != e->tap_count || tap->pix_count != 0)) {
         snprintf(g_err, sizeof(g_err), "rollout: a tap log without ids_dev follows bbai_step_tap_set's list (%lld envs, no pixel rows)", (long long)e->tap_count);
         return BBAI_ERR_ARG;
@@ -3565,42 +3568,34 @@ int bbai_rollout(bbai_env* e, int T, const uint8_t* actions, uint8_t* image, uin
     const bool fused = auto_reset && (e->inplace || use_fused_consume(e));
     if (!pixels && (fused || !auto_reset) && !e->tokens && (!tap || own_tap) && (e->rollout_multi || own_tap)) {
         CallScope call(e, s);
-        if (call.rc != BBAI_OK) return call.rc;
+        BBAI_TRY(call.rc);
         for (int t = 0; t < T;) {
             StepPlan p;
-            { int rc = step_prepare(e, auto_reset, s, p); if (rc != BBAI_OK) return rc; }
+            BBAI_TRY(step_prepare(e, auto_reset, s, p));
             int ticks = e->rollout_multi ? T - t : 1;
             if (fused) ticks = std::min(ticks, e->period - tick_pos(e).pos);
-            if (own_tap) {
-                const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
-                p.tap = TapArgs{e->tap_mask, e->tap_rank0, e->tap_perm, tap->image_out + orow * c * OBS_BYTES, tap->dir_out + orow * c,
-                                tap->reward64_out + row * c, tap->done_out + row * c, tap->count};
-            }
-            { int rc = step_kernel(e, p, actions + (size_t)t * n, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum, 0, step_blocks(e), ticks); if (rc != BBAI_OK) return rc; }
-            if (fused) { int rc = window_end(e, s, 2, dones, ticks); if (rc != BBAI_OK) return rc; }
+            if (own_tap) p.tap = tap_args(e, tap_rows(t));         // (tap->count == e->tap_count: checked above)
+            io.actions = actions + (size_t)t * n;
+            BBAI_TRY(step_kernel(e, p, io, s, 0, step_blocks(e), ticks));
+            if (fused) BBAI_TRY(window_end(e, s, 2, dones, ticks));
             t += ticks;
         }
         return call.leave();
     }
     if (own_tap && pixels) { snprintf(g_err, sizeof(g_err), "rollout: a tap log without ids_dev has no pixel rows (encoded observations only)"); return BBAI_ERR_ARG; }
     for (int t = 0; t < T; ++t) {
+        io.actions = actions + (size_t)t * n;
+        const TapRows rows = tap ? tap_rows(t) : TapRows{};
         if (own_tap) {          // (unfused auto-reset / a token buffer: one bbai_step_tapped per step)
             CallScope call(e, s);
-            if (call.rc != BBAI_OK) return call.rc;
-            const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
-            const TapRows rows = {tap->image_out + orow * c * OBS_BYTES, tap->dir_out + orow * c, tap->reward64_out + row * c, tap->done_out + row * c};
-            { int rc = step_launch(e, actions + (size_t)t * n, image, dirs, rewards, rewards64, dones, auto_reset, s, e->done_action_enum, &rows); if (rc != BBAI_OK) return rc; }
-            { int rc = call.leave(); if (rc != BBAI_OK) return rc; }
+            BBAI_TRY(call.rc);
+            BBAI_TRY(step_launch(e, io, s, &rows));
+            BBAI_TRY(call.leave());
             continue;
         }
-        { int rc = step_render_launch(e, actions + (size_t)t * n, image, dirs, rewards, rewards64, dones, auto_reset, pixels, s, e->done_action_enum); if (rc != BBAI_OK) return rc; }
-        if (tap) {
-            const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
-            int rc = tap_launch(tap->count, tap->pix_count, tap->ids_dev, image, dirs, rewards64, dones, pixels, tap->image_out + orow * c * OBS_BYTES,
-                                tap->dir_out + orow * c, tap->reward64_out + row * c, tap->done_out + row * c,
-                                tap->pix_count ? tap->pixels_out + orow * (size_t)tap->pix_count * PIX_BYTES : nullptr, stream);
-            if (rc != BBAI_OK) return rc;
-        }
+        BBAI_TRY(step_render_launch(e, io, pixels, s));
+        if (tap) BBAI_TRY(tap_launch(tap->count, tap->pix_count, tap->ids_dev, image, dirs, rewards64, dones, pixels, rows.image_out, rows.dir_out, rows.rew_out, rows.done_out,
+                                     tap->pix_count ? tap->pixels_out + (size_t)(tap->obs_row0 + t) * (size_t)tap->pix_count * PIX_BYTES : nullptr, stream));
     }
     return BBAI_OK;
 }
@@ -3693,55 +3688,32 @@ int bbai_set_done_actions(bbai_env* e, int enable) {
 }
 int bbai_get_done_actions(bbai_env* e) { return e && e->lsm ? 1 : 0; }
 
-// Performance knobs by name (never semantics: every setting produces the same bytes).  What the BBAI_* environment variables
-// set at bbai_create, switchable on a live handle so that measurements can alternate settings inside ONE process on ONE box
-// (tools/ab.py).  Synchronises the device first.
+// Performance knobs by name (KNOBS, plus the three that do work): what the BBAI_* environment variables set at bbai_create, switchable on a
+// live handle so that measurements can alternate settings inside ONE process on ONE box (tools/ab.py).  Synchronises the device first.
 int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     if (!e || !name) ARG_FAIL("null handle or name");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
     const int v = (int)value;
-    if (!strcmp(name, "render_queue")) e->render_queue = v;
-    else if (!strcmp(name, "render_queue_bpc")) e->render_queue_bpc = v;
-    else if (!strcmp(name, "render_queue_blocks")) e->render_queue_blocks = v;
-    else if (!strcmp(name, "render_pace")) e->render_pace = v < 0 ? 0 : v;
-    else if (!strcmp(name, "render_group")) e->render_group = v;
-    else if (!strcmp(name, "render_tpb")) e->render_tpb = v;
-    else if (!strcmp(name, "render_delta")) { e->render_delta = v != 0; e->rt_valid = false; e->rt_filled = 0; }
-    else if (!strcmp(name, "render_delta_sched")) e->render_delta_sched = v;
-    else if (!strcmp(name, "render_delta_tpb")) e->render_delta_tpb = v;
-    else if (!strcmp(name, "render_delta_bpc")) e->render_delta_bpc = std::max(0, v);
-    else if (!strcmp(name, "render_delta_from_step")) e->render_delta_from_step = v < 0 ? -1 : v != 0;
-    else if (!strcmp(name, "render_piece_bytes")) {
-        if (v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
-        e->render_piece_bytes = v;
-    }
-    else if (!strcmp(name, "grid_render_bpc")) e->grid_bpc = std::max(0, v);
-    else if (!strcmp(name, "step_prio")) e->step_prio = v;
-    else if (!strcmp(name, "pregen_group")) e->pregen_group = v;
-    else if (!strcmp(name, "pregen_lane")) {
+    const Knob* k = find_knob(name);
+    if (!strcmp(name, "pregen_lane")) {
         if (!e->mtt) { if (v) ARG_FAIL("pregen_lane: this level kind / layout is not covered by the lane generator"); }
         else if ((v != 0) != (e->pregen_lane != 0)) {
             HIP_TRY(hipDeviceSynchronize());
             // the lane-group kernel reads and writes the canonical form; the lane kernel needs the tempered halves behind it
-            { int rc = mt_canon(e); if (rc != BBAI_OK) return rc; }
-            { int rc = mt_sync(e); if (rc != BBAI_OK) return rc; }
+            BBAI_TRY(mt_canon(e));
+            BBAI_TRY(mt_sync(e));
             e->pregen_lane = v != 0;
         }
     }
-    else if (!strcmp(name, "lane_blocks")) e->lane_blocks = std::max(1, v);
-    else if (!strcmp(name, "pregen_blocks")) e->pregen_cap = std::max(64, v);
-    else if (!strcmp(name, "pregen_min")) e->pregen_min = std::max(0, v);
-    else if (!strcmp(name, "pregen_per_group")) e->pregen_per_group = std::max(1, v);
-    else if (!strcmp(name, "consume_fused")) e->consume_fused = v;
-    else if (!strcmp(name, "gate_strict")) e->gate_strict = v != 0;
-    else if (!strcmp(name, "gate_probe")) { e->gate_probe = v; e->n_probed = 0; e->gate_forced = 0; }      // (forget the verdicts: the next window probes again)
+    else if (!strcmp(name, "lookahead_streams")) BBAI_TRY(set_sides(e, v));
     else if (!strcmp(name, "gate_fault_inject")) e->host_flags[0] = v != 0;       // tests: what a timed-out gate leaves behind
-    else if (!strcmp(name, "bot_group")) e->bot_group = v;
-    else if (!strcmp(name, "step_render_split")) e->step_render_split = v;
-    else if (!strcmp(name, "rollout_multi")) e->rollout_multi = v;
-    else if (!strcmp(name, "lookahead_streams")) { int rc = set_sides(e, v); if (rc != BBAI_OK) return rc; }
-    else if (!strcmp(name, "done_action_enum")) e->done_action_enum = v != 0;       // (the one SEMANTIC switch in this list: include/bbai.h bbai_set_done_actions)
+    else if (k && !k->read_only) {
+        if (k->field == &bbai_env::render_piece_bytes && v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
+        e->*k->field = knob_value(*k, v);
+        if (k->field == &bbai_env::render_delta) { e->rt_valid = false; e->rt_filled = 0; }
+        if (k->field == &bbai_env::gate_probe) { e->n_probed = 0; e->gate_forced = 0; }      // (forget the verdicts: the next window probes again)
+    }
     else {
         snprintf(g_err, sizeof(g_err), "set_option: unknown option '%s'", name);
         return BBAI_ERR_ARG;
@@ -3755,49 +3727,18 @@ static int read_flow(bbai_env* e, int word, unsigned long long* out) {
     return BBAI_OK;
 }
 
-// Read back a knob: the names of bbai_set_option, plus "render_pace_effective" and "lookahead_period" (the refill period the handle chose).
+// Read back a knob: every row of KNOBS, plus what is computed on the way out.  ("gate_fault_inject" is write only.)
 int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     if (!e || !name || !out) ARG_FAIL("null handle, name or output");
-    if (!strcmp(name, "render_queue")) *out = e->render_queue;
-    else if (!strcmp(name, "render_queue_bpc")) *out = e->render_queue_bpc;
-    else if (!strcmp(name, "render_queue_blocks")) *out = e->render_queue_blocks;
-    else if (!strcmp(name, "render_pace")) *out = e->render_pace;
-    else if (!strcmp(name, "render_group")) *out = e->render_group;
-    else if (!strcmp(name, "render_tpb")) *out = e->render_tpb;
-    else if (!strcmp(name, "render_delta")) *out = e->render_delta;
-    else if (!strcmp(name, "render_delta_sched")) *out = e->render_delta_sched;
-    else if (!strcmp(name, "render_delta_tpb")) *out = e->render_delta_tpb;
-    else if (!strcmp(name, "render_delta_bpc")) *out = e->render_delta_bpc;
-    else if (!strcmp(name, "render_delta_from_step")) *out = e->render_delta_from_step;
-    else if (!strcmp(name, "render_piece_bytes")) *out = e->render_piece_bytes;
-    else if (!strcmp(name, "grid_render_bpc")) *out = e->grid_bpc;
+    if (const Knob* k = find_knob(name)) *out = e->*k->field;
     else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
-    else if (!strcmp(name, "step_prio")) *out = e->step_prio;
-    else if (!strcmp(name, "pregen_group")) *out = e->pregen_group;
-    else if (!strcmp(name, "pregen_lane")) *out = e->pregen_lane;
-    else if (!strcmp(name, "lane_blocks")) *out = e->lane_blocks;
-    else if (!strcmp(name, "pregen_blocks")) *out = e->pregen_cap;
-    else if (!strcmp(name, "pregen_min")) *out = e->pregen_min;
-    else if (!strcmp(name, "pregen_per_group")) *out = e->pregen_per_group;
-    else if (!strcmp(name, "consume_fused")) *out = e->consume_fused;
-    else if (!strcmp(name, "gate_strict")) *out = e->gate_strict;
-    else if (!strcmp(name, "gate_probe")) *out = e->gate_probe;
-    else if (!strcmp(name, "gate_forced_strict")) *out = e->gate_forced;          // 1: the caller's stream failed the concurrency probe
     else if (!strcmp(name, "gate_fault")) *out = e->host_flags ? (int64_t)e->host_flags[0] : 0;     // sticky; no synchronisation
-    else if (!strcmp(name, "bot_group")) *out = e->bot_group;
-    else if (!strcmp(name, "step_render_split")) *out = e->step_render_split;
-    else if (!strcmp(name, "rollout_multi")) *out = e->rollout_multi;
-    else if (!strcmp(name, "lookahead_streams")) *out = e->n_sides;
     else if (!strcmp(name, "profile_step_ticks")) *out = e->prof_step_ticks;
-    else if (!strcmp(name, "inplace")) *out = e->inplace;
     else if (!strcmp(name, "cplane")) *out = e->cplane ? 1 : 0;
-    else if (!strcmp(name, "done_action_enum")) *out = e->done_action_enum;
-    else if (!strcmp(name, "lookahead_period")) *out = e->period;
     else if (!strcmp(name, "gate_timeouts")) {      // (synchronises) window gates that gave up waiting for a refill: must be 0 (k_gate)
         ON_DEVICE(e->device);
         unsigned long long v = 0;
-        int rc = read_flow(e, FLOW_GATE_TIMEOUTS, &v);
-        if (rc != BBAI_OK) return rc;
+        BBAI_TRY(read_flow(e, FLOW_GATE_TIMEOUTS, &v));
         *out = (int64_t)v;
     }
     else if (!strcmp(name, "render_pace_effective")) *out = e->render_pace > 0 ? e->render_pace : 0;
@@ -3831,7 +3772,7 @@ int bbai_generator_failures(bbai_env* e, uint64_t* out) {
     if (!e || !out) ARG_FAIL("null pointer");
     ON_DEVICE(e->device);
     unsigned long long v = 0;
-    { int rc = read_flow(e, FLOW_GEN_FAILURES, &v); if (rc != BBAI_OK) return rc; }
+    BBAI_TRY(read_flow(e, FLOW_GEN_FAILURES, &v));
     *out = (uint64_t)v;
     return BBAI_OK;
 }

@@ -350,7 +350,8 @@ int bbai_get_done_actions(bbai_env* env);
 
 /* Performance knobs of a live handle, by name (what the BBAI_* environment variables set at bbai_create; the reference has
  * no counterpart: these choose launch shapes and buffers, never results -- every setting but the last yields the same bytes, which
- * tests/test_gpu_parity.py::test_options_do_not_change_results checks).  Synchronises the device.  Names:
+ * tests/test_gpu_parity.py::test_options_do_not_change_results checks).  Synchronises the device.  A knob's default and clamp are the same
+ * whether its value comes from the variable at bbai_create or from a set (one table in bbai_engine.hip; tests/test_gpu_options.py).  Names:
  *   "render_queue"      -1 = by batch size (default), 0 = one-shot render blocks, m > 0 = persistent-block queue shape m
  *   "render_pace"       experiment: 1/16 ns of wall clock per render ticket (a time gate over two ticket counters); 0 = off (default)
  *   "render_queue_bpc", "render_queue_blocks"   persistent render blocks per CU (0 = 1024 threads' worth) / in total (0 = per CU)
