@@ -1,7 +1,9 @@
 // bbai_render.hpp -- the partial-view pixel render (RGBImgPartialObsWrapper as a tile-atlas gather): the full render (k_render, k_render_q),
 // the delta render into the registered target (k_render_delta) and its store-only form behind a step that found the dirty cells itself
 // (k_render_dstore).  Every stage the kernels share is written once: load_atlas_lds / load_lut_lds, tile_id, store_chunk16, delta_cell,
-// init_line_table, list_dirty_lines, store_listed_lines, init_piece_cells, store_dirty_pieces.  Two copies remain, each marked where it
+// init_line_table, list_dirty_lines, store_listed_lines, init_piece_cells, init_chunk_table, store_chunk16_t, store_dirty_pieces.  The piece
+// stores address their chunks through a per-block table (chunk_recipe below: the frame geometry of a 16-byte chunk, worked out once per
+// block and not once per store); the full renders keep the arithmetic form (render_chunk).  Two copies remain, each marked where it
 // stands, because the shared form changed the compiler's register counts: phase A in k_render_delta's piece branch, B1 in k_render_dstore.
 //
 // The first part is plain C++ -- the geometry of a frame in memory, which the host tests read through tests/hostsim (hs_line_cells).  The
@@ -36,6 +38,39 @@ BB_HD uint64_t line_cells(int s, int t) {
     }
     return m;
 }
+
+// The recipe of the 16-byte chunk k (of VEC_PER_ENV) of an env's image: its two 8-byte halves (chunks 2k and 2k + 1 of render_chunk) as
+// (view cell, byte offset inside the atlas tile = row in tile * 24 + third of the row * 8), packed one byte each: cell A, offset A, cell B,
+// offset B from the low byte up.  It depends on the chunk's place in the frame alone: the piece stores read it from a table in LDS
+// (init_chunk_table) where the full renders redo the divisions per store.  Worked out from the byte address, not from render_chunk's
+// chunk arithmetic -- the assertion below holds the two against each other for every chunk.
+BB_HD constexpr uint32_t chunk_half_recipe(int byte) {
+    const int row = byte / (PIX * 3), xb = byte - row * (PIX * 3);        // pixel row of the frame, byte within the row
+    const int cell = xb / (TILE * 3) * VIEW + row / TILE;                  // view cell: column * VIEW + row (as tile_id's `cell`)
+    const int off = row % TILE * (TILE * 3) + xb % (TILE * 3);             // byte inside the tile
+    return (uint32_t)cell | (uint32_t)off << 8;
+}
+BB_HD constexpr uint32_t chunk_recipe(int k) { return chunk_half_recipe(16 * k) | chunk_half_recipe(16 * k + 8) << 16; }
+
+// ... against render_chunk's arithmetic, restated (render_chunk reads LDS and is no constant expression)
+BB_HD constexpr bool chunk_recipes_match_render_chunk() {
+    for (int k = 0; k < VEC_PER_ENV; ++k) {
+        uint32_t w = 0;
+        for (int h = 0; h < 2; ++h) {
+            const int ch = 2 * k + h;
+            const int py = ch / CHUNKS_PER_ROW, cx = ch - py * CHUNKS_PER_ROW;
+            const int ti = cx / 3, part = cx - ti * 3;
+            const int tj = py >> 3, ty = py & 7;
+            const int cell = ti * VIEW + tj, off = ty * 24 + part * 8;
+            if (cell < 0 || cell >= VIEW * VIEW || off < 0 || off + 8 > TILE_BYTES) return false;
+            w |= ((uint32_t)cell | (uint32_t)off << 8) << (16 * h);
+        }
+        if (chunk_recipe(k) != w) return false;
+    }
+    return true;
+}
+static_assert(TILE == 8 && TILE_BYTES <= 256 && VIEW * VIEW <= 256, "a cell and a tile offset fit a byte each");
+static_assert(chunk_recipes_match_render_chunk(), "chunk_recipe(k) = render_chunk's (cell, offset) of chunks 2k and 2k + 1, for every k");
 
 // P-byte pieces of an env's image (store_dirty_pieces below)
 template <int P>
@@ -79,6 +114,20 @@ __device__ __forceinline__ uint64_t render_chunk(const uint8_t* s_atlas, const u
 __device__ __forceinline__ void store_chunk16(const uint8_t* s_atlas, const uint8_t* t49, int k, u32x4* dst) {
     const uint64_t lo = render_chunk(s_atlas, t49, 2 * k);
     const uint64_t hi = render_chunk(s_atlas, t49, 2 * k + 1);
+    u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+    __builtin_nontemporal_store(v, dst);
+}
+
+// The same store through the chunk table (`s_ct`: chunk_recipe of every chunk, init_chunk_table): one table word, two tile ids, two atlas
+// words -- no division per store.  The same bytes as store_chunk16.
+__device__ __forceinline__ void init_chunk_table(uint32_t* s_ct, int tid, int T) {
+    for (int k = tid; k < bbai::VEC_PER_ENV; k += T) s_ct[k] = bbai::chunk_recipe(k);
+}
+__device__ __forceinline__ void store_chunk16_t(const uint8_t* s_atlas, const uint32_t* s_ct, const uint8_t* t49, int k, u32x4* dst) {
+    const uint32_t w = s_ct[k];
+    const uint32_t ta = t49[w & 0xff], tb = t49[(w >> 16) & 0xff];
+    const uint64_t lo = *(const uint64_t*)(s_atlas + ta * TILE_BYTES + ((w >> 8) & 0xff));
+    const uint64_t hi = *(const uint64_t*)(s_atlas + tb * TILE_BYTES + (w >> 24));
     u32x4 v = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
     __builtin_nontemporal_store(v, dst);
 }
@@ -294,8 +343,8 @@ __device__ __forceinline__ void init_piece_cells(uint64_t* s_pm, int tid, int nt
 // Stores the pieces of one env whose cells meet the dirty mask `m` (wave-uniform, nonzero).  Called by a whole wave; `wl` is the
 // wave's list (NP entries), `t49` the env's 49 tile ids, `out` the env's first 16-byte chunk.
 template <int P>
-__device__ __forceinline__ void store_dirty_pieces(uint64_t m, const uint64_t* s_pm, uint16_t* wl, const uint8_t* s_atlas, const uint8_t* t49,
-                                                   u32x4* out, int lane) {
+__device__ __forceinline__ void store_dirty_pieces(uint64_t m, const uint64_t* s_pm, uint16_t* wl, const uint8_t* s_atlas, const uint32_t* s_ct,
+                                                   const uint8_t* t49, u32x4* out, int lane) {
     constexpr int NP = Pieces<P>::NP, S = Pieces<P>::S;
     int cnt = 0;
     for (int p0 = 0; p0 < NP; p0 += 64) {
@@ -308,7 +357,7 @@ __device__ __forceinline__ void store_dirty_pieces(uint64_t m, const uint64_t* s
     wave_lds_sync();
     for (int i = lane; i < cnt * S; i += 64) {
         const int k = (int)wl[i / S] * S + (i & (S - 1));
-        store_chunk16(s_atlas, t49, k, out + k);
+        store_chunk16_t(s_atlas, s_ct, t49, k, out + k);
     }
     wave_lds_sync();                                  // the list is read before the wave's next env writes it
 }
@@ -348,9 +397,11 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
         __shared__ uint64_t s_pm[Pieces<P>::NP];
         __shared__ uint16_t s_wl[W][Pieces<P>::NP];
         __shared__ uint8_t s_tile1[G * CELLS + 8];
+        __shared__ uint32_t s_ct[VEC_PER_ENV];
         init_piece_cells<P>(s_pm, threadIdx.x, T);
+        init_chunk_table(s_ct, threadIdx.x, T);
         load(g);
-        __syncthreads();                              // atlas, lut and piece table loaded
+        __syncthreads();                              // atlas, lut, piece and chunk tables loaded
         for (; g < gend; g += gstep) {
             const int64_t env0 = g * G;
             const int ne = (int)(n - env0 < G ? n - env0 : G);
@@ -370,7 +421,7 @@ __global__ __launch_bounds__(T) void k_render_delta(int64_t n, const uint8_t* __
 #pragma unroll
             for (int j = 0; j < EPW; ++j) {
                 const int e = wave + j * W;
-                if (dm[j]) store_dirty_pieces<P>(dm[j], s_pm, s_wl[wave], s_atlas, s_tile1 + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
+                if (dm[j]) store_dirty_pieces<P>(dm[j], s_pm, s_wl[wave], s_atlas, s_ct, s_tile1 + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
             }
         }
         return;
@@ -449,8 +500,10 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
         __shared__ uint64_t s_pm[Pieces<P>::NP];
         __shared__ uint16_t s_wl[W][Pieces<P>::NP];
         __shared__ uint64_t s_dm3[3][G];
+        __shared__ uint32_t s_ct[VEC_PER_ENV];
         const int wave = tid >> 6;
         init_piece_cells<P>(s_pm, tid, T);
+        init_chunk_table(s_ct, tid, T);
         auto load_ids = [&](int64_t grp, int b) -> uint2 {
             if (tid >= DSTORE_PIECES || grp >= ngroups) return make_uint2(0u, 0u);
             const int ea = (8 * tid) / CELLS, eb = (8 * tid + 7) / CELLS;
@@ -459,7 +512,7 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
         };
         if (tid < G) s_dm3[0][tid] = load_mask(g);
         uint64_t mreg = load_mask(g + gstep);
-        __syncthreads();                              // atlas, piece table and the first group's masks
+        __syncthreads();                              // atlas, piece and chunk tables and the first group's masks
         uint2 idr = load_ids(g, 0);
         int buf = 0, mb = 0;
         for (; g < ngroups; g += gstep, buf ^= 1, mb = mb == 2 ? 0 : mb + 1) {
@@ -474,7 +527,7 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
             for (int j = 0; j < EPW; ++j) {
                 const int e = wave + j * W;
                 const uint64_t m = s_dm3[mb][e];      // (0 past the end of the range)
-                if (m) store_dirty_pieces<P>(m, s_pm, s_wl[wave], s_atlas, s_tile[buf] + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
+                if (m) store_dirty_pieces<P>(m, s_pm, s_wl[wave], s_atlas, s_ct, s_tile[buf] + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
             }
         }
         return;
