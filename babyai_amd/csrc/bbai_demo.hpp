@@ -10,6 +10,8 @@
 // aligned loads around it stay inside any allocation that starts 16-byte aligned and is a multiple of 16 bytes long.
 // ------------------------------------------------------------------------------------------
 #pragma once
+#include <hip/hip_runtime.h>
+#include "bbai_kernels.hpp"      // u32x4
 
 namespace bbai {
 

@@ -1,29 +1,27 @@
-// bbai_engine.hip -- HIP kernels + C ABI of the batched BabyAI engine (gfx950 / MI355X).
+// bbai_engine.hip -- the host side and the C ABI of the batched BabyAI engine (gfx950 / MI355X): the handle (bbai_env), its options, the
+// launches of every kernel and the streams, windows and events around them.  This file holds no kernel; its translation unit is made of
+// the kernel headers it includes, one per family, each at the spot where its code stood (the order is the kernels' order in the library,
+// nothing else: every header includes what it uses; what several families or this file share is in bbai_kernels.hpp).
 //
-// Kernels (all integer / byte work, HBM- and latency-bound; no MFMA by design):
-//   k_step<VP, FUSE>  lane = env, one wave per block.  Coalesced SoA loads of the 16-byte hot state, action, stale set and verifier program;
-//                  per-lane transition + verifier on the env's record; the 7x7 window is fetched as 7 rows x 3 dwords (one 128-byte line
-//                  of the window plane, VP) and rotated, occluded and masked in REGISTERS (bbai_view.hpp: byte permutes, SWAR opacity,
-//                  dot-product row masks); the 147-byte encodings of the block's 64 envs are staged in LDS at the output pitch and leave as one
-//                  contiguous 16-byte-per-lane span.  Finished envs: FUSE 1 -- the stepping wave consumes their look-ahead slots itself
-//                  (consume_env); FUSE 3 (in-place layout) -- every finished lane moves its own env on to its next ring slot
-//                  (advance_load / advance_finish); FUSE 0 -- compacted into a reset list for k_consume.  The fused paths leave NO
-//                  returning atomic and no list behind: one fire-and-forget add to a sharded total per wave, per-env bytes for the refill.
-//   k_pregen<F, G, OBS>  (F = level family) one env per group of G lanes: the NEXT levels of an env's MT19937 stream, working set in LDS
-//                  (bbai_gen.hpp), into the env's look-ahead ring (OBS: + the level's first observation).  step() draws no randomness, so an
-//                  env's level sequence is a pure function of its seed: generation runs ahead of need on a second HIP stream, one launch per
-//                  window of B consume-ticks over the list k_compact builds from the window's `pending` bytes.
-//   k_compact / k_mark / k_gate   the windows' turnover: the refill's work list (look-ahead stream), the refill's completion count, and
-//                  the step stream's wait for "every env is sure to keep a window's worth of ready levels" (see NWIN below).
-//   k_consume      wave = env over the reset list (unfused steps, reset()): look-ahead slot -> live state, SoA verifier view, first observation.
-//   k_tokens       lane = env: mission text as fixed-vocabulary token ids of the envs that started a new episode.
-//   k_render_q / k_render   RGBImgPartialObsWrapper as a pure tile-atlas gather: atlas + per-cell tile ids in LDS, 16 bytes per lane per
-//                  store, a wave writes 1 KiB of contiguous pixels; persistent blocks fed by ONE ticket counter from 262 144 envs
-//                  (k_render_q), one-shot (512, 2) blocks below.  Into the registered target (bbai_set_render_target): k_render_delta /
-//                  k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
-//                  the buffer holds are stored.  All four live in bbai_render.hpp; their launches (render_launch) are here.
-//   k_bot<W>       lane = env: one decision of the reference's GOFAI expert (babyai/bot.py) per env, W = occupancy target
-//                  (bbai_bot.hpp); only launched by bbai_bot_act / bbai_bot_rollout.
+// Kernels (all integer / byte work, HBM- and latency-bound; no MFMA by design) -- where each one lives:
+//   bbai_stepk.hpp    k_step<VP, FUSE, CP>, k_step_ticks: lane = env, one wave per block; the finished envs' consume (consume_env,
+//                     advance_load / advance_finish) and the step's dirty cells for its delta render (step_dirty).  Launched by step_kernel.
+//   bbai_pregen.hpp   k_pregen<F, G, OBS>: the lane-group level generator, one env per group of G lanes, into the env's look-ahead ring;
+//                     k_mt_sync / k_mt_canon: the two forms of the generators' RNG state.  (launch_pregen_g, mt_sync, mt_canon.  The lane =
+//                     level generator k_pregen_lane is bbai_genlane.hip, a translation unit of its own: launch_pregen_lane -> bbai_lane_launch.)
+//   bbai_ring.hpp     k_consume (look-ahead slot -> live state over the reset list: unfused steps, reset()); k_compact / k_mark / k_gate (the
+//                     windows' turnover: window_begin, window_end); k_probe_wait / k_probe_set (probe_stream); k_live_copy, k_import_hot,
+//                     k_sync_prog / k_sync_view / k_sync_cpl (export, import, checkpoints); k_seed, k_init_hot.
+//   bbai_botk.hpp     k_bot<W>: one decision of the reference's expert per env (bbai_bot.hpp); k_botg in experiment builds.  (bot_launch)
+//   bbai_render.hpp   k_render_q / k_render: RGBImgPartialObsWrapper as a pure tile-atlas gather: atlas + per-cell tile ids in LDS, 16 bytes per
+//                     lane per store, a wave writes 1 KiB of contiguous pixels; persistent blocks fed by ONE ticket counter from 262 144 envs
+//                     (k_render_q), one-shot (512, 2) blocks below.  Into the registered target (bbai_set_render_target): k_render_delta /
+//                     k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
+//                     the buffer holds are stored.  (render_launch)
+//   bbai_gridk.hpp    k_render_grid<TS>: the full-grid picture; k_full_obs: the fully observable encoding.  (render_grid_launch, full_launch)
+//   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
+//                     k_gae (bbai_gae).
+//   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch: demonstrations that stay on the device.
 //
 // Reference semantics: see bbai_step.hpp / bbai_gen.hpp / bbai_bot.hpp headers for file:line citations.
 #include <hip/hip_runtime.h>
@@ -96,9 +94,8 @@ constexpr int MAX_SIDES = 8;            // look-ahead streams a window's refill 
 #define LOOKAHEAD_STREAMS_DEFAULT 1
 #endif
 constexpr int MAX_PERIOD = 96;          // refill period B (ticks per look-ahead refill); ring depth D = 2B (+ 1 in place): slot numbers and per-window counts stay bytes
-constexpr int NWIN = 34;                // window buffers (see "the windows' bookkeeping" below): at most 33 refills outstanding, whatever B
 
-struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defaults and clamps: KNOBS, below the kernels)
+struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defaults and clamps: KNOBS, below)
     LevelCfg cfg;
     int64_t n;
     int device;
@@ -218,7 +215,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int n_cus;            // compute units of the device
     int done_action_enum; // done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
     int consume_fused;    // -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
-    int inplace;          // BBAI_INPLACE: the in-place layout (live_slot below): an env's live record IS the look-ahead slot its episode was generated into
+    int inplace;          // BBAI_INPLACE: the in-place layout (live_slot, bbai_kernels.hpp): an env's live record IS the look-ahead slot its episode was generated into
     uint8_t* atlas;       // [n_tiles][192]
     uint8_t* lut;         // [2][256]
     int n_tiles;
@@ -237,1731 +234,15 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint64_t* bot_stats;  // [2] decisions that ended in a dead bot: by the reference's rules / by our capacity limits
 };
 
-// ------------------------------------------------------------------------------------------
-// k_step
-// ------------------------------------------------------------------------------------------
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// ---- the windows' bookkeeping: no lists, no same-address atomics on the step path -----------------------------------------------
-// Rounds 1-4 compacted the finished envs of every tick into a window list for the refill (one RETURNING atomic per stepping wave
-// on ONE address: ~2 700 of them per step at 262 144 reset-heavy envs, served at ~11 ns each -- half of that k_step's time) and made
-// the step stream wait, at the start of window w + 2, for the refill of window w (an env MIGHT finish on every tick).  Now:
-//   * what a stepping wave leaves behind is one fire-and-forget add to a sharded total (SHARDS cache lines) and per-env bytes; the
-//     refill's work list is built where it costs nothing: k_compact, on the look-ahead stream in front of k_pregen, turns the window's
-//     `pending` bytes (n bytes per B ticks) into SHARDS dense sub-lists (one returning atomic per 64 envs that hold a finished one,
-//     spread over SHARDS counters), which k_pregen walks as ONE list through a prefix of the sub-counts -- the same perfectly
-//     balanced entry-per-group distribution as before.  (Letting the generator's groups scan the bytes themselves was measured
-//     first -- lease r05a: a group then finds 0 to 4 envs where its neighbour finds one, a wave lives as long as its unluckiest
-//     group, and the mazes' steps slowed by 10-30 % under the generator's idle lanes.)
-//   * every window records M = the most often ONE env finished in it (1 unless short episodes repeat inside a window: the
-//     rare atomicMax in the consume paths); an env's unrefilled slots are <= the sum of M over the windows whose refill has not
-//     landed, so window x may start as soon as that sum is <= B (every env then still has B ready levels, and a window consumes
-//     at most B) -- k_gate, one wave on the step stream at every window start, waits for exactly that instead of for "refill
-//     w - 2 has landed".  A reset storm (a million maze envs timing out on the same tick: 37 ms of generator time) then runs
-//     UNDER the following windows instead of stopping the step stream, as long as no env finishes B more times meanwhile.
-//   * NWIN = 34 window buffers (pending / first_slot / meta): up to 33 refills can be outstanding (B + 1 of them for B <= 32).
-// tests/test_ring_protocol.py models the rule (sufficient, and the ring depths stay tight).
-__device__ __forceinline__ void count_resets(unsigned long long* __restrict__ totals, unsigned int k, unsigned int blk) {
-    atomicAdd(&totals[(blk & (SHARDS - 1)) * SHARD_U64], (unsigned long long)k);        // (result unused: a no-return atomic)
-}
-// envs (= threads) per k_step block.  The kernel is bound by its chain of dependent memory round trips, not by bytes or
-// instructions, and a block is what waits at its barriers for its slowest wave: ONE wave per block (64) measured against
-// 128 / 256 in round 3 (profiles/r03/step_variants_ab.jsonl: BossLevel encoded 1 048 576 envs k_step 0.130 -> 0.124 -> 0.111 ms,
-// PickupLoc 262 144 0.071 -> 0.061 -> 0.051, GoTo 131 072 0.0212 -> 0.0192 -> 0.0184, GoToLocal 65 536 0.0244 -> 0.0216 -> 0.0214).
-// The in-wave consume (FUSE) RELIES on it: the LDS traffic of a block is ordered by the wave's program order alone.
-constexpr int STEP_BLOCK = 64;
-#ifndef BBAI_STEP_WAVES
-#define BBAI_STEP_WAVES 1          // minimum waves per SIMD the register allocation of k_step has to allow (the compiler's own figures:
-#endif                             // babyai_amd/kernel_resources.json, quoted in DESIGN.md section 4; the block's 9.4 KB of LDS stop at 17 blocks per CU)
-// BBAI_PREFETCH_ID=1 (experiment): the id-plane entry of the front cell fetched WITH the window.  Measured slower everywhere
-// (step_variants_ab.jsonl: BossLevel encoded 1M k_step 0.130 -> 0.148 ms, GoTo 131 072 0.021 -> 0.028): one more line per
-// env-step costs more than the verifier's occasional extra round trip.  Off.
-#ifndef BBAI_PREFETCH_ID
-#define BBAI_PREFETCH_ID 0
-#endif
-
-// BBAI_VIEW_LDS=1 (A/B builds): rounds 2-4's view -- the window parked in LDS and read back cell by cell (view_cells / encode_view below).  The shipped
-// path is bbai_view.hpp: the same view as byte permutes on packed registers (k_step: -~900 of ~2 600 vector instructions, -63 LDS operations per env-step).
-#ifndef BBAI_VIEW_LDS
-#define BBAI_VIEW_LDS 0
-#endif
-// Observation with the 7x7 window staged in LDS (rounds 2-4's k_step path).  49 scattered byte loads per lane keep the
-// texture-address unit busy for most of k_step (tools/step_ab.py ablation), so the window is fetched in WORLD
-// orientation as 7 rows x 3 aligned dwords, byte-aligned with v_alignbyte, parked in 56 dword-aligned bytes inside the
-// lane's own LDS obs row (`scr`, bbai_step.hpp row_scratch), and read back in VIEW orientation (rotation = per-direction
-// address arithmetic on ds_read_u8).  All of a lane's reads precede its writes and lanes only touch bytes of their own
-// row, so no barrier is needed here.
-// The window's rows come from `q` (first aligned dword of row 0), `rstride` dwords apart, `off` = byte offset of the
-// window's first column inside that dword: the record's appearance plane (rstride = ES / 4) or the env's V-plane line
-// (rstride = 4).  `ce` = appearance of what the agent carries (E_EMPTY: nothing).  `fe2` receives the appearance of the
-// cell in front of the agent (view cell (3, 5)) for the verifier and the next step's transition.
-// Two halves, so that the verifier (which only needs fe2) can run between them while nothing of the 37-dword encoding is
-// live yet: view_cells fetches and rotates the window (cp = the 49 cells, vis = visibility rows), encode_view writes the
-// encoding from them.
-// window_fetch issues the loads (7 rows x 3 dwords: one dwordx3 each); view_cells consumes them.  k_step puts the rare
-// object actions (pickup / drop / toggle: dependent record loads and stores) BETWEEN the two, so their memory round trips
-// overlap the window's instead of preceding it.  Such an action changes exactly one cell of the window that was fetched
-// before it ran -- the one in front of the agent, view cell (3, 5): `nfe` >= 0 is its new appearance, patched in LDS.
-__device__ __forceinline__ void window_fetch(const uint32_t* __restrict__ q, int rstride, uint32_t* wd) {
-#pragma unroll
-    for (int r = 0; r < VIEW; ++r) { wd[3 * r] = q[r * rstride]; wd[3 * r + 1] = q[r * rstride + 1]; wd[3 * r + 2] = q[r * rstride + 2]; }
-}
-__device__ __forceinline__ void view_cells(const uint32_t* wd, int off, int dir, uint32_t ce, int nfe,
-                                           uint8_t* __restrict__ scr /* this lane's 56 bytes of LDS scratch */, uint32_t* cp, uint32_t* vis, int& fe2) {
-    uint32_t* win = (uint32_t*)scr;                          // 7 rows x 8 bytes, dword aligned
-#pragma unroll
-    for (int r = 0; r < VIEW; ++r) {
-        win[2 * r] = __builtin_amdgcn_alignbyte(wd[3 * r + 1], wd[3 * r], off);
-        win[2 * r + 1] = __builtin_amdgcn_alignbyte(wd[3 * r + 2], wd[3 * r + 1], off);
-    }
-    // view (vi, vj) -> window byte: dir3 (vj, vi), dir0 (vi, 6-vj), dir1 (6-vj, 6-vi), dir2 (6-vi, vj); row pitch 8
-    const int k0 = dir == 0 ? 6 : dir == 1 ? 54 : dir == 2 ? 48 : 0;
-    const int kvi = dir == 0 ? 8 : dir == 1 ? -1 : dir == 2 ? -8 : 1;
-    const int kvj = dir == 0 ? -1 : dir == 1 ? -8 : dir == 2 ? 1 : 8;
-    uint8_t* wb = scr + k0;
-    if (nfe >= 0) wb[kvi * 3 + kvj * 5] = (uint8_t)nfe;      // (same lane: LDS operations of a lane stay in order)
-#pragma unroll
-    for (int k = 0; k < 13; ++k) cp[k] = 0;                      // the 49 cells, 4 per dword, view order [vi][vj]
-    uint32_t opq[VIEW] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int vi = 0; vi < VIEW; ++vi)
-#pragma unroll
-        for (int vj = 0; vj < VIEW; ++vj) {
-            const int idx = vi * VIEW + vj;
-            const uint32_t e = wb[kvi * vi + kvj * vj];
-            cp[idx >> 2] |= e << (8 * (idx & 3));
-            opq[vj] |= (e_opaque((int)e) ? 1u : 0u) << vi;
-        }
-    process_vis_rows(opq, vis);
-    fe2 = (int)((cp[(3 * VIEW + 5) >> 2] >> (8 * ((3 * VIEW + 5) & 3))) & 0xFFu);
-    {   // the agent's own cell (3,6) shows what it carries
-        constexpr int idx = 3 * VIEW + 6;
-        cp[idx >> 2] = (cp[idx >> 2] & ~(0xFFu << (8 * (idx & 3)))) | (ce << (8 * (idx & 3)));
-    }
-}
-// Four cells at a time: a dword of (visibility-masked) appearance bytes e0..e3 becomes the 12 encoding bytes
-// t0 c0 s0 t1 | c1 s1 t2 c2 | s2 t3 c3 s3 (type = e & 7, colour = (e >> 3) & 7, state = e >> 6) with three field extractions on
-// the whole dword and six byte permutes (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first,
-// 0x0C is zero) -- 11 instructions per four cells instead of ~55 shifting every channel byte into place on its own.
-__device__ __forceinline__ void encode_view(const uint32_t* cp, const uint32_t* vis, RowPacker o) {
-#pragma unroll
-    for (int k = 0; k < 13; ++k) {
-        // the cells of this dword that are visible: byte b <- bit (idx / 7) of vis[idx % 7], idx = 4k + b
-        uint32_t m = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int idx = 4 * k + b;
-            if (idx < VIEW * VIEW) m |= (uint32_t)__builtin_amdgcn_sbfe((int)vis[idx % VIEW], idx / VIEW, 1) & (0xFFu << (8 * b));   // v_bfe_i32: 0 / ~0
-        }
-        const uint32_t x = cp[k] & m;
-        const uint32_t t = x & 0x07070707u, c = (x >> 3) & 0x07070707u, st = (x >> 6) & 0x03030303u;
-        if (k < 12) {
-            o.put(3 * k, __builtin_amdgcn_perm(__builtin_amdgcn_perm(t, c, 0x050C0004u), st, 0x07000504u));
-            o.put(3 * k + 1, __builtin_amdgcn_perm(__builtin_amdgcn_perm(c, st, 0x060C0105u), t, 0x07020504u));
-            o.put(3 * k + 2, __builtin_amdgcn_perm(__builtin_amdgcn_perm(st, t, 0x070C0306u), c, 0x07030504u));
-        } else {
-            o.put(36, (t & 0xFFu) | ((c & 0xFFu) << 8) | ((st & 0xFFu) << 16));   // cell 48: three bytes, the row's last dword
-        }
-    }
-    o.finish();
-}
-
-// Wave-cooperative observation of ONE env (used where a wave owns an env: consume_env): lane l < 49 owns view cell
-// (vi, vj) = (l % 7, l / 7); the opacity mask of the whole view is one ballot; every lane runs the 7-row
-// visibility sweep on it and writes its own three bytes.  In two halves so that the caller can put other memory traffic
-// between the cell load and its use: observe_fetch returns the lane's cell, observe_emit does the rest.
-__device__ __forceinline__ int observe_fetch(const LevelCfg& c, const uint8_t* __restrict__ rec, const Hot& h, int lane) {
-    const int vi = lane % VIEW, vj = lane / VIEW;
-    int e = E_EMPTY;
-    if (lane < VIEW * VIEW) {
-        int x, y;
-        view_to_world(h.ax, h.ay, h.dir, vi, vj, x, y);
-        e = rec[e_index(c, x, y)];
-    }
-    return e;
-}
-__device__ __forceinline__ void observe_emit(const LevelCfg& c, const uint8_t* __restrict__ rec, const Hot& h, int e,
-                                             uint8_t* __restrict__ dst, int lane) {
-    const int vi = lane % VIEW, vj = lane / VIEW;
-    const unsigned long long opaque = __ballot(lane < VIEW * VIEW && e_opaque(e));
-    uint32_t opq[VIEW], vis[VIEW];
-#pragma unroll
-    for (int r = 0; r < VIEW; ++r) opq[r] = (uint32_t)(opaque >> (VIEW * r)) & 0x7Fu;
-    process_vis_rows(opq, vis);
-    if (lane < VIEW * VIEW) {
-        if (vi == 3 && vj == 6) e = h.carry != NONE8 ? rec[c.off_app + h.carry] : (int)E_EMPTY;
-        uint32_t row = 0;
-#pragma unroll
-        for (int r = 0; r < VIEW; ++r) row = (vj == r) ? vis[r] : row;
-        const bool v = row >> vi & 1;
-        uint8_t* o = dst + (vi * VIEW + vj) * 3;
-        o[0] = v ? e_type(e) : 0; o[1] = v ? e_color(e) : 0; o[2] = v ? e_state(e) : 0;
-    }
-}
-
-// V-plane helpers (bbai_types.hpp "window plane").  Patch one cell into every line that holds it.
-__device__ __forceinline__ void v_patch(const LevelCfg& c, uint8_t* __restrict__ vrow, int x, int y, int val) {
-    const int xm = x + MARGIN, ym = y + MARGIN, nxo = v_nxo(c), nyo = v_nyo(c);
-    const int yo_lo = ym >= 6 ? (ym - 6) >> 1 : 0, yo_hi = (ym >> 1) < nyo - 1 ? (ym >> 1) : nyo - 1;
-    for (int xo = (xm >> 3) - 1; xo <= (xm >> 3); ++xo) {
-        if (xo < 0 || xo >= nxo) continue;
-        for (int yo = yo_lo; yo <= yo_hi; ++yo) vrow[(yo * nxo + xo) * VLINE + (ym - 2 * yo) * 16 + (xm - 8 * xo)] = (uint8_t)val;
-    }
-}
-// One 16-byte row segment of a V-plane line out of an appearance plane (`E`, row pitch ES); `sc` = plane index of a cell
-// to show as empty (the start-carry object, which leaves the grid right after the first observation), or -1.
-__device__ __forceinline__ u32x4 v_segment(const LevelCfg& c, const uint8_t* __restrict__ E, int line, int r, int sc) {
-    const int nxo = v_nxo(c);
-    const int yo = line / nxo, xo = line - yo * nxo;
-    const int prow = 2 * yo + r, pcol = 8 * xo;
-    const int base = prow * c.ES + pcol;
-    uint32_t w[4];
-    // branch-free: a dword outside the plane is read at offset 0 and replaced by zero, so the four loads (and those of the
-    // caller's other segments) are in flight together -- as conditional loads each one was its own round trip
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const bool ok = prow < c.EH && pcol + 4 * d < c.ES;
-        uint32_t v = *(const uint32_t*)(E + (ok ? base + 4 * d : 0));
-        const int k = sc - (base + 4 * d);
-        if (k >= 0 && k < 4) v = (v & ~(0xFFu << (8 * k))) | ((uint32_t)E_EMPTY << (8 * k));
-        w[d] = ok ? v : 0u;
-    }
-    u32x4 out = {w[0], w[1], w[2], w[3]};
-    return out;
-}
-
-// An env's C plane row (bbai_types.hpp) from its record by ONE wave: lane l = plane cell (l & 7, l >> 3); lanes < cpl_ids = the id bytes (an
-// object stands on the grid iff the id plane holds it at its recorded position).  consume_env (reset()) and k_sync_cpl (imports).
-__device__ __forceinline__ void cpl_build_wave(const LevelCfg& c, const uint8_t* __restrict__ rec, uint8_t* __restrict__ row, int lane) {
-    const int x = lane & 7, y = lane >> 3;
-    const int e = (x < c.W && y < c.H) ? (int)rec[e_index(c, x, y)] : (int)E_WALL;
-    int v = 0xFF;
-    if (lane < c.maxo) {
-        const int ox = rec[c.off_pos + 2 * lane], oy = rec[c.off_pos + 2 * lane + 1];
-        if (ox < c.W && oy < c.H && rec[c.off_I + i_index(c, ox, oy)] == lane + 2) v = oy << 3 | ox;
-    }
-    row[lane] = (uint8_t)e;
-    if (lane < cpl_ids(c)) row[CPL_PLANE + lane] = (uint8_t)v;
-}
-
-// ---- the in-place layout (bbai_env::inplace, chosen at bbai_create) ------------------------------------------------------------
-// Classic layout: every env has a live record of its own (rec[env]); a finished env's next level is COPIED out of its look-ahead
-// slot (1.3 - 1.7 KB + the window plane), by a k_consume launch behind every step or by the stepping wave.  On reset-heavy small
-// shards (single rooms: 2 % of the envs finish on every step) that second dependent launch is 40 % of a step (profiles/r04/NOTES.md
-// section 2), and doing its work inside the stepping waves costs more than the launch.  In-place layout: the live record of an env
-// IS the ring slot its episode was generated into -- the slot BEFORE hot.slot -- and a finished env just moves on to the next
-// slot: nothing is copied, the stepping LANE loads the new pose and program (one round trip), emits the first observation with the
-// step's own window pipeline and swaps the SoA state.  The ring is one slot deeper (2B + 1: the live one + the 2B look-ahead
-// levels of the classic ring); the slot an episode leaves is the one the window's refill regenerates.  rec[] stays allocated as the
-// staging area of export / import / checkpoints.  No window plane in this layout (the window comes out of the record's appearance
-// plane: measures equal on the shards this is for).
-// (ring_at -- the ENV-MAJOR look-ahead ring's addressing -- lives in bbai_kernels.hpp)
-constexpr int OBS_BLOCK = 160;          // bytes of a next_obs slot that hold the first observation (147 used; sixteen-byte loads); OBS_SLOT / CPL_OFF: bbai_types.hpp
-__device__ __forceinline__ int live_slot(int next_slot, int depth) { return (next_slot ? next_slot : depth) - 1; }
-__device__ __forceinline__ uint8_t* live_rec(const LevelCfg& c, int64_t n, int64_t env, uint8_t* recs, uint8_t* ring, int depth, int next_slot) {
-    (void)n;
-    return ring ? ring + ring_at(live_slot(next_slot, depth), env, depth) * (int64_t)c.rec_bytes : recs + env * (int64_t)c.rec_bytes;
-}
-
-// look-ahead slot -> live state of ONE env by ONE wave (k_consume: wave = env over the reset list; k_step<.., FUSE>: the wave that
-// stepped the env): coalesced record copy, SoA verifier view, first observation of the new episode (to `obs_dst`: the caller's
-// image row, or the block's LDS row in k_step), window plane + front cache, window bookkeeping for the batched refill.
-// `win_meta` = the meta line of the tick's window (its M is raised when an env finishes for the second time inside one window).
-// The job is a handful of kilobytes per env, so what it costs is its chain of dependent memory round trips (a reset-heavy small
-// shard pays it on every step): everything that depends on nothing but the slot is LOADED FIRST, in batches that are all in
-// flight together (pose, program, the record's 16-byte vectors, the window plane's row segments), the one load that needs the
-// new pose (the view cell) goes out as soon as the pose is there, and the stores follow.  Round 3's form (load - store pairs
-// in loops) was ten round trips long.
-__device__ __forceinline__ void consume_env(const LevelCfg& c, int64_t n, int64_t env, int slot, int lane, uint8_t* recs,
-                                            Hot* __restrict__ hots, uint64_t* __restrict__ stales, uint8_t* next_recs /* in-place: the start-carry patch goes into the slot */,
-                                            const Hot* __restrict__ next_hots, uint32_t* __restrict__ vheads, uint64_t* __restrict__ vsets,
-                                            int depth, uint8_t* __restrict__ pending, uint8_t* __restrict__ first_slot,
-                                            uint32_t* __restrict__ win_meta, uint8_t* __restrict__ obs_dst, uint8_t* __restrict__ dirs,
-                                            uint8_t* __restrict__ vplane /* or NULL */,
-                                            uint16_t* __restrict__ fcache, uint8_t* __restrict__ lsm_arr /* or NULL */,
-                                            bool inplace = false /* the slot BECOMES the live record: no copy; the slot the episode leaves is what gets refilled */,
-                                            uint8_t* __restrict__ cplane = nullptr /* in-place small rooms: the env's C plane row is rebuilt from the slot */) {
-    const int nvec = c.rec_bytes >> 4;
-    uint8_t* nrec = next_recs + ring_at(slot, env, depth) * (int64_t)c.rec_bytes;
-    Hot h = next_hots[ring_at(slot, env, depth)];
-    const Prog* p = (const Prog*)(nrec + c.off_prog);
-    const int start_carry = p->start_carry;
-    const uint64_t pset = lane < 8 ? p->set[lane >> 1][lane & 1] : 0ull;
-    const uint32_t vh = vhead_pack(*p);
-    const int pend = lane == 0 ? (int)pending[env] : 0;
-    h.slot = (uint8_t)(slot + 1 == depth ? 0 : slot + 1);
-    // the view cell of the new pose (the one load that needs the pose)
-    const int e_view = observe_fetch(c, nrec, h, lane);
-    uint32_t fe0 = nrec[e_index(c, h.ax + dir_dx(h.dir), h.ay + dir_dy(h.dir))];       // (the front cell for the cache: with the view cells, not behind everything)
-    // record: slot -> live copy
-    if (!inplace) {
-        const u32x4* src = (const u32x4*)nrec;
-        u32x4* dst = (u32x4*)(recs + env * (int64_t)c.rec_bytes);
-        constexpr int CPB = 2;
-        for (int k0 = lane; k0 < nvec; k0 += 64 * CPB) {
-            u32x4 buf[CPB];
-#pragma unroll
-            for (int j = 0; j < CPB; ++j) buf[j] = src[k0 + 64 * j < nvec ? k0 + 64 * j : nvec - 1];
-            asm volatile("" : "+v"(buf[0]), "+v"(buf[1]));       // (both loads in flight before the first store: the scheduler otherwise pairs them load - store - load - store)
-#pragma unroll
-            for (int j = 0; j < CPB; ++j) if (k0 + 64 * j < nvec) dst[k0 + 64 * j] = buf[j];
-        }
-    }
-    // the new episode's window plane, straight from the slot (L2 hits next to the copy above.  Parking the plane in LDS was
-    // measured and dropped in round 3: any LDS at all makes k_consume's blocks queue behind the generator's waves for it)
-    uint8_t* vrow = vplane ? vplane + env * (int64_t)v_bytes(c) : nullptr;
-    if (vplane) {
-        const int nseg = v_nxo(c) * v_nyo(c) * 8;
-        constexpr int SGB = 4;
-        for (int s0 = lane; s0 < nseg; s0 += 64 * SGB) {
-            u32x4 seg[SGB];
-#pragma unroll
-            for (int j = 0; j < SGB; ++j) { const int sg = s0 + 64 * j < nseg ? s0 + 64 * j : nseg - 1; seg[j] = v_segment(c, nrec, sg >> 3, sg & 7, -1); }
-#pragma unroll
-            for (int j = 0; j < SGB; ++j) { const int sg = s0 + 64 * j; if (sg < nseg) *(u32x4*)(vrow + (sg >> 3) * VLINE + (sg & 7) * 16) = seg[j]; }
-        }
-    }
-    uint8_t* crow = cplane ? cplane + env * (int64_t)cpl_bytes(c) : nullptr;
-    if (crow) cpl_build_wave(c, nrec, crow, lane);
-    // the verifier's SoA view of the new program
-    if (lane < 8) vsets[(int64_t)lane * n + env] = pset;
-    if (lane == 8) vheads[env] = vh;
-    // first observation of the new episode, straight from the slot (identical bytes to the live copy)
-    observe_emit(c, nrec, h, e_view, obs_dst, lane);
-    if (lane == 0) {
-        uint64_t stale0 = 0;
-        uint32_t ce0 = E_EMPTY;
-        // PutNext*Carrying: the first observation above still shows the object on the grid (the reference builds
-        // it before handing the object to the agent, bonus_levels.py:821-829); now move it into the agent's hands.  In the
-        // window plane (and the front cache) its cell is empty from the start.
-        if (start_carry != NONE8) {
-            const int sx = nrec[c.off_pos + 2 * start_carry], sy = nrec[c.off_pos + 2 * start_carry + 1];
-            if (vplane) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the segment stores of every lane have landed; the patch goes over them
-                v_patch(c, vrow, sx, sy, E_EMPTY);
-            }
-            if (crow) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the row bytes of the other lanes)
-                crow[8 * sy + sx] = (uint8_t)E_EMPTY;
-                crow[CPL_PLANE + start_carry] = 0xFF;
-            }
-            if (e_index(c, sx, sy) == e_index(c, h.ax + dir_dx(h.dir), h.ay + dir_dy(h.dir))) fe0 = E_EMPTY;
-            ce0 = nrec[c.off_app + start_carry];
-            apply_start_carry(c, inplace ? nrec : recs + env * (int64_t)c.rec_bytes, h, stale0, start_carry);
-        }
-        if (vplane || crow) fcache[env] = (uint16_t)(fe0 | (ce0 << 8));
-        hots[env] = h;
-        stales[env] = stale0;
-        if (lsm_arr) lsm_arr[env] = 0;                  // fresh instruction objects: lastStepMatch = False (verifier.py:213-214)
-        dirs[env] = h.dir;
-        // window bookkeeping for the batched refill: first consumption in this window registers the env
-        if (pend == 0) first_slot[env] = (uint8_t)(inplace ? live_slot(slot, depth) : slot);
-        else atomicMax(win_meta, (uint32_t)(pend + 1));       // (rare: the env finished before in this window)
-        pending[env] = (uint8_t)(pend + 1);
-    }
-}
-
-// In-place layout: a finished env moves on to its next look-ahead slot, done by the env's OWN lane inside k_step (all the finished
-// lanes of a wave side by side: no per-env loop, no tail).  Everything it needs depends on the slot alone -- pose, program, window
-// bookkeeping and the new episode's first observation, which the generator wrote next to the level (computing it here, with the
-// step's own window pipeline, doubled the vector work of every wave that carries a finished env: measured, profiles/r04/
-// inplace_own_lane_observation_ab.jsonl) -- so it is ONE round trip, and it is issued the moment the lane knows its episode is over
-// (advance_load, right behind the step's own stores); advance_finish swaps the SoA state of the env and puts the observation into
-// the lane's LDS row.  Nothing here waits for another wave: the window keeps no list (see NWIN above).
-template <bool CP>
-struct AdvanceRegs {
-    u32x4 hv, tail /* Prog bytes 96..111: kind[4], root, n_a, n_b, strict, start_carry */, o[OBS_BLOCK / 16];
-    u32x4 cp[CP ? (CPL_PLANE + CPL_MAX_IDS) / 16 : 1];      // the next level's C plane row
-    uint64_t ps[8];
-    uint32_t pend;
-};
-template <bool CP>
-__device__ __forceinline__ void advance_load(const LevelCfg& c, int64_t env, int next /* hot.slot: the slot that becomes live */, int depth,
-                                             const uint8_t* ring, const Hot* __restrict__ next_hots, const uint8_t* __restrict__ next_obs,
-                                             const uint8_t* __restrict__ pending, AdvanceRegs<CP>& r) {
-    const int64_t at = ring_at(next, env, depth);
-    const uint8_t* nrec = ring + at * (int64_t)c.rec_bytes;
-    r.hv = *(const u32x4*)(next_hots + at);
-    const Prog* p = (const Prog*)(nrec + c.off_prog);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r.ps[k] = p->set[k >> 1][k & 1];
-    r.tail = *(const u32x4*)((const uint8_t*)p + 96);
-    r.pend = pending[env];
-    const u32x4* ob = (const u32x4*)(next_obs + at * OBS_SLOT);
-#pragma unroll
-    for (int k = 0; k < OBS_BLOCK / 16; ++k) r.o[k] = ob[k];
-    if constexpr (CP) {
-        const u32x4* cr = (const u32x4*)(next_obs + at * OBS_SLOT + CPL_OFF);
-#pragma unroll
-        for (int k = 0; k < (CPL_PLANE + CPL_MAX_IDS) / 16; ++k) r.cp[k] = cr[k];      // (the slot holds 96 bytes whatever the level's id count)
-    }
-}
-template <bool CP>
-__device__ __forceinline__ void advance_finish(const LevelCfg& c, int64_t n, int64_t env, int lane, int next, int depth, uint8_t* ring, const AdvanceRegs<CP>& r,
-                                               Hot* __restrict__ hots, uint64_t* __restrict__ stales, uint32_t* __restrict__ vheads, uint64_t* __restrict__ vsets,
-                                               uint8_t* __restrict__ pending, uint8_t* __restrict__ first_slot, uint32_t* __restrict__ win_meta,
-                                               uint8_t* __restrict__ s_rows, uint8_t* __restrict__ dirs, uint8_t* __restrict__ lsm_arr,
-                                               uint8_t* __restrict__ cplane, uint16_t* __restrict__ fcache) {
-    static_assert(sizeof(Prog) == 112 && offsetof(Prog, kind) == 96 && offsetof(Prog, start_carry) == 104, "Prog tail");
-    Hot h;
-    __builtin_memcpy(&h, &r.hv, sizeof(h));
-    h.slot = (uint8_t)(next + 1 == depth ? 0 : next + 1);
-    Prog pt;                                    // (only the tail fields are read below)
-    __builtin_memcpy((uint8_t*)&pt + 96, &r.tail, 16);
-    const uint32_t vh = vhead_pack(pt);
-    const int start_carry = pt.start_carry;
-    {
-        RowPacker rp(s_rows, lane);
-#pragma unroll
-        for (int j = 0; j < 37; ++j) rp.put(j, r.o[j >> 2][j & 3]);
-        rp.finish();
-    }
-    uint64_t stale0 = 0;
-    uint32_t ce0 = E_EMPTY;
-    if constexpr (CP) {
-        u32x4* crow = (u32x4*)(cplane + env * (int64_t)cpl_bytes(c));
-        const int nv = cpl_bytes(c) >> 4;
-#pragma unroll
-        for (int k = 0; k < (CPL_PLANE + CPL_MAX_IDS) / 16; ++k) if (k < nv) crow[k] = r.cp[k];
-    }
-    // PutNext*Carrying (consume_env): the first observation shows the object on the grid; now it is in the agent's hands
-    if (start_carry != NONE8) {
-        uint8_t* nrec = ring + ring_at(next, env, depth) * (int64_t)c.rec_bytes;
-        if constexpr (CP) {
-            const int sx = nrec[c.off_pos + 2 * start_carry], sy = nrec[c.off_pos + 2 * start_carry + 1];
-            ce0 = nrec[c.off_app + start_carry];
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the row above has landed; the patch goes over it
-            uint8_t* crow = cplane + env * (int64_t)cpl_bytes(c);
-            crow[8 * sy + sx] = (uint8_t)E_EMPTY;
-            crow[CPL_PLANE + start_carry] = 0xFF;
-        }
-        apply_start_carry(c, nrec, h, stale0, start_carry);
-    }
-    if constexpr (CP) fcache[env] = (uint16_t)(E_EMPTY | (ce0 << 8));
-#pragma unroll
-    for (int k = 0; k < 8; ++k) vsets[(int64_t)k * n + env] = r.ps[k];
-    vheads[env] = vh;
-    hots[env] = h;
-    stales[env] = stale0;
-    if (lsm_arr) lsm_arr[env] = 0;
-    dirs[env] = h.dir;
-    if (r.pend == 0) first_slot[env] = (uint8_t)live_slot(next, depth);      // the slot this env's finished episode lived in: free for the refill
-    else atomicMax(win_meta, r.pend + 1u);
-    pending[env] = (uint8_t)(r.pend + 1);
-}
-
-// VP: the window comes from the env's V-plane line (ONE 128-byte line per step) and the transition's inputs -- the
-// appearance of the front cell and of the carried object -- from the 2-byte cache the previous step left (`fcache`), so a
-// plain move / turn touches no other record line; without VP both come out of the record (round 2's path: 2-3 lines for
-// the window + the lines of the front cell's id and the carried object's appearance).
-// FUSE: a wave whose envs finished consumes their look-ahead slots ITSELF (consume_env for every set bit of the wave's ballot,
-// the new episode's first observation straight into the block's LDS rows), instead of listing them for a k_consume launch.
-// `fuse` carries what k_consume's arguments carried.
-// The step's own tap (bbai_step_tapped): the listed envs' outputs of THIS step into caller-owned log rows, written by the stepping lanes
-// themselves -- what a bbai_tap_ids launch behind the step would copy, without the launch (k_tap is 3 us + a dependent-launch gap: a quarter
-// of a 65 536-env step).  mask[block] bit l = env 64 block + l is listed; its log row = perm[rank0[block] + listed envs below it in the block].
-struct TapArgs {
-    const unsigned long long* mask; const uint32_t* rank0; const int32_t* perm;
-    uint8_t* image_out; uint8_t* dir_out; double* rew_out; uint8_t* done_out;
-    int64_t count;        // listed envs = log rows per tick (a launch of several ticks moves on by one row set per tick)
-};
-struct FuseArgs {
-    uint8_t* next_recs; const Hot* next_hots; const uint8_t* next_obs; int depth;
-    uint8_t* pending; uint8_t* first_slot; uint32_t* win_meta; unsigned long long* totals;
-};
-// step_body: ONE tick of a 64-env block (the whole of k_step; k_step_ticks calls it once per tick).  `s_obs`: the block's LDS rows.
-template <bool VP, int FUSE /* 0: finished envs listed for k_consume; 1: consumed by the stepping wave (consume_env); 3: in-place layout (advance_load / advance_finish) */,
-          bool CP = false /* in-place small single rooms: pose-independent C plane row instead of the record's planes (bbai_types.hpp) */>
-__device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t* __restrict__ recs,
-                                                     Hot* __restrict__ hots, uint64_t* __restrict__ stales,
-                                                     uint32_t* vheads, uint64_t* vsets /* read by every lane, WRITTEN for the envs the wave moves on (FUSE): no restrict */,
-                                                     const uint8_t* __restrict__ actions, uint8_t* image /* read (frozen envs re-emit) AND written: no restrict */,
-                                                     uint8_t* __restrict__ dirs, float* __restrict__ rewards,
-                                                     double* __restrict__ rewards64, uint8_t* __restrict__ dones, int auto_reset,
-                                                     int32_t* __restrict__ reset_list, uint8_t* __restrict__ reset_slot, uint32_t* __restrict__ counters,
-                                                     int prio, uint8_t* __restrict__ vplane, uint16_t* __restrict__ fcache,
-                                                     uint8_t* __restrict__ lsm_arr /* NULL, or the done-action mode's per-env bits */,
-                                                     int enum_done /* done-action mode: this step's `done` actions are the enum member (bbai_step.hpp verify_side) */,
-                                                     FuseArgs fuse, int64_t block0 /* first 64-env block of this launch (bbai_step_render steps the batch in two halves) */,
-                                                     uint8_t* __restrict__ cplane /* CP: [n][cpl_bytes] */, const TapArgs& tap /* mask == NULL: none */,
-                                                     uint8_t* const s_obs, const int lane /* threadIdx.x */, const int blk_x /* blockIdx.x */) {
-    static_assert(!CP || (FUSE == 3 && !VP), "the C plane belongs to the in-place layout");
-    uint8_t* const s_rows = s_obs + ROWS_FRONT;
-    if (prio) __builtin_amdgcn_s_setprio(3);            // the look-ahead generator's waves share the CUs: issue ours first
-    const int64_t env0 = ((int64_t)blk_x + block0) * STEP_BLOCK;
-    const int64_t env = env0 + lane;
-    const bool active = env < n;
-    bool want_reset = false;
-    bool frozen_copy = false; // CP: a frozen lane's row copy, deferred until every lane has read its parked plane (below)
-    int my_slot = 0;
-    AdvanceRegs<CP> adv;      // (in-place layout: the finished lanes' next-slot loads)
-    if (active) {
-        // everything the step needs from the SoA arrays in ONE memory round trip, before the frozen test (the loads the
-        // branch would otherwise delay are a second round trip on every step's critical path)
-        u32x4 hv = *(const u32x4*)(hots + env);
-        uint64_t stale = stales[env];
-        VProg vp; vp.bind(vheads[env], vsets + env, n);
-        int action = actions[env];
-        uint32_t fc = (VP || CP) ? (uint32_t)fcache[env] : 0u;
-        Lsm lsm = {lsm_arr ? (uint32_t)lsm_arr[env] : 0u, lsm_arr != nullptr};
-        // CP: the env's whole grid + object positions come with the SoA state -- nothing below depends on a second memory round trip
-        u32x4 pv[4] = {}, iv[2] = {};
-        uint8_t* crow = nullptr;
-        if constexpr (CP) {
-            crow = cplane + env * (int64_t)cpl_bytes(c);
-            const u32x4* cr = (const u32x4*)crow;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pv[k] = cr[k];
-            iv[0] = cr[4];
-            const u32x4 none = {~0u, ~0u, ~0u, ~0u};
-            iv[1] = none;
-            if (cpl_ids(c) > 16) iv[1] = cr[5];
-            asm volatile("" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(iv[0]), "+v"(iv[1]));
-        }
-        // (the empty asm pins the loaded values here: the compiler would otherwise sink the loads into the branch)
-        asm volatile("" : "+v"(hv), "+v"(stale), "+v"(vp.head), "+v"(vp.set00), "+v"(action), "+v"(fc));
-        Hot h;
-        __builtin_memcpy(&h, &hv, sizeof(h));
-        my_slot = h.slot;
-        uint8_t* rec = FUSE == 3 ? fuse.next_recs + ring_at(live_slot(h.slot, fuse.depth), env, fuse.depth) * (int64_t)c.rec_bytes : recs + env * (int64_t)c.rec_bytes;
-        if (!h.frozen) {
-            double reward = 0.0;
-            const EnvRef r = env_ref(c, rec, vp);
-            uint8_t* vrow = VP ? vplane + env * (int64_t)v_bytes(c) : nullptr;
-            int fe, ce;
-            // CP: the lane's plane parked in LDS (8 rows x 8 bytes at a 72-byte lane pitch, inside the block's obs-row area: every lane's reads of
-            // it precede, in the one wave's program order, every lane's row writes at the end of the step), for the per-lane row / cell addressing
-            uint8_t* const pl = s_obs + lane * 72;
-            if constexpr (CP) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    *(uint2*)(pl + 16 * k) = make_uint2(pv[k][0], pv[k][1]);
-                    *(uint2*)(pl + 16 * k + 8) = make_uint2(pv[k][2], pv[k][3]);
-                }
-                fe = pl[8 * (h.ay + dir_dy(h.dir)) + h.ax + dir_dx(h.dir)];
-                ce = (int)(fc >> 8);
-            } else if (VP) {
-                fe = (int)(fc & 0xFFu); ce = (int)(fc >> 8);
-            } else {
-                fe = r.E[e_index(c, h.ax + dir_dx(h.dir), h.ay + dir_dy(h.dir))];
-                ce = h.carry != NONE8 ? r.app[h.carry] : (int)E_EMPTY;
-            }
-            if (action != A_RESET_ENV) apply_pose(h, action, fe);
-            // the 7x7 window of the pose after the action.  Grid.slice extents (get_view_exts): its top-left world cell
-            const int dir = h.dir;
-            const int txm = h.ax + MARGIN + (dir == 0 ? 0 : dir == 2 ? -6 : -3);
-            const int tym = h.ay + MARGIN + (dir == 1 ? 0 : dir == 3 ? -6 : -3);
-            uint32_t wd[3 * VIEW];
-            uint32_t wl[VIEW], wh[VIEW];
-            if constexpr (CP) {
-                window_rows_cpl(pl, c.H, h.ax, h.ay, dir, wl, wh);
-            } else if (VP) {
-                const uint8_t* line = vrow + ((tym >> 1) * v_nxo(c) + (txm >> 3)) * VLINE + (tym & 1) * 16 + (txm & 4);
-                window_fetch((const uint32_t*)line, 4, wd);
-            } else {
-                window_fetch((const uint32_t*)(rec + ((tym * c.ES + txm) & ~3)), c.ES >> 2, wd);     // (ES is a multiple of 4)
-            }
-            // the id-plane entry of the front cell, fetched WITH the window: the verifier's common question ("is the object
-            // in front of me one of the described ones") and the object actions then need no further memory round trip
-            // (BBAI_PREFETCH_ID=0: read lazily, as rounds 1-2 did -- one more line per env-step, one round trip less)
-            int idf = -1;
-#if BBAI_PREFETCH_ID
-            idf = r.I[i_index(c, h.ax + dir_dx(dir), h.ay + dir_dy(dir))];
-#endif
-            const int fpos = (h.ay + dir_dy(dir)) << 3 | (h.ax + dir_dx(dir));      // CP: the front cell in C plane coordinates
-            if constexpr (CP) {
-                const uint32_t idw[8] = {iv[0][0], iv[0][1], iv[0][2], iv[0][3], iv[1][0], iv[1][1], iv[1][2], iv[1][3]};
-                idf = cid_lookup(idw, 8, fpos);                 // (what r.I would say about an object there; 0 = none)
-            }
-            // pickup / drop / toggle, while the window is on its way
-            int nfe = -1;
-            if (action != A_RESET_ENV) {
-                int nid = -1;
-                nfe = apply_objects(c, r, h, stale, action, fe, ce, idf, &nid);
-                if (VP && nfe >= 0) v_patch(c, vrow, h.ax + dir_dx(dir), h.ay + dir_dy(dir), nfe);
-                if constexpr (CP) {          // the env's C plane row follows the record: the cell, and who stands (or no longer stands) on it
-                    if (nfe >= 0) crow[fpos] = (uint8_t)nfe;
-                    if (nid >= 0) {
-                        if (idf >= 2) crow[CPL_PLANE + idf - 2] = 0xFF;              // picked up / an opened box
-                        if (nid >= 2) crow[CPL_PLANE + nid - 2] = (uint8_t)fpos;     // dropped / a box's content
-                    }
-                }
-                if (idf >= 0 && nid >= 0) idf = nid;
-            }
-            int fe2;
-            uint32_t cp[13];
-#if BBAI_VIEW_LDS
-            uint32_t vis[VIEW];
-            view_cells(wd, txm & 3, dir, (uint32_t)ce, nfe, s_rows + row_scratch(lane), cp, vis, fe2);
-#else
-            if constexpr (CP) view_rows_perm(wl, wh, dir, (uint32_t)ce, nfe, cp, fe2);
-            else view_cells_perm(wd, txm & 3, dir, (uint32_t)ce, nfe, cp, fe2);       // (bbai_view.hpp: rotation, occlusion and masking in registers)
-#endif
-            // "env.reset() for THIS env, now" (A_RESET_ENV, bbai_step.hpp): the episode ends with done = 1, reward = 0
-            const bool done = action == A_RESET_ENV ? true : finish_step(c, r, h, stale, action, fe2, reward, lsm, idf, enum_done != 0);
-            if (lsm_arr) lsm_arr[env] = (uint8_t)lsm.bits;
-            if (done && !auto_reset) h.frozen = 1;
-            want_reset = done && auto_reset;
-            hots[env] = h;
-            stales[env] = stale;
-            if (VP || CP) fcache[env] = (uint16_t)((uint32_t)fe2 | ((uint32_t)ce << 8));
-            rewards[env] = (float)reward;
-            if (rewards64) rewards64[env] = reward;        // the reference's Python float, bit for bit (levelgen.py:59-61)
-            dones[env] = done ? 1 : 0;
-            dirs[env] = h.dir;
-#if BBAI_VIEW_LDS
-            encode_view(cp, vis, RowPacker(s_rows, lane));
-#else
-            encode_cells(cp, RowPacker(s_rows, lane));
-#endif
-        }
-        // frozen envs keep re-emitting their last outputs: copy them through LDS unchanged
-        else {
-            if (h.frozen == 2 && auto_reset) {      // level the generator gave up on (last-resort guard): skip to the next one
-                rewards[env] = 0.0f;
-                if (rewards64) rewards64[env] = 0.0;
-                dones[env] = 1;
-                want_reset = true;
-            }
-            if constexpr (CP) {
-                frozen_copy = true;
-            } else {
-                const uint8_t* src = image + env * OBS_BYTES;
-                for (int b = 0; b < OBS_BYTES; ++b) s_rows[lane * OBS_BYTES + b] = src[b];
-            }
-        }
-        if constexpr (FUSE == 3) { if (want_reset) advance_load<CP>(c, env, my_slot, fuse.depth, fuse.next_recs, fuse.next_hots, fuse.next_obs, fuse.pending, adv); }
-    }
-    if constexpr (CP) {
-        // The stepping lanes parked their planes INSIDE the obs-row area (at a 72-byte pitch: over other lanes' rows).  Their own rows are written
-        // after every plane read by the wave's program order; a frozen lane's row copy sits in the other arm of a branch, which the compiler may
-        // emit FIRST -- the parked planes then went over rows already copied (caught by test_manyenvs_freeze).  So it waits here, behind a
-        // convergent fence that no arm of that branch can cross.
-        __builtin_amdgcn_wave_barrier();
-        if (frozen_copy) {
-            const uint8_t* src = image + env * OBS_BYTES;
-            for (int b = 0; b < OBS_BYTES; ++b) s_rows[lane * OBS_BYTES + b] = src[b];
-        }
-    }
-    // finished envs.  Unfused: compacted into the reset list for k_consume (one returning atomic per wave).  Fused / in-place: counted
-    // (one fire-and-forget add to this block's shard of the total) and moved on by this wave itself.
-    {
-        unsigned long long bal = __ballot(want_reset);
-        if (bal) {
-            const int leader = __ffsll((long long)bal) - 1;
-            if constexpr (FUSE == 0) {
-                uint32_t basei = 0;
-                if (lane == leader) basei = atomicAdd(&counters[0], (uint32_t)__popcll(bal));
-                basei = __shfl(basei, leader);
-                if (want_reset) {
-                    const uint32_t at = basei + __popcll(bal & ((1ull << lane) - 1));
-                    reset_list[at] = (int32_t)env;
-                    reset_slot[at] = (uint8_t)my_slot;
-                }
-            } else if constexpr (FUSE == 3) {
-                // in-place layout: every finished lane moves its own env on (its stores to its own SoA entries stay in program order)
-                if (lane == leader) count_resets(fuse.totals, (unsigned int)__popcll(bal), (unsigned int)blk_x);
-                if (want_reset)
-                    advance_finish<CP>(c, n, env, lane, my_slot, fuse.depth, fuse.next_recs, adv, hots, stales, vheads, vsets, fuse.pending, fuse.first_slot,
-                                       fuse.win_meta, s_rows, dirs, lsm_arr, cplane, fcache);
-            } else {
-                // Everything this wave stored to the records, window planes and SoA entries of these envs must have landed
-                // before other lanes overwrite them (a terminal pickup patches the record the consume is about to replace).
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == leader) count_resets(fuse.totals, (unsigned int)__popcll(bal), (unsigned int)blk_x);
-                while (bal) {
-                    const int src = __ffsll((long long)bal) - 1;
-                    bal &= bal - 1;
-                    const int slot = __shfl(my_slot, src);
-                    // (the new episode's first observation goes over the finished env's row; LDS traffic of the one wave stays in program order)
-                    consume_env(c, n, env0 + src, slot, lane, recs, hots, stales, fuse.next_recs, fuse.next_hots, vheads, vsets,
-                                fuse.depth, fuse.pending, fuse.first_slot, fuse.win_meta, s_rows + src * OBS_BYTES, dirs,
-                                VP ? vplane : nullptr, fcache, lsm_arr);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // the block's contiguous obs span leaves as it lies in LDS: 16 bytes per lane per store (64 x 147 B = 588 x 16 B; the
-    // span of every full block starts 16-byte aligned in the output).  The last, partial block ends with a byte tail.
-    const int64_t nb = n - env0 < STEP_BLOCK ? n - env0 : STEP_BLOCK;      // envs in this block
-    const int total = (int)nb * OBS_BYTES;
-    uint8_t* out = image + env0 * OBS_BYTES;
-    {
-        // (a caller's buffer that is not 16-byte aligned -- a row of a [T][n][147] history with odd n -- gets dwords or bytes)
-        const int al = (int)((uintptr_t)out & 15);
-        int done_bytes = 0;
-        if (al == 0) {
-            const int nvec = total >> 4;
-            const u32x4* s128 = (const u32x4*)s_rows;
-            for (int v = lane; v < nvec; v += STEP_BLOCK) ((u32x4*)out)[v] = s128[v];     // (non-temporal here: measured, no effect -- profiles/r03/NOTES.md)
-            done_bytes = nvec << 4;
-        } else if ((al & 3) == 0) {
-            const int ndw = total >> 2;
-            const uint32_t* s32 = (const uint32_t*)s_rows;
-            for (int d = lane; d < ndw; d += STEP_BLOCK) ((uint32_t*)out)[d] = s32[d];
-            done_bytes = ndw << 2;
-        }
-        for (int b = done_bytes + lane; b < total; b += STEP_BLOCK) out[b] = s_rows[b];
-    }
-    // the step's own tap: a listed env's row out of LDS (for an env that finished: already its new episode's first observation), its direction /
-    // reward / done as this wave stored them (agent-scope loads: the direction of a consumed env was stored by another lane)
-    if (tap.mask) {
-        const int64_t blk = (int64_t)blk_x + block0;
-        const unsigned long long tm = tap.mask[blk];
-        if (active && (tm >> lane & 1ull)) {
-            const int64_t row = (int64_t)tap.perm[tap.rank0[blk] + (uint32_t)__popcll(tm & ((1ull << lane) - 1ull))];
-            uint8_t* o = tap.image_out + row * OBS_BYTES;
-            const uint8_t* srow = s_rows + lane * OBS_BYTES;
-            for (int b = 0; b < OBS_BYTES; ++b) o[b] = srow[b];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            tap.dir_out[row] = __hip_atomic_load(dirs + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tap.done_out[row] = __hip_atomic_load(dones + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tap.rew_out[row] = __hip_atomic_load(rewards64 + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-// The dirty cells of a step whose render is a delta render of the registered target (render_launch: k_render_dstore).  k_step's tail, after
-// step_body has stored the block's rows: lanes over (env, cell) of the block's 64 rows, 16 cells per lane and chunk -- the chunk's 16 shadow
-// bytes in one coalesced 16-byte load, its 48 encoding bytes in three 16-byte LDS reads (a row is 49 cells at the output pitch of 147 =
-// 3 x 49: cell b of the block is LDS bytes [3 b, 3 b + 3)) -- the new tile id of every cell (the same s_lut lookup as k_render, the agent's
-// table for AGENT_CELL), the changed ones written back to the shadow (the chunk whole, where one differs), and per env a 64-bit dirty mask
-// (bit = cell) into `dmask`: gathered by LDS atomics in the first 512 bytes of the row area, which nothing reads any more.
-constexpr int CELLS = VIEW * VIEW;
-constexpr int AGENT_CELL = 3 * VIEW + 6;                        // the agent's own cell of the view: (3, 6) (tile_id, bbai_render.hpp)
-static_assert(AGENT_CELL == 3 * VIEW + 6, "the agent stands in the middle of the view's last row");
-constexpr int DIRTY_CHUNKS = (STEP_BLOCK * CELLS / 16 + STEP_BLOCK - 1) / STEP_BLOCK;      // 16-byte shadow chunks per lane: 196 per block -> 4
-static_assert(STEP_BLOCK * CELLS % 16 == 0 && OBS_BYTES == 3 * CELLS, "a block's shadow rows are whole 16-byte chunks; a row is 3 bytes per cell");
-__device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __restrict__ shadow /* [n][49] */, uint64_t* __restrict__ dmask /* [n] */,
-                                           const uint8_t* __restrict__ lut, uint8_t* const s_rows, uint8_t* const s_lut, const int lane) {
-    const int nb = n - env0 < STEP_BLOCK ? (int)(n - env0) : STEP_BLOCK;
-    const int nbytes = nb * CELLS;
-    uint8_t* const sh = shadow + env0 * CELLS;                   // (16-byte aligned: env0 is a multiple of 64)
-    const uint2 lv = ((const uint2*)lut)[lane];
-    uint32_t old[DIRTY_CHUNKS][4];
-#pragma unroll
-    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
-        const int v = lane + k * STEP_BLOCK;
-        old[k][0] = old[k][1] = old[k][2] = old[k][3] = 0;
-        if (16 * v + 16 <= nbytes) {
-            const u32x4 w = ((const u32x4*)sh)[v];
-            old[k][0] = w[0]; old[k][1] = w[1]; old[k][2] = w[2]; old[k][3] = w[3];
-        } else {                                                 // (the last, partial block's last chunk)
-            for (int i = 0; i < 16 && 16 * v + i < nbytes; ++i) old[k][i >> 2] |= (uint32_t)sh[16 * v + i] << (8 * (i & 3));
-        }
-    }
-    *(uint2*)(s_lut + 8 * lane) = lv;
-    __syncthreads();                                             // (one wave: the lut's LDS writes before its reads)
-    uint64_t ma[DIRTY_CHUNKS], mb[DIRTY_CHUNKS];                 // the chunk's dirty cells in its first env, and in the next one
-#pragma unroll
-    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
-        const int v = lane + k * STEP_BLOCK;
-        ma[k] = mb[k] = 0;
-        if (16 * v >= nbytes) continue;
-        const u32x4* enc = (const u32x4*)(s_rows + 48 * v);
-        const u32x4 q0 = enc[0], q1 = enc[1], q2 = enc[2];
-        const uint32_t ew[12] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2[0], q2[1], q2[2], q2[3]};
-        const int ea = 16 * v / CELLS;
-        int cell = 16 * v - ea * CELLS;
-        bool second = false;
-        uint32_t nw[4] = {0, 0, 0, 0};
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            if (16 * v + i < nbytes) {
-                const int o0 = (ew[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 0xFF;
-                const int o1 = (ew[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 0xFF;
-                const int o2 = (ew[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 0xFF;
-                const int key = o0 | (o1 << 3) | (o2 << 6);
-                const uint32_t id = s_lut[(cell == AGENT_CELL ? 256 : 0) + key];
-                nw[i >> 2] |= id << (8 * (i & 3));
-                if (id != ((old[k][i >> 2] >> (8 * (i & 3))) & 0xFFu)) {
-                    any = true;
-                    if (second) mb[k] |= 1ull << cell; else ma[k] |= 1ull << cell;
-                }
-            }
-            if (++cell == CELLS) { cell = 0; second = true; }
-        }
-        if (any) {
-            if (16 * v + 16 <= nbytes) { u32x4 w = {nw[0], nw[1], nw[2], nw[3]}; ((u32x4*)sh)[v] = w; }
-            else for (int i = 0; i < 16 && 16 * v + i < nbytes; ++i) sh[16 * v + i] = (uint8_t)(nw[i >> 2] >> (8 * (i & 3)));
-        }
-    }
-    __syncthreads();                                             // every lane has read its rows: their first 512 bytes take the masks
-    unsigned long long* const s_dm = (unsigned long long*)s_rows;
-    s_dm[lane] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < DIRTY_CHUNKS; ++k) {
-        const int ea = 16 * (lane + k * STEP_BLOCK) / CELLS;
-        if (ma[k]) atomicOr(s_dm + ea, (unsigned long long)ma[k]);
-        if (mb[k]) atomicOr(s_dm + ea + 1, (unsigned long long)mb[k]);
-    }
-    __syncthreads();
-    if (lane < nb) dmask[env0 + lane] = s_dm[lane];
-}
-
-// What a step launch is given: the kernels' one argument (the kernarg segment IS this struct).
-struct StepArgs {
-    LevelCfg c; int64_t n; uint8_t* recs; Hot* hots; uint64_t* stales; uint32_t* vheads; uint64_t* vsets; const uint8_t* actions; uint8_t* image; uint8_t* dirs;
-    float* rewards; double* rewards64; uint8_t* dones; int auto_reset; int32_t* reset_list; uint8_t* reset_slot; uint32_t* counters; int prio; uint8_t* vplane;
-    uint16_t* fcache; uint8_t* lsm_arr; int enum_done; FuseArgs fuse; int64_t block0; uint8_t* cplane; TapArgs tap;
-    int ticks;            // k_step_ticks: steps this launch takes; tick t reads actions + t n and logs into the tap rows t * tap.count further on
-    uint8_t* dshadow; uint64_t* dmask; const uint8_t* lut;     // k_step: dshadow != NULL = the dirty cells of this step for its delta render (step_dirty)
-};
-template <bool VP, int FUSE, bool CP = false>
-__global__ __launch_bounds__(STEP_BLOCK, BBAI_STEP_WAVES) void k_step(StepArgs a) {
-    // the block's observation rows at the OUTPUT pitch of 147 bytes (bbai_step.hpp RowPacker), 16 bytes of front padding
-    __shared__ __attribute__((aligned(16))) uint8_t s_obs[ROWS_FRONT + STEP_BLOCK * OBS_BYTES + 16];
-    __shared__ __attribute__((aligned(8))) uint8_t s_lut[512];      // step_dirty (9 952 bytes in all: 16 blocks = 16 waves still fit a CU's 160 KiB)
-    step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset, a.reset_list,
-                            a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.fuse, a.block0, a.cplane, a.tap, s_obs, (int)threadIdx.x, (int)blockIdx.x);
-    if (a.dshadow) step_dirty(a.n, ((int64_t)blockIdx.x + a.block0) * STEP_BLOCK, a.dshadow, a.dmask, a.lut, s_obs + ROWS_FRONT, s_lut, (int)threadIdx.x);
-}
-// Several ticks in one launch (bbai_rollout, open-loop actions): an env's step touches only its own state, its block's LDS rows and -- for a
-// finished env -- look-ahead slots the window gate in front of the launch has vouched for, so a block walks through its ticks on its own, with
-// no launch boundary (and no dependent-launch gap: 4-5 us, a third of a 65 536-env step) in between.  Everything a tick reads of the previous one
-// was stored by THIS wave: its vector-memory operations stay in program order.
-// Every tick reads its arguments from the kernarg segment AGAIN, through a pointer the compiler cannot see through: left to itself it hoists
-// what the ticks share (fifty LevelCfg words, thirty pointers and all that derives from them) out of the loop and keeps it in registers across
-// the body -- 251 VGPRs against 93, two waves per SIMD against five.
-typedef const StepArgs __attribute__((address_space(4))) * StepArgsPtr;
-// ... and the register budget is the four waves per SIMD the one-tick kernels of the default paths have (115-117 VGPRs): the constants the
-// loop optimiser still parks in registers in front of the loop are rematerialised or, a handful, spilled (2-7 VGPRs: kernel_resources.json).
-template <bool VP, int FUSE, bool CP = false>
-__global__ __launch_bounds__(STEP_BLOCK, 4) void k_step_ticks(StepArgs a_) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_obs[ROWS_FRONT + STEP_BLOCK * OBS_BYTES + 16];
-    const int ticks = a_.ticks;
-    for (int tick = 0; tick < ticks; ++tick) {
-        StepArgsPtr ap = (StepArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-        int t = tick, lane = (int)threadIdx.x, blk_x = (int)blockIdx.x;        // (the lane and block arithmetic likewise: re-derived per tick)
-        asm volatile("" : "+s"(ap), "+s"(t), "+v"(lane), "+s"(blk_x));
-        const StepArgs a = *(const StepArgs*)ap;          // (InferAddressSpaces turns these back into scalar loads of the constant segment)
-        TapArgs tap = a.tap;
-        tap.image_out += (int64_t)t * tap.count * OBS_BYTES; tap.dir_out += (int64_t)t * tap.count; tap.rew_out += (int64_t)t * tap.count; tap.done_out += (int64_t)t * tap.count;
-        step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions + (int64_t)t * a.n, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset,
-                                a.reset_list, a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.fuse, a.block0, a.cplane, tap, s_obs, lane, blk_x);
-        __syncthreads();        // (one wave per block: orders this tick's LDS reads before the next one's writes for the compiler)
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_pregen / k_consume : look-ahead level generation (one wavefront generates one env's levels)
-// ------------------------------------------------------------------------------------------
-// One env per group of G lanes, 64 / G envs per wavefront (bbai_gen.hpp "Execution model").  sync() orders the group's LDS
-// accesses: it is reached under divergent control flow (the groups of a wave are in different places of the generator),
-// so it is a wave-local fence, never a workgroup barrier -- the workgroup is one wave.
-// (GroupCtx<G>: bbai_kernels.hpp)
-
-// (Lane = level -- GroupCtx<1>: the same templates with a one-lane context, working set in per-lane global memory, MT19937 state advanced in
-// place -- was built and measured in round 5 (profiles/r05/NOTES.md): 86-95 VGPRs, but every access to the working set becomes a global
-// round trip: bulk fill 2 x SLOWER (PickupLoc 7.4 -> 14.2 ns per level, GoTo 35 -> 82), in the step loop 2-7 x.  Removed.)
-// The look-ahead generator.  A workgroup is ONE wave carrying 64 / G envs; every group walks its share of the window's `pending`
-// bytes on its own: fetch an env that has levels pending, load its MT19937 state into the
-// group's LDS block, then one ATTEMPT of the generator's rejection loop per trip of the main loop (Gen::attempt) -- a
-// group whose attempt was accepted writes the level out and goes on to its next level / env while its neighbours retry,
-// so the wave only idles lanes inside an attempt, never across attempts.
-// Work list: the window's finished envs as SHARDS dense sub-lists (k_compact); entry k of their concatenation is found through the
-// prefix of the sub-counts (64 words in LDS, a six-step search per entry: once per level, i.e. per ~50-300 us of work); groups stride
-// over the entries, so every group gets the same number of envs to within one.  `dense` (bbai_seed's first fill): every env, no list.
-// Minimum waves per SIMD the generator's register allocation has to allow.  4 (<= 128 VGPRs) instead of the 3 the compiler
-// settles on by itself (131-135 VGPRs at two envs per wave): PickupLoc 262 144 envs 0.0939 -> 0.0877 ms per step, the GoTo family
-// already fits (profiles/r04/pregen_waves_per_simd_ab.jsonl).  The bonus family would spill (167 VGPRs) and four envs per wave
-// need 200: those keep 2.
-#ifndef BBAI_PREGEN_WAVES
-#define BBAI_PREGEN_WAVES 4
-#endif
-template <int KIND, int G, bool OBS /* in-place layout: the level's first observation is written next to it */>
-__global__ __launch_bounds__(64, (KIND == K_BONUS || G == 16) ? 2 : BBAI_PREGEN_WAVES) void k_pregen(LevelCfg c, int64_t n, uint8_t* __restrict__ next_recs,
-                                                  Hot* __restrict__ next_hots, uint32_t* __restrict__ mts,
-                                                  int32_t* __restrict__ mtis,
-                                                  const int32_t* __restrict__ gen_list, const uint32_t* __restrict__ gen_count /* NULL: dense -- every env, the whole grid works */,
-                                                  int depth,
-                                                  uint8_t* __restrict__ pending, const uint8_t* __restrict__ first_slot,
-                                                  unsigned long long* __restrict__ gen_failures, int min_groups, int per_group /* list entries a working group should get */,
-                                                  uint8_t* __restrict__ next_obs /* in-place layout: [D][n][OBS_SLOT], else NULL */) {
-    constexpr int NG = 64 / G;
-    typedef GroupCtx<G> Ctx;
-    const Ctx ctx;
-    __shared__ GenWork ws[NG];
-    __shared__ uint32_t s_mt[NG][MT_N + MT_CH];      // the env's MT19937 state + the generator's chunk of tempered outputs (bbai_gen.hpp MT_CH)
-    GenWork& w = ws[threadIdx.x / G];
-    const int lane = ctx.lane();
-    // the refill list: prefix of the sub-list lengths (one word per lane, a wave scan, parked in LDS for the groups' searches)
-    __shared__ uint32_t s_start[SHARDS + 1];
-    int64_t count = n;
-    const int64_t cap = gen_sublist_cap(n);
-    if (gen_count) {
-        uint32_t c = gen_count[threadIdx.x * GEN_COUNT_U32], incl = c;            // (SHARDS == 64 == the block)
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if ((int)threadIdx.x >= o) incl += t; }
-        s_start[threadIdx.x + 1] = incl;
-        if (threadIdx.x == 0) s_start[0] = 0;
-        __syncthreads();
-        count = (int64_t)s_start[SHARDS];
-    }
-    // How many lane groups WORK on a window's refill (single rooms): the grid is sized for the worst case (every env finished on every
-    // tick), the list usually holds a fraction of that, and every resident generator wave holds registers and LDS that the step kernels'
-    // workgroups queue for -- but a refill that takes as long as a window paces the whole step stream (k_gate).  active = entries /
-    // per_group, at least `min_groups`, at most the grid; surplus blocks leave at once.  Round 4 (k_step + k_consume, 25 + 15 us per
-    // step at 65 536 envs) found entries / 32 and >= 2 048 groups best.  Round 5, with k_step at 16 us, no second launch and the
-    // stream free to run ahead of the refills, the SAME sweep says: more groups, shorter refills (profiles/r05/pregen_sizing_sweep.jsonl,
-    // ms per step): GoToLocal 65 536 envs 0.0319 at 2 048 groups, 0.0205 at 4 096, 0.0179 at 6 144, 0.0199 at 8 192, 0.0206 with the whole grid;
-    // GoToLocal 32 768: 0.0181 / 0.0122 / 0.0127 at 2 048 / 4 096 / 8 192; PickupLoc 262 144: 0.0755 at entries / 32, 0.067 at / 16, 0.059-0.063
-    // at / 12 ... / 4; GoToLocal 262 144: 0.0706 / 0.0644 / 0.0618 / 0.0655 at / 32, 16, 8, 4; PickupLoc 524 288: 0.134 / 0.121 / 0.124 / 0.132.
-    // Shipped: entries / 12, at least 6 144 groups.
-    int64_t stride = (int64_t)gridDim.x * NG;
-    if (gen_count && min_groups > 0) {
-        int64_t active = count / per_group;
-        active = active < min_groups ? min_groups : active;
-        active = (active + NG - 1) / NG * NG;                   // whole blocks: every group of a block that stays has its own residue
-        stride = active < stride ? active : stride;
-    }
-    int64_t it = (int64_t)blockIdx.x * NG + threadIdx.x / G;
-    if ((int64_t)blockIdx.x * NG >= stride) return;             // (whole blocks only: the groups of a wave stay together)
-    // the group's current env
-    bool have = false;
-    int64_t env = 0;
-    int cnt = 0, done_levels = 0, slot = 0, mti = 0, last_locked = -1, attempts = 0;
-    bool dirty = false;           // the env's state words were regenerated (a twist) since they were loaded: only then do they go back
-    for (;;) {
-        if (!have) {
-            while (it < count) {
-                int64_t cand = it;
-                if (gen_count) {
-                    // entry `it` of the concatenated sub-lists: the sub-list j with s_start[j] <= it < s_start[j + 1]
-                    int j = 0;
-#pragma unroll
-                    for (int o = SHARDS / 2; o; o >>= 1) if ((int64_t)s_start[j + o] <= it) j += o;
-                    cand = (int64_t)gen_list[(int64_t)j * cap + (it - (int64_t)s_start[j])];
-                }
-                it += stride;
-                const int pc = pending[cand];            // levels to generate for this env (consecutive ring slots)
-                if (pc == 0) continue;                   // (dense: env was not consumed in this window)
-                env = cand; cnt = pc; have = true;
-                break;
-            }
-            if (have) {
-                // the env's generator state: all of its loads in flight together (MT19937 words, position, first slot) -- as a
-                // load - store loop this was five dependent round trips before the first draw
-                const uint32_t* mt = mts + env * MT_N;
-                constexpr int MTQ = (MT_N + G - 1) / G;
-                uint32_t mtw[MTQ];
-#pragma unroll
-                for (int q = 0; q < MTQ; ++q) { const int k = lane + q * G; mtw[q] = mt[k < MT_N ? k : MT_N - 1]; }
-                mti = mtis[env];
-                slot = first_slot[env];
-                ctx.sync();
-#pragma unroll
-                for (int q = 0; q < MTQ; ++q) { const int k = lane + q * G; if (k < MT_N) s_mt[threadIdx.x / G][k] = mtw[q]; }
-                ctx.sync();
-                const int prev = slot == 0 ? depth - 1 : slot - 1;          // holds the level generated just before
-                last_locked = next_hots[ring_at(prev, env, depth)].last_locked;   // LevelGen.locked_room survives episodes
-                last_locked = last_locked == NONE8 ? -1 : last_locked;
-                done_levels = 0; attempts = 0; dirty = false;
-            }
-        }
-        if (__ballot(have) == 0ull) break;               // every group of the wave has run out of work
-        if (!have) continue;
-        Gen<Ctx> g(ctx, c, w, s_mt[threadIdx.x / G], s_mt[threadIdx.x / G] + MT_N, mti, last_locked);
-        bool ok = g.template attempt<KIND>();
-        mti = g.mti;
-        dirty |= g.twisted;
-        last_locked = g.last_locked;
-        // last-resort guard (Gen::MAX_ATTEMPTS): never seen; keeps an impossible level from hanging the device
-        const bool gave_up = !ok && ++attempts >= Gen<Ctx>::MAX_ATTEMPTS;
-        if (!ok && !gave_up) continue;
-        const int max_steps = g.finish();
-        // write-out: record planes, tables, program
-        uint8_t* rec = next_recs + ring_at(slot, env, depth) * (int64_t)c.rec_bytes;
-        {
-            const uint32_t* src = (const uint32_t*)w.E;
-            uint32_t* dst = (uint32_t*)rec;
-            const int ndw = (c.ES * c.EH) >> 2;
-            for (int k = lane; k < ndw; k += G) dst[k] = src[k];
-        }
-        {
-            const int cells = c.W * c.H, ndw = (cells + 3) >> 2;          // off_I is a dword multiple, the plane is padded to one
-            const uint32_t* src = (const uint32_t*)w.I;
-            uint32_t* dst = (uint32_t*)(rec + c.off_I);
-            for (int k = lane; k < ndw; k += G) {
-                uint32_t v = src[k];
-                if (4 * k + 4 > cells) v &= 0xFFFFFFFFu >> (8 * (4 * k + 4 - cells));      // bytes past the plane stay zero
-                dst[k] = v;
-            }
-        }
-        for (int k = lane; k < c.maxo; k += G) {
-            bool used = k < g.nobj;
-            rec[c.off_app + k] = used ? w.app[k] : 0;
-            rec[c.off_pos + 2 * k] = used ? w.px[k] : 0;
-            rec[c.off_pos + 2 * k + 1] = used ? w.py[k] : 0;
-            rec[c.off_cont + k] = used ? w.cont[k] : NONE8;
-        }
-        {
-            const uint32_t* src = (const uint32_t*)&w.prog;
-            uint32_t* dst = (uint32_t*)(rec + c.off_prog);
-            for (int k = lane; k < (int)(sizeof(Prog) / 4); k += G) dst[k] = src[k];
-        }
-        if constexpr (OBS) {
-            // In-place layout: the level's first observation (gen_obs at the start pose: MiniGridEnv.reset), from the appearance plane
-            // in LDS.  Lane l of the group takes view cells l, l + G, ...: cell = vi + 7 vj; the opacity mask of the view is the
-            // group's share of a ballot per round; every lane runs the 7-row visibility sweep and writes its cells' three bytes
-            // (the layout observe_emit writes: cell (vi, vj) at byte (7 vi + vj) * 3; the agent's own cell shows what it carries: nothing yet).
-            uint8_t* ob = next_obs + ring_at(slot, env, depth) * OBS_SLOT;
-            constexpr int R = (VIEW * VIEW + G - 1) / G;
-            constexpr unsigned long long GM = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
-            int ec[R];
-            unsigned long long opaque = 0;
-            ctx.sync();
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int cell = r * G + lane;
-                int e = E_EMPTY;
-                if (cell < VIEW * VIEW) {
-                    int x, y;
-                    view_to_world(g.ax, g.ay, g.adir, cell % VIEW, cell / VIEW, x, y);
-                    e = w.E[(y + MARGIN) * c.ES + (x + MARGIN)];
-                }
-                ec[r] = e;
-                const unsigned long long bal = __ballot(cell < VIEW * VIEW && e_opaque(e));
-                opaque |= ((bal >> ((int)threadIdx.x & ~(G - 1) & 63)) & GM) << (r * G);
-            }
-            uint32_t opq[VIEW], vis[VIEW];
-#pragma unroll
-            for (int r = 0; r < VIEW; ++r) opq[r] = (uint32_t)(opaque >> (VIEW * r)) & 0x7Fu;
-            process_vis_rows(opq, vis);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int cell = r * G + lane;
-                if (cell < VIEW * VIEW) {
-                    const int vi = cell % VIEW, vj = cell / VIEW;
-                    const int e = (vi == 3 && vj == 6) ? (int)E_EMPTY : ec[r];
-                    uint32_t row = 0;
-#pragma unroll
-                    for (int q = 0; q < VIEW; ++q) row = (vj == q) ? vis[q] : row;
-                    const bool v = row >> vi & 1;
-                    uint8_t* o = ob + (vi * VIEW + vj) * 3;
-                    o[0] = v ? e_type(e) : 0; o[1] = v ? e_color(e) : 0; o[2] = v ? e_state(e) : 0;
-                }
-            }
-            // ... and, for the small single rooms, the level's C plane row (bbai_types.hpp): the grid at pitch 8 + where every object stands
-            if (cpl_ok(c)) {
-                uint8_t* row = ob + CPL_OFF;
-                for (int d = lane; d < CPL_PLANE / 4; d += G) {
-                    const int y = d >> 1, x0 = (d & 1) * 4;
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const int x = x0 + b;
-                        const uint32_t e = (x < c.W && y < c.H) ? (uint32_t)w.E[(y + MARGIN) * c.ES + (x + MARGIN)] : (uint32_t)E_WALL;
-                        v |= e << (8 * b);
-                    }
-                    ((uint32_t*)row)[d] = v;
-                }
-                for (int k = lane; k < CPL_MAX_IDS; k += G)
-                    row[CPL_PLANE + k] = (k < g.nobj && w.px[k] != NONE8) ? (uint8_t)(w.py[k] << 3 | w.px[k]) : (uint8_t)0xFF;
-            }
-        }
-        if (lane == 0) {
-            Hot h;
-            h.ax = (uint8_t)g.ax; h.ay = (uint8_t)g.ay; h.dir = (uint8_t)g.adir; h.carry = NONE8;
-            h.step = 0; h.max_steps = (uint16_t)max_steps;
-            h.pre4 = 0xFFFFFFFFu;
-            h.vstate = 0; h.frozen = 0;
-            if (gave_up) {
-                h.frozen = 2;
-                atomicAdd(gen_failures, 1ull);
-            }
-            h.last_locked = last_locked < 0 ? NONE8 : (uint8_t)last_locked;
-            h.slot = 0;
-            next_hots[ring_at(slot, env, depth)] = h;
-        }
-        slot = slot + 1 == depth ? 0 : slot + 1;
-        attempts = 0;
-        if (++done_levels == cnt) {                      // this env's levels are done: MT state back, buffer entry free
-            // draws only advance the index: the 624 state words change at a twist alone (every 624 draws -- one single-room level in seven)
-            if (dirty) {
-                uint32_t* mt = mts + env * MT_N;
-                ctx.sync();
-                for (int k = lane; k < MT_N; k += G) mt[k] = s_mt[threadIdx.x / G][k];
-            }
-            if (lane == 0) {
-                mtis[env] = mti;
-                pending[env] = 0;                        // buffer entry is free for a later window
-            }
-            have = false;
-        }
-    }
-}
-
-// Derived / canonical forms of the lane generator's RNG state.
-//   k_mt_sync:  after anything that wrote (mts, mtis) in the canonical form (imports, checkpoint loads, the lane-group generator): the latest
-//               generation's tempered outputs into half 0, parity 0.
-//   k_mt_canon: before anything that reads the canonical form (checkpoint saves, the lane-group generator): an env whose position lies in
-//               the PREVIOUS generation gets that generation's raw words back (un-tempered from its half) and position + 624.
-__global__ __launch_bounds__(256) void k_mt_sync(int64_t n, const uint32_t* __restrict__ mts, uint32_t* __restrict__ mtt, uint8_t* __restrict__ mtpar) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n * MT_N) return;
-    const int64_t env = i / MT_N;
-    const int k = (int)(i - env * MT_N);
-    mtt[env * (2 * MT_N) + k] = mt_temper(mts[i]);
-    if (k == 0) mtpar[env] = 0;
-}
-__global__ __launch_bounds__(256) void k_mt_canon(int64_t n, uint32_t* __restrict__ mts, uint32_t* __restrict__ mtt, uint8_t* __restrict__ mtpar, int32_t* __restrict__ mtis) {
-    // one wave per env (the position is read by every lane before lane 0 rewrites it: the wave runs in lockstep up to the barrier)
-    const int64_t env = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (env >= n) return;
-    const int pos = mtis[env];
-    const int par = mtpar[env];
-    __builtin_amdgcn_wave_barrier();
-    if (pos >= 0) return;
-    const uint32_t* prev = mtt + env * (2 * MT_N) + (par ^ 1) * MT_N;
-    for (int k = lane; k < MT_N; k += 64) mts[env * MT_N + k] = mt_untemper(prev[k]);
-    if (lane == 0) { mtis[env] = pos + MT_N; mtpar[env] = (uint8_t)(par ^ 1); }
-}
-
-// look-ahead slot -> live state for the envs that finished (or all, on reset()): one wave copies one record
-__global__ __launch_bounds__(256) void k_consume(LevelCfg c, int64_t n, uint8_t* recs, Hot* __restrict__ hots,
-                                                 uint64_t* __restrict__ stales, uint8_t* next_recs,
-                                                 const Hot* __restrict__ next_hots, uint32_t* __restrict__ vheads,
-                                                 uint64_t* __restrict__ vsets, const int32_t* __restrict__ reset_list,
-                                                 const uint8_t* __restrict__ reset_slot, const uint32_t* __restrict__ counter, int all,
-                                                 unsigned long long* __restrict__ totals, int depth,
-                                                 uint8_t* __restrict__ pending, uint8_t* __restrict__ first_slot,
-                                                 uint32_t* __restrict__ win_meta,
-                                                 uint8_t* __restrict__ image, uint8_t* __restrict__ dirs,
-                                                 uint32_t* __restrict__ other_counter, int prio,
-                                                 uint8_t* __restrict__ vplane /* or NULL */, uint16_t* __restrict__ fcache,
-                                                 uint8_t* __restrict__ lsm_arr /* or NULL */, int inplace, uint8_t* __restrict__ cplane /* or NULL */) {
-    if (prio) __builtin_amdgcn_s_setprio(3);
-    const int64_t count = all ? n : (int64_t)counter[0];
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t it = wave; it < count; it += nwaves) {
-        const int64_t env = all ? it : (int64_t)reset_list[it];
-        const int slot = all ? (int)hots[env].slot : (int)reset_slot[it];       // (k_step listed it next to the env: no round trip through the env's state)
-        consume_env(c, n, env, slot, lane, recs, hots, stales, next_recs, next_hots, vheads, vsets, depth, pending, first_slot,
-                    win_meta, image + env * OBS_BYTES, dirs, vplane, fcache, lsm_arr, inplace != 0, cplane);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd(&totals[0], (unsigned long long)count);
-        other_counter[0] = 0;       // the next step's k_step appends to the other ping-pong counter from zero
-    }
-}
-
-// ---- window turnover (NWIN above) ------------------------------------------------------------------------------------------------
-// k_compact, look-ahead stream, in front of the window's k_pregen: the envs whose `pending` byte is set, as SHARDS dense sub-lists.  Wave
-// w covers envs [64 w, 64 w + 64) and appends to sub-list w % SHARDS: one returning atomic per wave that found any, spread over SHARDS
-// counters (1 048 576 envs, every one pending: 256 per counter) -- off the step path, a few microseconds per window.
-__global__ __launch_bounds__(256) void k_compact(int64_t n, const uint8_t* __restrict__ pending, int32_t* __restrict__ gen_list, uint32_t* __restrict__ gen_count,
-                                                 int64_t wave0, int64_t waves /* this look-ahead stream's 64-env blocks: [wave0, wave0 + waves) */) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = wave0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t env = wave * 64 + lane;
-    const bool mine = wave < wave0 + waves && env < n && pending[env] != 0;
-    const unsigned long long bal = __ballot(mine);
-    if (!bal) return;
-    const int j = (int)(wave % SHARDS);
-    const int leader = __ffsll((long long)bal) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&gen_count[j * GEN_COUNT_U32], (uint32_t)__popcll(bal));
-    base = __shfl(base, leader);
-    if (mine) gen_list[(int64_t)j * gen_sublist_cap(n) + base + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)env;
-}
-// k_mark, look-ahead stream, behind the refill of window w: `refilled` = w + 1.  (A kernel of its own: the refill's stores are visible to
-// whoever sees this value because that kernel has ENDED -- no fence inside the generator's waves.)
-__global__ void k_mark(unsigned long long* __restrict__ flow, unsigned long long refilled) {
-    __hip_atomic_store(&flow[FLOW_REFILLED], refilled, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-// k_gate, step stream, in front of the first tick of window x (which uses buffer x % NWIN): waits until
-//   (a) the windows r .. x - 1 whose refill has not landed (r = `refilled`) are at most NWIN - 1 (buffer x % NWIN is free again), and
-//   (b) the sum of their M (meta[0]; 1 unless an env finished repeatedly inside one window) is <= B: every env then has at least
-//       2B - B = B ready levels, and window x consumes at most B per env;
-// then clears the meta line of window x.  With r = x - 1 (rounds 1-4 waited for exactly that) both hold trivially, so the wait ends at the
-// latest when refill x - 2 lands; every refill it can wait for was enqueued before it.  One wave; polls with s_sleep.  A wait beyond
-// ~10 s of the constant 100-MHz clock gives up (counted in flow[FLOW_GATE_TIMEOUTS], read back as option "gate_timeouts": the handle's
-// results are void then -- it means a lost refill, never seen) instead of hanging the device.
-__global__ __launch_bounds__(64) void k_gate(unsigned long long* __restrict__ flow, uint32_t* __restrict__ metas, unsigned long long x, int period,
-                                              uint32_t* __restrict__ host_fault /* pinned host word: sticky, read by every entry point */) {
-    const int lane = (int)threadIdx.x;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        const unsigned long long r = __hip_atomic_load(&flow[FLOW_REFILLED], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long open = x > r ? x - r : 0ull;          // windows r .. x - 1
-        uint32_t m = 0;
-        if ((unsigned long long)lane < open && open < (unsigned long long)NWIN) {
-            m = metas[(size_t)((r + lane) % NWIN) * META_U32];
-            m = m < 1u ? 1u : m;
-        }
-#pragma unroll
-        for (int o = 32; o; o >>= 1) m += __shfl_xor(m, o);
-        if (open < (unsigned long long)NWIN && m <= (uint32_t)period) break;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 1000000000ull) {
-            if (lane == 0) {
-                atomicAdd(&flow[FLOW_GATE_TIMEOUTS], 1ull);
-                __hip_atomic_store(host_fault, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            break;
-        }
-        __builtin_amdgcn_s_sleep(32);
-    }
-    if (lane == 0) metas[(size_t)(x % NWIN) * META_U32] = 0;
-}
-
-// probe_stream's two kernels: the waiter (caller's stream) polls a flag for at most ~20 ms of the 100-MHz clock, the setter (look-ahead stream, enqueued
-// BEHIND it) raises it.  Verdict into pinned host memory: 1 = the setter ran while the waiter was resident (the streams are concurrent), 2 = it did not.
-__global__ void k_probe_wait(unsigned long long* __restrict__ flow, uint32_t* __restrict__ host_verdict) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    uint32_t v = 2;
-    for (;;) {
-        if (__hip_atomic_load(&flow[FLOW_PROBE], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0ull) { v = 1; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) break;
-        __builtin_amdgcn_s_sleep(16);
-    }
-    __hip_atomic_store(host_verdict, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_probe_set(unsigned long long* __restrict__ flow, unsigned long long v) {
-    __hip_atomic_store(&flow[FLOW_PROBE], v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// In-place layout: rec[] is the staging area of export / import / checkpoints.  dir 0: live slots -> rec[first ..], dir 1: rec[first ..] -> live
-// slots; one wave per env.
-__global__ __launch_bounds__(256) void k_live_copy(LevelCfg c, int64_t n, int64_t first, int64_t count, uint8_t* __restrict__ recs,
-                                                   uint8_t* __restrict__ ring, const Hot* __restrict__ hots, int depth, int dir) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    const int nvec = c.rec_bytes >> 4;
-    for (int64_t it = wave; it < count; it += nwaves) {
-        const int64_t env = first + it;
-        u32x4* stage = (u32x4*)(recs + env * (int64_t)c.rec_bytes);
-        u32x4* live = (u32x4*)(ring + ring_at(live_slot(hots[env].slot, depth), env, depth) * (int64_t)c.rec_bytes);
-        for (int k = lane; k < nvec; k += 64) { if (dir) live[k] = stage[k]; else stage[k] = live[k]; }
-    }
-}
-// ... and an imported hot state keeps the env's place in its ring (hot.slot): the slot says where the live record IS
-__global__ void k_import_hot(int64_t first, int64_t count, const Hot* __restrict__ staged, Hot* __restrict__ hots) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    Hot h = staged[i];
-    h.slot = hots[first + i].slot;
-    hots[first + i] = h;
-}
-
-// rebuild the SoA verifier view from the records (after bbai_import_state)
-__global__ void k_sync_prog(LevelCfg c, int64_t n, int64_t first, int64_t count, const uint8_t* __restrict__ recs,
-                            uint32_t* __restrict__ vheads, uint64_t* __restrict__ vsets) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const int64_t env = first + i;
-    const Prog* p = (const Prog*)(recs + env * (int64_t)c.rec_bytes + c.off_prog);
-    for (int k = 0; k < 8; ++k) vsets[(int64_t)k * n + env] = p->set[k >> 1][k & 1];
-    vheads[env] = vhead_pack(*p);
-}
-
-// rebuild the window plane and the front-cell cache from the live records (after bbai_import_state / checkpoint_load):
-// one wave per env
-__global__ __launch_bounds__(256) void k_sync_view(LevelCfg c, int64_t first, int64_t count, const uint8_t* __restrict__ recs,
-                                                   const Hot* __restrict__ hots, uint8_t* __restrict__ vplane, uint16_t* __restrict__ fcache) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    const int nseg = v_nxo(c) * v_nyo(c) * 8;
-    for (int64_t it = wave; it < count; it += nwaves) {
-        const int64_t env = first + it;
-        const uint8_t* rec = recs + env * (int64_t)c.rec_bytes;
-        uint8_t* vrow = vplane + env * (int64_t)v_bytes(c);
-        for (int sg = lane; sg < nseg; sg += 64) *(u32x4*)(vrow + (sg >> 3) * VLINE + (sg & 7) * 16) = v_segment(c, rec, sg >> 3, sg & 7, -1);
-        if (lane == 0) {
-            const Hot h = hots[env];
-            const uint32_t fe = rec[e_index(c, h.ax + dir_dx(h.dir), h.ay + dir_dy(h.dir))];
-            const uint32_t ce = h.carry != NONE8 ? rec[c.off_app + h.carry] : (uint32_t)E_EMPTY;
-            fcache[env] = (uint16_t)(fe | (ce << 8));
-        }
-    }
-}
-
-// ... and the C plane rows + the carried object's appearance of the small single rooms (in-place layout): one wave per env, from the staged records
-__global__ __launch_bounds__(256) void k_sync_cpl(LevelCfg c, int64_t first, int64_t count, const uint8_t* __restrict__ recs,
-                                                  const Hot* __restrict__ hots, uint8_t* __restrict__ cplane, uint16_t* __restrict__ fcache) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t it = wave; it < count; it += nwaves) {
-        const int64_t env = first + it;
-        const uint8_t* rec = recs + env * (int64_t)c.rec_bytes;
-        cpl_build_wave(c, rec, cplane + env * (int64_t)cpl_bytes(c), lane);
-        if (lane == 0) {
-            const Hot h = hots[env];
-            const uint32_t fe = rec[e_index(c, h.ax + dir_dx(h.dir), h.ay + dir_dy(h.dir))];
-            const uint32_t ce = h.carry != NONE8 ? rec[c.off_app + h.carry] : (uint32_t)E_EMPTY;
-            fcache[env] = (uint16_t)(fe | (ce << 8));
-        }
-    }
-}
-
-// The reference's expert for every env (babyai/bot.py Bot.replan): lane = env, grid-stride over the batch with one BFS
-// scratch block per resident thread.  A new episode (step_count == 0) starts a fresh Bot.
-template <int WAVES_PER_SIMD>
-__global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_bot(LevelCfg c, int64_t n, const uint8_t* __restrict__ recs, const uint8_t* __restrict__ ring /* in-place layout: the live records are ring slots; else NULL */,
-                                            int depth, const Hot* __restrict__ hots,
-                                            const uint64_t* __restrict__ stales, uint8_t* __restrict__ states, int stack_cap,
-                                            uint16_t* __restrict__ works, uint32_t* __restrict__ slow_rows, int eager, const uint8_t* __restrict__ prev_actions,
-                                            uint8_t* __restrict__ out, unsigned long long* __restrict__ stats,
-                                            int dead_action /* what a bot that gave up emits: BOT_DEAD, or A_RESET_ENV in a rollout */,
-                                            uint8_t* __restrict__ gave_up /* or NULL: [n] 1 where the bot gave up at this decision */) {
-    // the searches' hot row masks (expandable / queued / seen), [row][lane] in LDS: every lane on its own bank
-    extern __shared__ uint32_t s_rows[];              // [R_FAST][H][64] row masks, then the queue ring uint16 [BOT_RING][64]
-    uint16_t* s_ring = (uint16_t*)(s_rows + R_FAST * c.H * 64);
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-    BotWork w;
-    w.eager = eager;
-    w.ring = s_ring + threadIdx.x; w.ring_stride = 64; w.ring_size = BOT_RING;
-    w.rows_fast = s_rows + threadIdx.x; w.rstride_fast = 64; w.rows_h = c.H;
-    w.rows_slow = slow_rows + tid * ((R_ALL - R_FAST) * MAX_W); w.rstride_slow = 1;
-    // per-thread contiguous scratch: measured faster than lane-interleaving it (BossLevel 262144 envs 12.8 vs 17.6 ms per
-    // decision batch) -- the lanes' searches diverge at once, so an interleaved line holds one useful 2-byte element
-    w.cells = c.W * c.H;                                    // 64 cells (512 B of scratch) for an 8x8 room, 484 for a 3x3 maze
-    w.base = works + tid * (int64_t)(4 * w.cells);
-    w.stride = 1;
-    for (int64_t i = tid; i < n; i += nthreads) {
-        const Hot h = hots[i];
-        if (h.frozen) { out[i] = A_DONE; if (gave_up) gave_up[i] = 0; continue; }
-        BotState& st = *(BotState*)(states + i * (int64_t)bot_state_bytes(stack_cap));
-        const bool first = h.step == 0 || st.next_step != h.step;       // (bot_decide applies the same rule)
-        const int taken = (prev_actions && !first) ? prev_actions[i] : -1;
-        const bool was_dead = !first && st.dead;
-        const int a = bot_decide(c, live_rec(c, n, i, (uint8_t*)recs, (uint8_t*)ring, depth, h.slot), h, stales[i], st, stack_cap, w, first, taken);
-        out[i] = (uint8_t)(a == BOT_DEAD ? dead_action : a);
-        if (gave_up) gave_up[i] = a == BOT_DEAD ? 1 : 0;
-        if (a == BOT_DEAD && !was_dead) atomicAdd(&stats[st.dead == DEAD_CAPACITY ? 1 : 0], 1ull);
-    }
-}
-
-// BBAI_BOT_GROUP_BUILD=1 (experiment builds only; the shipped library has no k_botg): the expert as one 16-lane group per env.  Built, verified on
-// the host emulation of lane groups (tests/test_hostsim_bot.py, which stays) and on the device, measured 1.9-2.4 x SLOWER than lane = env
-// (profiles/r05/NOTES.md section 11); a 4-waves-per-SIMD build of it produced different decisions, never explained -- 250 KB of dead-by-default
-// code with an open question attached does not belong in the product.
-#ifndef BBAI_BOT_GROUP_BUILD
-#define BBAI_BOT_GROUP_BUILD 0
-#endif
-#if BBAI_BOT_GROUP_BUILD
-
-// The expert as ONE LANE GROUP PER ENV (G lanes, 64 / G envs per wave; bbai_bot.hpp "Execution model"): the subgoal machine runs
-// group-uniform, the view, the mask rows, the neighbours of a popped position and the acceptance / key scans are split over the lanes.
-// Per group in LDS: the four row-mask arrays [R_ALL][H], search 1's predecessor + queue arrays [2][W * H] uint16 (the eager first
-// search never leaves LDS), and the env's BotState for the length of the decision (the subgoal stack stays in global memory: a
-// decision touches its top).  Search 2's arrays (only when search 1 failed) are per-resident-group global scratch.
-__host__ __device__ inline int botg_group_words(const LevelCfg& c) {
-    return R_ALL * c.H + (2 * c.W * c.H * 2 + 3) / 4 + (int)sizeof(BotState) / 4;
-}
-template <int G, int WAVES_PER_SIMD>
-__global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_botg(LevelCfg c, int64_t n, const uint8_t* __restrict__ recs, const uint8_t* __restrict__ ring, int depth,
-                                             const Hot* __restrict__ hots, const uint64_t* __restrict__ stales, uint8_t* __restrict__ states, int stack_cap,
-                                             uint16_t* __restrict__ works, int eager, const uint8_t* __restrict__ prev_actions, uint8_t* __restrict__ out,
-                                             unsigned long long* __restrict__ stats, int dead_action, uint8_t* __restrict__ gave_up) {
-    extern __shared__ uint32_t s_botg[];
-    constexpr int NG = 64 / G, SW = (int)sizeof(BotState) / 4;
-    const GroupCtx<G> ctx;
-    const int lane = ctx.lane();
-    const int cells = c.W * c.H;
-    uint32_t* blk = s_botg + ((int)threadIdx.x / G) * botg_group_words(c);
-    const int64_t group = (int64_t)blockIdx.x * NG + (int)threadIdx.x / G, ngroups = (int64_t)gridDim.x * NG;
-    BotWork w;
-    w.eager = eager;
-    w.ring = nullptr; w.ring_stride = 0; w.ring_size = 0;
-    w.rows_fast = blk; w.rstride_fast = 1; w.rows_h = c.H; w.fast_n = R_ALL;
-    w.rows_slow = nullptr; w.rstride_slow = 0;
-    w.cells = cells;
-    w.near_q = (uint16_t*)(blk + R_ALL * c.H);
-    w.base = works + group * (int64_t)(4 * cells);          // (arrays 2, 3: search 2)
-    w.stride = 1;
-    uint32_t* sst = blk + R_ALL * c.H + (2 * cells * 2 + 3) / 4;
-    BotState& st = *(BotState*)sst;
-    const size_t sbytes = bot_state_bytes(stack_cap);
-    for (int64_t i = group; i < n; i += ngroups) {
-        const Hot h = hots[i];
-        if (h.frozen) {
-            if (lane == 0) { out[i] = A_DONE; if (gave_up) gave_up[i] = 0; }
-            continue;
-        }
-        uint32_t* gst = (uint32_t*)(states + i * (int64_t)sbytes);
-        for (int k = lane; k < SW; k += G) sst[k] = gst[k];
-        ctx.sync();
-        const bool first = h.step == 0 || st.next_step != h.step;
-        const int taken = (prev_actions && !first) ? prev_actions[i] : -1;
-        const bool was_dead = !first && st.dead;
-        const int a = bot_decide(ctx, c, live_rec(c, n, i, (uint8_t*)recs, (uint8_t*)ring, depth, h.slot), h, stales[i], st, (Subgoal*)(gst + SW), stack_cap, w, first, taken);
-        ctx.sync();
-        if (lane == 0) {
-            out[i] = (uint8_t)(a == BOT_DEAD ? dead_action : a);
-            if (gave_up) gave_up[i] = a == BOT_DEAD ? 1 : 0;
-            if (a == BOT_DEAD && !was_dead) atomicAdd(&stats[st.dead == DEAD_CAPACITY ? 1 : 0], 1ull);
-        }
-        for (int k = lane; k < SW; k += G) gst[k] = sst[k];
-        ctx.sync();
-    }
-}
-#endif
-
-// env.seed(s) for every env: lane = env.  Each lane writes its own 624-word state (2496-byte pitch): a wave's 64 open
-// lines stay in L2 until they are full, so HBM sees each state line once.
-__global__ __launch_bounds__(64) void k_seed(int64_t n, const uint64_t* __restrict__ seeds, uint32_t* __restrict__ mts, int32_t* __restrict__ mtis) {
-    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    seed_env(seeds[i], mts + i * MT_N);
-    mtis[i] = MT_N;                               // output index 624: the first draw twists (RandomState.seed leaves pos = N)
-}
-
-__global__ void k_init_hot(int64_t n, Hot* __restrict__ hots, Hot* __restrict__ next_hots, uint64_t* __restrict__ stales, int depth) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        Hot h;
-        memset(&h, 0, sizeof(h));
-        h.carry = NONE8; h.frozen = 1; h.last_locked = NONE8;
-        h.pre4 = 0xFFFFFFFFu;
-        hots[i] = h;
-        for (int d = 0; d < depth; ++d) next_hots[ring_at(d, i, depth)] = h;
-        stales[i] = 0;
-    }
-}
-
+#include "bbai_stepk.hpp"
+#include "bbai_pregen.hpp"
+#include "bbai_ring.hpp"
+#include "bbai_botk.hpp"
 #include "bbai_render.hpp"
-
-// ------------------------------------------------------------------------------------------
-// k_render_grid : the full-grid picture, MiniGridEnv.render('rgb_array', highlight, tile_size), of listed envs (bbai_render_grid)
-// ------------------------------------------------------------------------------------------
-// A frame is uint8[H ts][W ts][3] (row = y, as Grid.render lays it out): H x W atlas tiles.  Per work item a block builds the tile-id
-// planes of its envs in LDS (bbai_grid.hpp: ONE lut lookup per cell, from the live record -- live_rec, as k_tokens / k_bot -- the pose and
-// the highlight mask), then streams the frames as 16-byte nontemporal stores, a frame being a flat run of 16-byte chunks (frame bytes
-// are a multiple of 192; row bytes need not be a multiple of 16).  A chunk is made of pieces that never cross a tile row: 8 bytes at
-// tile size 8 (24-byte tile rows, as render_chunk), 16 bytes at 16 and 32; per piece one multiply-high divide finds its pixel row and
-// tile, then the piece is copied from the atlas -- in LDS at 8 and 16 (25 / 102 KB), from L2 at 32 (≈400 KB: it stays resident).
-// Work items (render_grid_launch): several envs per item for small frames, several items per env for large ones; persistent blocks.
-// Writes nothing but `out`.  An id outside [0, n) draws every cell with the zero tile the atlas carries behind its last one.
-constexpr int GRID_BLOCK = 1024;
-constexpr int GRID_MAX_ENVS = 32;                // envs per work item
-constexpr int GRID_ID_BYTES = 4096;              // tile ids of one work item
-constexpr int GRID_MAX_TILES = 132;              // atlas tiles (+ the zero tile)
-constexpr int GRID_UNROLL = 4;                   // 16-byte chunks per lane in flight
-
-template <int TS> struct GridTile {
-    static constexpr int P = TS == 8 ? 8 : 16;           // bytes per piece
-    static constexpr int PPT = TS * 3 / P;               // pieces per tile row: 3, 3, 6
-    static constexpr int BYTES = TS * TS * 3;
-    static constexpr bool LDS = TS <= 16;
-};
-
-struct GridArgs {
-    LevelCfg c;
-    int64_t n;
-    const uint8_t* recs;
-    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
-    int depth;
-    const Hot* hots;
-    const int64_t* ids;          // NULL: envs 0 .. count - 1
-    int64_t count;
-    uint8_t* out;
-    const uint8_t* atlas;        // [n_tiles + 1][TS][TS][3], the last one all zero
-    const uint8_t* lut;          // [2][5][256]
-    int n_tiles, highlight;
-    int envs_per_item, slices;   // one of them is 1
-    int64_t items;
-    uint32_t frame16;            // 16-byte chunks per frame
-    uint64_t frame_magic;        // 2^32 / frame16 + 1: q / frame16 as a multiply-high (q frame16 < 2^32)
-    uint32_t ppr;                // pieces per pixel row
-    uint64_t ppr_magic;
-};
-
-__device__ __forceinline__ uint32_t grid_div(uint32_t q, uint64_t magic) { return (uint32_t)(((uint64_t)q * magic) >> 32); }
-
-template <int TS>
-__device__ __forceinline__ const uint8_t* grid_piece(const uint8_t* atlas, const uint8_t* ids, int W, const GridArgs& a, uint32_t p) {
-    using G = GridTile<TS>;
-    const uint32_t py = grid_div(p, a.ppr_magic), px = p - py * a.ppr;
-    const uint32_t tx = px / G::PPT, part = px - tx * G::PPT;
-    const int id = ids[(py / TS) * W + tx];
-    return atlas + id * G::BYTES + (py % TS) * (TS * 3) + part * G::P;
-}
-
-template <int TS>
-__global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(GridArgs a) {      // (8 waves per SIMD: two blocks per CU)
-    using G = GridTile<TS>;
-    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[G::LDS ? (GRID_MAX_TILES + 1) * G::BYTES : 16];
-    __shared__ __attribute__((aligned(16))) uint8_t s_lut[GRID_LUT_BYTES];
-    __shared__ uint8_t s_ids[GRID_ID_BYTES];
-    __shared__ uint32_t s_hl[GRID_MAX_ENVS][MAX_W];
-    __shared__ Hot s_hot[GRID_MAX_ENVS];
-    __shared__ const uint8_t* s_rec[GRID_MAX_ENVS];
-    const int tid = threadIdx.x;
-    const uint8_t* atlas = a.atlas;
-    if (G::LDS) {
-        for (int k = tid; k < (a.n_tiles + 1) * G::BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_atlas)[k] = ((const u32x4*)a.atlas)[k];
-        atlas = s_atlas;
-    }
-    for (int k = tid; k < GRID_LUT_BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_lut)[k] = ((const u32x4*)a.lut)[k];
-    const int W = a.c.W, HW = a.c.W * a.c.H;
-    const int64_t F16 = a.frame16;
-    constexpr int ESTRIDE = GRID_BLOCK / GRID_MAX_ENVS;       // the envs' view work spread over the waves (two envs per wave)
-    u32x4* const out = (u32x4*)a.out;
-    for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
-        const int64_t first = a.slices > 1 ? item / a.slices : item * a.envs_per_item;      // first output frame of the item
-        const int slice = (int)(item - first * a.slices);                                   // (0 unless sliced)
-        const int ne = a.slices > 1 ? 1 : (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
-        __syncthreads();                                  // atlas loaded / the previous item's ids consumed
-        if (tid % ESTRIDE == 0 && tid / ESTRIDE < ne) {
-            const int e = tid / ESTRIDE;
-            const int64_t env = a.ids ? a.ids[first + e] : first + e;
-            const uint8_t* rec = nullptr;
-            Hot h = {};
-            if (env >= 0 && env < a.n) {
-                h = a.hots[env];
-                rec = live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? h.slot : 0);
-                grid_highlight(a.c, rec, h, s_hl[e]);
-            }
-            s_hot[e] = h;
-            s_rec[e] = rec;
-        }
-        __syncthreads();
-        for (int ci = tid; ci < ne * HW; ci += GRID_BLOCK) {
-            const int e = ci / HW, cell = ci - e * HW;
-            const int y = cell / W, x = cell - y * W;
-            const uint8_t* rec = s_rec[e];
-            s_ids[ci] = (uint8_t)(rec ? grid_tile(a.c, rec, s_hot[e], s_lut, a.highlight, s_hl[e], x, y) : a.n_tiles);
-        }
-        __syncthreads();
-        // chunks [q0, q1) of the item, counted from its first frame's first chunk
-        const int64_t q0 = a.slices > 1 ? slice * F16 / a.slices : 0;
-        const int64_t q1 = a.slices > 1 ? (slice + 1) * F16 / a.slices : ne * F16;
-        u32x4* const base = out + first * F16;
-        for (int64_t qb = q0 + tid; qb < q1; qb += GRID_UNROLL * GRID_BLOCK) {
-            u32x4 v[GRID_UNROLL];
-#pragma unroll
-            for (int u = 0; u < GRID_UNROLL; ++u) {
-                const uint32_t q = (uint32_t)(qb + u * GRID_BLOCK < q1 ? qb + u * GRID_BLOCK : q1 - 1);     // (past the end: a chunk of the item, not stored)
-                const uint32_t e = a.slices > 1 ? 0u : grid_div(q, a.frame_magic);
-                const uint32_t j = q - e * (uint32_t)F16;
-                const uint8_t* ids = s_ids + e * HW;
-                if (TS == 8) {
-                    const uint64_t lo = *(const uint64_t*)grid_piece<TS>(atlas, ids, W, a, 2 * j);
-                    const uint64_t hi = *(const uint64_t*)grid_piece<TS>(atlas, ids, W, a, 2 * j + 1);
-                    v[u] = u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-                } else {
-                    v[u] = *(const u32x4*)grid_piece<TS>(atlas, ids, W, a, j);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < GRID_UNROLL; ++u)
-                if (qb + u * GRID_BLOCK < q1) __builtin_nontemporal_store(v[u], base + qb + u * GRID_BLOCK);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_full_obs : the fully observable encoding, FullyObsWrapper.observation, of listed envs (bbai_observe_full, bbai_step_full)
-// ------------------------------------------------------------------------------------------
-// A frame is uint8[W][H][3] (F = 3 W H bytes, indexed [x][y] as grid.encode() is).  Work item = envs_per_item envs; per item a block
-//   1. copies the H interior rows of each env's appearance plane (H x ES bytes of the live record -- live_rec: both state layouts) into
-//      LDS as dwords, FULL_UNROLL independent loads per lane in flight: ONE memory round trip per item (a load per cell in a loop is one
-//      round trip per trip, and it measured 2.1 TB/s);
-//   2. writes each cell's 3 bytes (bbai_grid.hpp full_cell, on the LDS rows) into the item's frames in LDS at their [x][y] place;
-//   3. stores the item's frames -- ONE contiguous byte range of `out` -- from LDS as 16-byte nontemporal chunks that cross frame boundaries
-//      freely (BossLevel: F = 1452, not a multiple of 16).  envs_per_item is a multiple of 16 / gcd(F, 16), so every item starts 16-byte
-//      aligned and only the end of the whole output can hold a partial chunk: that tail is stored byte by byte.
-// The next item's ids and Hots are loaded into registers while the current one is worked on.  Writes nothing but `out`.  An id outside
-// [0, n) gives an all-zero frame.
-constexpr int FULL_BLOCK = 512;
-constexpr int FULL_LDS = 24576;               // frame bytes of one work item (3 x 25 x 25 x 16 = 30 000 > this: see full_launch)
-constexpr int FULL_APP = 16384;               // appearance rows of one work item
-constexpr int FULL_MAX_ENVS = 128;            // envs per work item
-constexpr int FULL_BPC = 3;                   // persistent blocks per CU (≈ 43 KB of LDS each)
-constexpr int FULL_UNROLL = 8;                // dword loads per lane in flight
-
-struct FullArgs {
-    LevelCfg c;
-    int64_t n;
-    const uint8_t* recs;
-    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
-    int depth;
-    const Hot* hots;
-    const int64_t* ids;          // NULL: envs 0 .. count - 1
-    int64_t count;
-    uint8_t* out;
-    int envs_per_item;
-    int64_t items;
-    uint64_t hw_magic, w_magic, rd_magic;   // multiply-high divides by W H, W and the dwords of an env's rows (grid_div; q < 2^16)
-};
-
-// (env, Hot) of entry k of an item: the Hot as one 16-byte load, zero for an id outside [0, n)
-__device__ __forceinline__ void full_entry(const FullArgs& a, int64_t k, int64_t& env, u32x4& h) {
-    env = a.ids ? a.ids[k] : k;
-    h = u32x4{0u, 0u, 0u, 0u};
-    if (env >= 0 && env < a.n) h = ((const u32x4*)a.hots)[env];
-    else env = -1;
-}
-
-__global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      // (6 waves per SIMD: FULL_BPC blocks per CU)
-    __shared__ __attribute__((aligned(16))) uint8_t s_frames[FULL_LDS];
-    __shared__ __attribute__((aligned(16))) uint32_t s_app[FULL_APP / 4];
-    __shared__ __attribute__((aligned(16))) Hot s_hot[FULL_MAX_ENVS];
-    __shared__ const uint8_t* s_rec[FULL_MAX_ENVS];
-    const int tid = threadIdx.x;
-    const int W = a.c.W, H = a.c.H, HW = W * H, F = 3 * HW, ES = a.c.ES;
-    const int RD = H * ES / 4;                          // dwords of an env's interior rows (ES: a multiple of 4)
-    const int D0 = MARGIN * ES / 4;                     // first dword of the interior rows
-    int64_t env = -1;
-    u32x4 h = {0u, 0u, 0u, 0u};
-    int64_t item = blockIdx.x;
-    if (item < a.items && tid < a.envs_per_item && item * a.envs_per_item + tid < a.count) full_entry(a, item * a.envs_per_item + tid, env, h);
-    for (; item < a.items; item += gridDim.x) {
-        const int64_t first = item * a.envs_per_item;
-        const int ne = (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
-        __syncthreads();                                  // the previous item's frames are stored
-        if (tid < ne) {
-            const uint8_t* rec = env >= 0 ? live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? (int)(h.w >> 24) : 0)      // (h.w >> 24 = slot)
-                                          : nullptr;
-            ((u32x4*)s_hot)[tid] = h;
-            s_rec[tid] = rec;
-        }
-        __syncthreads();
-        for (int k0 = tid; k0 < ne * RD; k0 += FULL_UNROLL * FULL_BLOCK) {
-            uint32_t v[FULL_UNROLL];
-#pragma unroll
-            for (int u = 0; u < FULL_UNROLL; ++u) {
-                const int k = k0 + u * FULL_BLOCK;
-                v[u] = 0;
-                if (k < ne * RD) {
-                    const int e = (int)grid_div((uint32_t)k, a.rd_magic);
-                    const uint8_t* rec = s_rec[e];
-                    if (rec) v[u] = ((const uint32_t*)rec)[D0 + (k - e * RD)];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < FULL_UNROLL; ++u)
-                if (k0 + u * FULL_BLOCK < ne * RD) s_app[k0 + u * FULL_BLOCK] = v[u];
-        }
-        {   // the next item's entries, under this item's work
-            const int64_t nf = (item + gridDim.x) * a.envs_per_item;
-            env = -1;
-            if (item + gridDim.x < a.items && tid < a.envs_per_item && nf + tid < a.count) full_entry(a, nf + tid, env, h);
-        }
-        __syncthreads();
-        for (int ci = tid; ci < ne * HW; ci += FULL_BLOCK) {
-            const int e = (int)grid_div((uint32_t)ci, a.hw_magic), cell = ci - e * HW;
-            const int y = (int)grid_div((uint32_t)cell, a.w_magic), x = cell - y * W;
-            uint8_t* o = s_frames + e * F + (x * H + y) * 3;
-            if (s_rec[e]) full_cell_key(((const uint8_t*)s_app)[e * RD * 4 + y * ES + x + MARGIN], s_hot[e], x, y, o);
-            else o[0] = o[1] = o[2] = 0;
-        }
-        __syncthreads();
-        const int bytes = ne * F, chunks = bytes >> 4;
-        uint8_t* const dst = a.out + first * F;           // 16-byte aligned (see above)
-        for (int q = tid; q < chunks; q += FULL_BLOCK) __builtin_nontemporal_store(((const u32x4*)s_frames)[q], (u32x4*)dst + q);
-        for (int b = (chunks << 4) + tid; b < bytes; b += FULL_BLOCK) dst[b] = s_frames[b];      // (the last item only)
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_tokens : mission strings as fixed-vocabulary token ids, produced on the device from the compiled
-// instruction program (grammar: babyai/levels/verifier.py:64-94,248-249,287-288,318-319,366-367,439-440,
-// 480-481,526-527).  Vocabulary ids = babyai_amd/missions.py VOCAB (1..32, 0 = padding).
-// ------------------------------------------------------------------------------------------
-constexpr int TOK_MAX = 72;      // longest sentence: two And-pairs of put-next clauses with locations
-struct TokOut {
-    uint8_t* p; int n;
-    __device__ __forceinline__ void put(int id) { if (n < TOK_MAX) p[n++] = (uint8_t)id; }
-};
-__device__ __forceinline__ void tok_desc(TokOut& o, DescInfo d) {
-    o.put(d.count > 1 ? 9 : 8);                         // a / the
-    if (d.color != 7) o.put(11 + d.color);              // red green blue purple yellow grey
-    o.put(d.type == 0 ? 10 : 24 - d.type);              // object | box ball key door
-    if (d.loc == LOC_FRONT) { o.put(21); o.put(22); o.put(23); o.put(24); }      // in front of you
-    else if (d.loc == LOC_BEHIND) { o.put(25); o.put(24); }                     // behind you
-    else if (d.loc == LOC_LEFT) { o.put(26); o.put(27); o.put(28); }            // on your left
-    else if (d.loc == LOC_RIGHT) { o.put(26); o.put(27); o.put(29); }           // on your right
-}
-__device__ __forceinline__ void tok_side(TokOut& o, const Prog* p, int base, int n) {
-    for (int q = 0; q < n; ++q) {
-        if (q) o.put(30);                                                        // and
-        const int kind = p->kind[base + q];
-        if (kind == L_GOTO) { o.put(1); o.put(2); }                              // go to
-        else if (kind == L_PICKUP) { o.put(3); o.put(4); }                       // pick up
-        else if (kind == L_OPEN) o.put(5);                                       // open
-        else o.put(6);                                                           // put
-        tok_desc(o, p->desc[base + q][0]);
-        if (kind == L_PUTNEXT) { o.put(7); o.put(2); tok_desc(o, p->desc[base + q][1]); }   // next to
-    }
-}
-__global__ __launch_bounds__(64) void k_tokens(LevelCfg c, int64_t n, const uint8_t* __restrict__ recs, const uint8_t* __restrict__ ring /* in-place layout, else NULL */, int depth,
-                                               const Hot* __restrict__ hots, uint8_t* __restrict__ tokens,
-                                               const int32_t* __restrict__ reset_list, const uint32_t* __restrict__ counter,
-                                               int mode /* 0: the reset list (unfused consume); 1: every env; 2: the envs whose `dones` byte is set -- a fused / in-place
-                                                           auto-reset step keeps no list, and there done == "a new episode started" */,
-                                               const uint8_t* __restrict__ dones) {
-    const int64_t count = mode ? n : (int64_t)counter[0];
-    for (int64_t it = (int64_t)blockIdx.x * 64 + threadIdx.x; it < count; it += (int64_t)gridDim.x * 64) {
-        const int64_t env = mode ? it : (int64_t)reset_list[it];
-        if (mode == 2 && !dones[env]) continue;
-        const Prog* p = (const Prog*)(live_rec(c, n, env, (uint8_t*)recs, (uint8_t*)ring, depth, ring ? hots[env].slot : 0) + c.off_prog);
-        TokOut o; o.p = tokens + env * TOK_MAX; o.n = 0;
-        tok_side(o, p, 0, p->n_a);
-        if (p->root == R_BEFORE) { o.put(31); tok_side(o, p, 2, p->n_b); }                   // , then
-        else if (p->root == R_AFTER) { o.put(32); o.put(24); tok_side(o, p, 2, p->n_b); }    // after you
-        while (o.n < TOK_MAX) o.p[o.n++] = 0;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_tap : copy the outputs of `count` envs (and the pixels of the first `pix_count` of them) into log rows -- the parity
-// tap of bench.py as ONE launch inside the timed region (five small tensor copies cost more than a 65 536-env step).
-// ids == NULL: the first `count` envs; else env ids[k] -> log row k (any order, anywhere in the batch).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_tap(int64_t count, int64_t pix_count, const int64_t* __restrict__ ids, const uint8_t* __restrict__ image,
-                                             const uint8_t* __restrict__ dirs, const double* __restrict__ rew64, const uint8_t* __restrict__ dones,
-                                             const uint8_t* __restrict__ pixels, uint8_t* __restrict__ image_out, uint8_t* __restrict__ dirs_out,
-                                             double* __restrict__ rew64_out, uint8_t* __restrict__ dones_out, uint8_t* __restrict__ pixels_out) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = tid; i < count * OBS_BYTES; i += nth) {
-        const int64_t k = i / OBS_BYTES, b = i - k * OBS_BYTES;
-        image_out[i] = image[(ids ? ids[k] : k) * OBS_BYTES + b];
-    }
-    for (int64_t i = tid; i < count; i += nth) {
-        const int64_t e = ids ? ids[i] : i;
-        dirs_out[i] = dirs[e]; dones_out[i] = dones[e]; rew64_out[i] = rew64[e];
-    }
-    constexpr int VEC = PIX_BYTES / 16;
-    const u32x4* src = (const u32x4*)pixels;
-    u32x4* dst = (u32x4*)pixels_out;
-    for (int64_t i = tid; i < pix_count * VEC; i += nth) {
-        const int64_t k = i / VEC, v = i - k * VEC;
-        dst[i] = src[(ids ? ids[k] : k) * VEC + v];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_gae : generalised advantage estimation of a rollout, lane = env (babyai/rl/algos/base.py:196-202 as ONE reverse
-// scan per env instead of T passes of five tensor ops).  All buffers are env-major [P][T], the layout the reference
-// flattens its experiences to (base.py:207-232), so nothing is transposed afterwards.  float32 arithmetic in the
-// reference's operation order (python scalars multiply as float32; the file is built with -ffp-contract=off):
-//   delta = (r + (d * next_value) * next_mask) - v ;  adv = delta + ((d * lambda) * next_adv) * next_mask
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_gae(int64_t P, int T, const float* __restrict__ rewards, const float* __restrict__ values,
-                                            const float* __restrict__ masks, const float* __restrict__ last_mask,
-                                            const float* __restrict__ last_value, float d, float dl, float* __restrict__ adv,
-                                            float* __restrict__ ret) {
-    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (p >= P) return;
-    const float* r = rewards + p * T; const float* v = values + p * T; const float* m = masks + p * T;
-    float next_value = last_value[p], next_mask = last_mask[p], next_adv = 0.0f;
-    for (int i = T - 1; i >= 0; --i) {
-        const float vi = v[i];
-        const float delta = (r[i] + (d * next_value) * next_mask) - vi;
-        const float a = delta + (dl * next_adv) * next_mask;
-        adv[p * T + i] = a;
-        ret[p * T + i] = vi + a;
-        next_value = vi; next_mask = m[i]; next_adv = a;
-    }
-}
-
+#include "bbai_gridk.hpp"
+#include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
+
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -2046,7 +327,7 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
     alloc((void**)&e->gen_count, SHARDS * GEN_COUNT_U32 * 4);
     e->gen_lists[0] = e->gen_list; e->gen_counts[0] = e->gen_count;         // (further look-ahead streams' lists: set_sides)
     {
-        // BBAI_INPLACE: 1 / 0 force the in-place layout (live_slot above) on / off; default: by level family and batch size
+        // BBAI_INPLACE: 1 / 0 force the in-place layout (live_slot, bbai_kernels.hpp) on / off; default: by level family and batch size
         const char* iv = getenv("BBAI_INPLACE");
         e->inplace = iv ? (atoi(iv) != 0) : inplace_by_default(c, n_envs);
     }
@@ -2411,7 +692,7 @@ struct ProfScope {
 };
 
 // A consume-tick (one reset() or one auto-resetting step) in three parts: window_begin -- at the first tick of a window k_gate holds
-// the stream until every env is sure to find B ready levels (NWIN above); the consume itself -- k_consume over the reset list,
+// the stream until every env is sure to find B ready levels (NWIN, bbai_kernels.hpp); the consume itself -- k_consume over the reset list,
 // or, fused, inside k_step (which therefore has to be launched AFTER window_begin); window_end -- the mission tokens of the new
 // episodes and, at the last tick of a window, the window's close and ONE refill launch on the look-ahead stream for everything it consumed.
 struct TickPos { int wb, pos; };

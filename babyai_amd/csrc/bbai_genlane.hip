@@ -1,5 +1,5 @@
 // bbai_genlane.hip -- k_pregen_lane, the look-ahead level generator with ONE LANE = ONE LEVEL (bbai_genl.hpp), in a translation unit of
-// its own because it is compiled with `-mllvm -disable-machine-cse`.
+// its own so that it compiles side by side with bbai_engine.hip.  It must be built with `-mllvm -disable-machine-cse`.
 //
 // Why.  ROCm 7.2's backend miscompiles this kernel at -O2 / -O3: with machine-CSE on, LevelGen.rand_obj takes the `rand_bool()` draw of
 // `if (cfg.locations && rand_bool())` in SOME trips of its loop although cfg.locations is 0 -- one extra draw, the env's stream shifted for
@@ -7,7 +7,7 @@
 // tools/genl_check.hip (this header on the device against the same header on the host), pinned by `-mllvm -opt-bisect-limit`: the first bad
 // pass execution is "machine-cse on k_check" (profiles/r06/NOTES.md section 2).  -O1, or -O3 without that pass, generate every level of every
 // covered kind exactly as the host does (tests/test_gpu_lane_generator.py keeps it that way: the product kernel against the lane-group
-// kernel on every covered level).  The rest of the engine keeps the pass.
+// kernel on every covered level).  The build gives the flag to the whole library (the lane-group generator k_pregen needs it as well).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>

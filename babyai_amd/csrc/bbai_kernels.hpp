@@ -1,12 +1,40 @@
-// bbai_kernels.hpp -- what the engine's translation units share on the device side: the look-ahead ring's addressing, the refill list's
-// shape, the lane-group context of the generators.  (bbai_engine.hip: every kernel but one, with the headers it includes
-// for a kernel family each -- bbai_render.hpp, bbai_demo.hpp; bbai_genlane.hip: k_pregen_lane, compiled with its own flags -- see there.)
+// bbai_kernels.hpp -- what the engine's translation units and kernel headers share on the device side: the 16-byte vector type, the view's
+// cell count, the windows' bookkeeping and its constants, the look-ahead ring's addressing and the live record of both state layouts, the
+// refill list's shape, the lane-group context of the generators.  A definition that one kernel family alone uses is in that family's header.
+// (bbai_engine.hip: the host side; it includes a header per kernel family -- bbai_stepk.hpp, bbai_pregen.hpp, bbai_ring.hpp, bbai_botk.hpp,
+// bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbai_types.hpp"
 
 namespace bbai {
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int CELLS = VIEW * VIEW;
+constexpr int AGENT_CELL = 3 * VIEW + 6;                        // the agent's own cell of the view: (3, 6) (tile_id in bbai_render.hpp, step_dirty in bbai_stepk.hpp)
+static_assert(AGENT_CELL == 3 * VIEW + 6, "the agent stands in the middle of the view's last row");
+
+// ---- the windows' bookkeeping: no lists, no same-address atomics on the step path -----------------------------------------------
+// Rounds 1-4 compacted the finished envs of every tick into a window list for the refill (one RETURNING atomic per stepping wave
+// on ONE address: ~2 700 of them per step at 262 144 reset-heavy envs, served at ~11 ns each -- half of that k_step's time) and made
+// the step stream wait, at the start of window w + 2, for the refill of window w (an env MIGHT finish on every tick).  Now:
+//   * what a stepping wave leaves behind is one fire-and-forget add to a sharded total (SHARDS cache lines) and per-env bytes; the
+//     refill's work list is built where it costs nothing: k_compact, on the look-ahead stream in front of k_pregen, turns the window's
+//     `pending` bytes (n bytes per B ticks) into SHARDS dense sub-lists (one returning atomic per 64 envs that hold a finished one,
+//     spread over SHARDS counters), which k_pregen walks as ONE list through a prefix of the sub-counts -- the same perfectly
+//     balanced entry-per-group distribution as before.  (Letting the generator's groups scan the bytes themselves was measured
+//     first -- lease r05a: a group then finds 0 to 4 envs where its neighbour finds one, a wave lives as long as its unluckiest
+//     group, and the mazes' steps slowed by 10-30 % under the generator's idle lanes.)
+//   * every window records M = the most often ONE env finished in it (1 unless short episodes repeat inside a window: the
+//     rare atomicMax in the consume paths); an env's unrefilled slots are <= the sum of M over the windows whose refill has not
+//     landed, so window x may start as soon as that sum is <= B (every env then still has B ready levels, and a window consumes
+//     at most B) -- k_gate, one wave on the step stream at every window start, waits for exactly that instead of for "refill
+//     w - 2 has landed".  A reset storm (a million maze envs timing out on the same tick: 37 ms of generator time) then runs
+//     UNDER the following windows instead of stopping the step stream, as long as no env finishes B more times meanwhile.
+//   * NWIN = 34 window buffers (pending / first_slot / meta): up to 33 refills can be outstanding (B + 1 of them for B <= 32).
+// tests/test_ring_protocol.py models the rule (sufficient, and the ring depths stay tight).
+constexpr int NWIN = 34;                // window buffers (above): at most 33 refills outstanding, whatever B
 constexpr int META_U32 = 32;            // uint32 per window buffer's meta line: [0] = M when > 1 (atomicMax)
 constexpr int SHARDS = 64;              // cache lines the reset total is spread over (k_step: shard = block & 63)
 constexpr int SHARD_U64 = 16;           // uint64 per shard: one 128-byte line each
@@ -18,6 +46,23 @@ __host__ __device__ __forceinline__ int64_t gen_sublist_cap(int64_t n) { return 
 // lie together.  (Slot-major, rounds 1-4a, put the 64 envs of a stepping wave into up to 64 regions n * rec_bytes apart as soon as
 // the live records are ring slots: profiles/r04/inplace_ring_depth_ab.jsonl, k_step 0.029 -> 0.035 ms from D = 5 to D = 65.)
 __device__ __forceinline__ int64_t ring_at(int slot, int64_t env, int depth) { return env * depth + slot; }
+
+// ---- the in-place layout (bbai_env::inplace, chosen at bbai_create) ------------------------------------------------------------
+// Classic layout: every env has a live record of its own (rec[env]); a finished env's next level is COPIED out of its look-ahead
+// slot (1.3 - 1.7 KB + the window plane), by a k_consume launch behind every step or by the stepping wave.  On reset-heavy small
+// shards (single rooms: 2 % of the envs finish on every step) that second dependent launch is 40 % of a step (profiles/r04/NOTES.md
+// section 2), and doing its work inside the stepping waves costs more than the launch.  In-place layout: the live record of an env
+// IS the ring slot its episode was generated into -- the slot BEFORE hot.slot -- and a finished env just moves on to the next
+// slot: nothing is copied, the stepping LANE loads the new pose and program (one round trip), emits the first observation with the
+// step's own window pipeline and swaps the SoA state.  The ring is one slot deeper (2B + 1: the live one + the 2B look-ahead
+// levels of the classic ring); the slot an episode leaves is the one the window's refill regenerates.  rec[] stays allocated as the
+// staging area of export / import / checkpoints.  No window plane in this layout (the window comes out of the record's appearance
+// plane: measures equal on the shards this is for).
+__device__ __forceinline__ int live_slot(int next_slot, int depth) { return (next_slot ? next_slot : depth) - 1; }
+__device__ __forceinline__ uint8_t* live_rec(const LevelCfg& c, int64_t n, int64_t env, uint8_t* recs, uint8_t* ring, int depth, int next_slot) {
+    (void)n;
+    return ring ? ring + ring_at(live_slot(next_slot, depth), env, depth) * (int64_t)c.rec_bytes : recs + env * (int64_t)c.rec_bytes;
+}
 
 // One env per group of G lanes, 64 / G envs per wavefront (bbai_gen.hpp "Execution model").  sync() orders the group's LDS
 // accesses: it is reached under divergent control flow (the groups of a wave are in different places of the generator),

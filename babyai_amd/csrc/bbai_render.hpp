@@ -7,8 +7,8 @@
 // stands, because the shared form changed the compiler's register counts: phase A in k_render_delta's piece branch, B1 in k_render_dstore.
 //
 // The first part is plain C++ -- the geometry of a frame in memory, which the host tests read through tests/hostsim (hs_line_cells).  The
-// kernels below it are part of bbai_engine.hip's translation unit: they are included where they stood (after its u32x4, CELLS and AGENT_CELL)
-// and stay at global scope -- the resource report, bench.py and tools/summarize_profile.py find them by their bare names.  The launches
+// kernels below it are part of bbai_engine.hip's translation unit: they are included where they stood and stay at global scope (u32x4, CELLS
+// and AGENT_CELL come from bbai_kernels.hpp) -- the resource report, bench.py and tools/summarize_profile.py find them by their bare names.  The launches
 // are bbai_engine.hip's (render_launch).
 #pragma once
 #include "bbai_types.hpp"
@@ -84,6 +84,10 @@ struct Pieces {
 }  // namespace bbai
 
 #if defined(__HIPCC__)
+#include "bbai_kernels.hpp"
+
+using namespace bbai;
+
 // ------------------------------------------------------------------------------------------
 // k_render : encoded obs -> 56x56x3 pixels through the tile atlas
 // ------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define BB_HD __host__ __device__ __forceinline__
 #define BB_COLD __host__ __device__ __attribute__((noinline))      // rare and large: ONE copy per kernel instead of one per call site
 #define BB_COLD_FN inline __host__ __device__ __attribute__((noinline))     // ... for a plain (non-template) function in a header

@@ -708,7 +708,7 @@ class BatchedBabyAIEnv(object):
         return hot[:, 6].astype(np.int32) | (hot[:, 7].astype(np.int32) << 8)
 
     def gate_timeouts(self):
-        """Window gates that gave up waiting for a look-ahead refill (bbai_engine.hip k_gate): must be 0 -- anything else means a
+        """Window gates that gave up waiting for a look-ahead refill (bbai_ring.hpp k_gate): must be 0 -- anything else means a
         refill was lost and the batch's results are void.  Synchronises."""
         return self.get_option("gate_timeouts")
 

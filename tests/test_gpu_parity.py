@@ -448,7 +448,7 @@ def test_evaluate_policy_tensor_path(gpu):
 
 def _consume_mode(monkeypatch, mode):
     """How finished envs get their next level: "0" = k_consume launch, "1" = inside k_step by the stepping wave, "inplace" = the in-place
-    state layout (the look-ahead slot IS the live record; bbai_engine.hip live_slot)."""
+    state layout (the look-ahead slot IS the live record; bbai_kernels.hpp live_slot)."""
     if mode == "inplace":
         monkeypatch.setenv("BBAI_INPLACE", "1")
     else:
@@ -1547,7 +1547,7 @@ def test_options_do_not_change_results(gpu):
 @pytest.mark.parametrize("level,n,period", [("GoToObjS4", 20000, "4"), ("GoTo", 6000, "2"), ("PickupLoc", 30000, None)])
 def test_steps_run_ahead_of_a_reset_storms_refill(gpu, level, n, period, layout, monkeypatch):
     """The step stream no longer waits for the refill of window w at the start of window w + 2: it runs on while every env is sure to
-    keep a window's worth of ready levels (bbai_engine.hip k_gate).  A reset command to EVERY env on one tick (a storm: one long
+    keep a window's worth of ready levels (bbai_ring.hpp k_gate).  A reset command to EVERY env on one tick (a storm: one long
     refill) followed at once by many windows of ordinary steps, every few windows another storm, a tick on which a quarter of the envs
     reset again inside the same window (M = 2), and stretches of resets on every tick (the worst case: the gate degenerates to the old
     rule) -- against a second batch that runs the old rule (gate_strict) and, for scattered envs, against the oracle."""

@@ -1,7 +1,7 @@
 """The look-ahead ring's window protocol as a model (host logic, no GPU): why D = 2B slots are enough for the classic state layout and
 D = 2B + 1 for the in-place one, and why the step stream may run AHEAD of the refills as far as k_gate lets it
-(babyai_amd/csrc/bbai_engine.hip: window_begin / window_end, k_gate / k_compact / k_mark, consume_env, advance_finish, k_pregen;
-DESIGN.md section 5).
+(babyai_amd/csrc/: window_begin / window_end in bbai_engine.hip, k_gate / k_compact / k_mark in bbai_ring.hpp, consume_env / advance_finish in
+bbai_stepk.hpp, k_pregen in bbai_pregen.hpp, the rule itself at NWIN in bbai_kernels.hpp).
 
 The engine generates every env's levels ahead of need into a ring of D slots.  Consume-ticks (one reset() or one auto-resetting step)
 are grouped into windows of B ticks; at the end of window w ONE refill launch regenerates the slots the window freed (per env:
@@ -25,7 +25,7 @@ and that a ring ONE slot shallower, or a gate that admits a sum of B + 1, breaks
 import numpy as np
 import pytest
 
-NWIN = 34            # bbai_engine.hip NWIN (MAX_PERIOD = 64 since round 6: at most 33 refills outstanding whatever B)
+NWIN = 34            # bbai_kernels.hpp NWIN (bbai_engine.hip MAX_PERIOD = 64 since round 6: at most 33 refills outstanding whatever B)
 
 
 class Env:
@@ -45,7 +45,7 @@ class Env:
         self.first_slot = [0] * nwin
 
     def live(self):
-        return (self.next - 1) % self.D     # in-place: the slot the current episode lives in (bbai_engine.hip live_slot)
+        return (self.next - 1) % self.D     # in-place: the slot the current episode lives in (bbai_kernels.hpp live_slot)
 
     def finish(self, wb):
         s = self.next

@@ -12,7 +12,7 @@
 #include "../babyai_amd/csrc/bbai_seed.hpp"
 using namespace bbai;
 constexpr int G = 32;
-struct ProfCtx {                                   // bbai_engine.hip GroupCtx<32> + the profiling hooks
+struct ProfCtx {                                   // bbai_kernels.hpp GroupCtx<32> + the profiling hooks
     static constexpr int kLanes = G;
     static constexpr bool kProfile = true;
     __device__ __forceinline__ int lane() const { return (int)threadIdx.x & (G - 1); }

@@ -1,6 +1,6 @@
 // ubench_listatomic.hip -- what one list atomic per stepping wave costs, and what reading NEXT to it costs.  (experiment for round 5)
 //
-// k_step appends a wave's finished envs to a list with ONE returning atomicAdd per wave (bbai_engine.hip, "compact finished envs into
+// k_step appends a wave's finished envs to a list with ONE returning atomicAdd per wave (bbai_stepk.hpp, "compact finished envs into
 // the reset list"); on reset-heavy batches nearly every wave has one (PickupLoc 262 144 envs: ~2 700 of 4 096 waves per step).  Round 4
 // found (profiles/r04/NOTES.md section 11) that a plain LOAD of the same cache line by every wave -- the window's count block,
 // win_prefix -- queued behind those atomics and, loads returning in order, held up everything the wave loaded after it: k_step 0.094 ms
