@@ -19,6 +19,7 @@
 //                     k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
 //                     the buffer holds are stored.  (render_launch)
 //   bbai_gridk.hpp    k_render_grid<TS>: the full-grid picture; k_full_obs: the fully observable encoding.  (render_grid_launch, full_launch)
+//   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32.  (render_view_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
 //   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch: demonstrations that stay on the device.
@@ -223,6 +224,9 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* grid_lut[3];     // [2][5][256]
     int grid_tiles[3];        // installed tiles (0: none)
     int grid_bpc;             // "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
+    uint8_t* view_atlas[2];   // the 7x7 view's picture (bbai_set_view_atlas), tile sizes 16 / 32: [VIEWPX_MAX_TILES + 1][ts][ts][3]
+    uint8_t* view_lut[2];     // [2][256]
+    int view_tiles[2];        // installed tiles (0: none)
     bool seeded, live;
     uint8_t* bot_state;   // [n][bot_state_bytes(bot_stack)] the expert's per-env plan (bbai_bot_act; allocated on first use)
     int bot_stack;        // subgoal stack capacity per env (BBAI_BOT_STACK, default 48)
@@ -240,6 +244,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_botk.hpp"
 #include "bbai_render.hpp"
 #include "bbai_gridk.hpp"
+#include "bbai_viewpx.hpp"
 #include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
 
@@ -572,6 +577,7 @@ void bbai_destroy(bbai_env* e) {
                     e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow, e->rt_dmask};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int k = 0; k < 3; ++k) { if (e->grid_atlas[k]) (void)hipFree(e->grid_atlas[k]); if (e->grid_lut[k]) (void)hipFree(e->grid_lut[k]); }
+    for (int k = 0; k < 2; ++k) { if (e->view_atlas[k]) (void)hipFree(e->view_atlas[k]); if (e->view_lut[k]) (void)hipFree(e->view_lut[k]); }
     if (e->host_flags) (void)hipHostFree((void*)e->host_flags);
     delete e;
 }
@@ -1286,6 +1292,73 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     if (k == 0) render_grid_launch<8>(e, highlight, ids, count, out, s);
     else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
     else render_grid_launch<32>(e, highlight, ids, count, out, s);
+    HIP_TRY(hipGetLastError());
+    return call.leave();
+}
+
+}  // extern "C"
+
+// ---- the 7x7 view as pixels at tile sizes 16 / 32 (k_view_pixels) ----
+static int view_ts_index(int ts) { return ts == 16 ? 0 : ts == 32 ? 1 : -1; }
+
+extern "C" {
+
+int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_tiles, const uint8_t* lut) {
+    const int k = view_ts_index(tile_size);
+    if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
+    if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_set_atlas)");
+    if (n_tiles < 1 || n_tiles > VIEWPX_MAX_TILES) ARG_FAIL("tile count out of range");
+    for (int i = 0; i < VIEWPX_LUT_BYTES; ++i)
+        if (lut[i] >= n_tiles) ARG_FAIL("a lut entry names a tile the atlas does not hold");
+    ON_DEVICE(e->device);
+    const size_t tb = (size_t)tile_size * tile_size * 3;
+    HIP_TRY(hipDeviceSynchronize());                 // (a render still in flight may read the atlas being replaced)
+    if (!e->view_atlas[k]) HIP_TRY(hipMalloc((void**)&e->view_atlas[k], (VIEWPX_MAX_TILES + 1) * tb));
+    if (!e->view_lut[k]) HIP_TRY(hipMalloc((void**)&e->view_lut[k], VIEWPX_LUT_BYTES));
+    HIP_TRY(hipMemcpy(e->view_atlas[k], tiles, n_tiles * tb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(e->view_atlas[k] + n_tiles * tb, 0, tb));        // the zero tile: frames of row ids outside [0, rows)
+    HIP_TRY(hipMemcpy(e->view_lut[k], lut, VIEWPX_LUT_BYTES, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    e->view_tiles[k] = n_tiles;
+    return BBAI_OK;
+}
+
+}  // extern "C"
+
+// Launch shape: work items of about 150 KB of frames -- 4 envs at tile size 16, one env at 32, or half an env while there are fewer
+// frames than blocks (a few frames still reach every CU); persistent blocks, two per CU.
+template <int TS>
+static void render_view_launch(bbai_env* e, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    const int k = view_ts_index(TS);
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const int64_t want = (int64_t)cus * 2;
+    ViewPxArgs a;
+    a.image = image; a.rows = rows; a.ids = ids; a.count = count; a.out = out;
+    a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
+    a.envs_per_item = TS == 16 ? VIEWPX_MAX_ENVS : 1;
+    a.slices = TS == 32 && count < want ? 2 : 1;
+    a.items = a.slices > 1 ? count * a.slices : (count + a.envs_per_item - 1) / a.envs_per_item;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, want));
+    hipLaunchKernelGGL((k_view_pixels<TS>), dim3(blocks), dim3(VIEWPX_BLOCK), 0, s, a);
+}
+
+extern "C" {
+
+int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    const int k = view_ts_index(tile_size);
+    if (!e) ARG_FAIL("null handle");
+    if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_render)");
+    if (rows < 0 || count < 0 || (!ids && count > rows)) ARG_FAIL("row count out of range");
+    if (count > 0 && rows > 0 && !image) ARG_FAIL("encoded buffer missing");
+    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
+    if (!e->view_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_view: no atlas for tile size %d (bbai_set_view_atlas)", tile_size); return BBAI_ERR_STATE; }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s);
+    else render_view_launch<32>(e, image, rows, ids, count, out, s);
     HIP_TRY(hipGetLastError());
     return call.leave();
 }

@@ -23,6 +23,7 @@ from . import missions
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBAI_ENGINE_LIB") or os.path.join(_HERE, "libbbai_hip.so")      # (override: experiment builds)
 ATLAS_PATH = os.path.join(_HERE, "data", "tile_atlas_ts8.npz")
+VIEW_ATLAS_PATH = os.path.join(_HERE, "data", "tile_atlas_ts%d.npz")      # the 7x7 view's picture, per tile size (8: tracked; 16 / 32: written by build() with tools/gen_atlas.py --tile-size)
 GRID_ATLAS_PATH = os.path.join(_HERE, "data", "grid_atlas_ts%d.npz")      # full-grid picture, per tile size (written by build(): tools/gen_grid_atlas.py)
 GRID_TILE_SIZES = (8, 16, 32)
 
@@ -39,10 +40,11 @@ class EngineError(RuntimeError):
 
 
 def check_tile_size(tile_size):
-    """RGBImgObsWrapper's tile size, checked before any device work: the engine has atlases for GRID_TILE_SIZES only."""
+    """RGBImgObsWrapper's / RGBImgPartialObsWrapper's tile size, checked before any device work: the engine has atlases for
+    GRID_TILE_SIZES only."""
     ts = int(tile_size)
     if ts != tile_size or ts not in GRID_TILE_SIZES:
-        raise ValueError("tile_size %r: the engine has atlases for %s only (tools/gen_grid_atlas.py makes them)" % (tile_size, GRID_TILE_SIZES))
+        raise ValueError("tile_size %r: the engine has atlases for %s only (tools/gen_grid_atlas.py, tools/gen_atlas.py make them)" % (tile_size, GRID_TILE_SIZES))
     return ts
 
 
@@ -79,6 +81,9 @@ def load_library():
     if hasattr(lib, "bbai_render_grid"):
         lib.bbai_set_grid_atlas.argtypes = [P, I32, P, I32, P]
         lib.bbai_render_grid.argtypes = [P, I32, I32, P, I64, P, P]
+    if hasattr(lib, "bbai_render_view"):
+        lib.bbai_set_view_atlas.argtypes = [P, I32, P, I32, P]
+        lib.bbai_render_view.argtypes = [P, I32, P, I64, P, I64, P, P]
     if hasattr(lib, "bbai_observe_full"):
         lib.bbai_observe_full.argtypes = [P, P, I64, P, P]
         lib.bbai_step_full.argtypes = [P, P, P, P, P, P, P, I32, P, P]
@@ -125,7 +130,7 @@ EXPORTED_SYMBOLS = (
     "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
     "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
-    "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch",
+    "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch", "bbai_set_view_atlas", "bbai_render_view",
 )
 
 
@@ -195,7 +200,7 @@ class BatchedBabyAIEnv(object):
     env_id : 'BabyAI-<Level>-v0' or '<Level>' (babyai/levels/levelgen.py:480)
     num_envs : number of parallel envs on this device
     device : torch device string / index (a ROCm GPU)
-    pixel : apply RGBImgPartialObsWrapper semantics (obs image uint8[N,56,56,3])
+    pixel : apply RGBImgPartialObsWrapper semantics (obs image uint8[N, 7*tile_size, 7*tile_size, 3]: [N,56,56,3] at the default 8)
     auto_reset : True = ParallelEnv protocol (penv.py:8-11); False = ManyEnvs protocol
                  (evaluate.py:73-81: finished envs freeze until reset())
     done_actions : the reference's BABYAI_DONE_ACTIONS verifier mode (babyai/levels/verifier.py:17,216-230: an instruction
@@ -206,7 +211,11 @@ class BatchedBabyAIEnv(object):
                  or RGBImgObsWrapper's uint8[N, H*tile_size, W*tile_size, 3] (pixel=True: render('rgb_array', highlight=False)); the
                  obs dict then has no use for 'direction', which the list-of-dicts adapters leave out as the wrappers do.  The 7x7
                  `image`, `direction`, rewards and dones are computed and kept as without it
-    tile_size : RGBImgObsWrapper's tile size with full_obs=True, pixel=True: 8, 16 or 32
+    tile_size : the pixel wrappers' tile size, 8, 16 or 32 (anything else with pixel=True: ValueError) -- RGBImgObsWrapper's with
+                 full_obs=True, RGBImgPartialObsWrapper's without.  The partial view at 8 is the 56x56 path with its delta render
+                 (9.4 KB per env per frame); at 16 / 32 `pixels` is uint8[N,112,112,3] / [N,224,224,3], every frame is drawn whole
+                 (include/bbai.h bbai_render_view: no delta render at these sizes) and a batch costs 37.6 KB / 150.5 KB per env per
+                 frame -- 65 536 envs at 32 are 9.9 GB
     validate_actions : check every step()'s actions on the device first and raise AssertionError("unknown action") like
                  the reference (gym_minigrid MiniGridEnv.step) instead of treating bytes 8..255 as `done` (include/bbai.h);
                  costs one reduction and a host synchronisation per step, so it is off by default
@@ -217,7 +226,7 @@ class BatchedBabyAIEnv(object):
         import torch
         self.torch = torch
         self.full_obs = bool(full_obs)
-        self.tile_size = check_tile_size(tile_size) if self.full_obs and pixel else int(tile_size)
+        self.tile_size = check_tile_size(tile_size) if pixel else int(tile_size)
         if not torch.cuda.is_available():
             raise EngineError("no ROCm GPU visible: the batched engine has no CPU path")
         self.lib = load_library()
@@ -251,6 +260,12 @@ class BatchedBabyAIEnv(object):
                 c, ts = self.cfg, self.tile_size
                 shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
                 self.full = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+            elif self.pixel and self.tile_size != 8:
+                # RGBImgPartialObsWrapper(env, 16 | 32): whole frames by bbai_render_view -- no bbai_set_atlas, no registered target
+                ts = self.tile_size
+                self.pixels = torch.zeros((n, 7 * ts, 7 * ts, 3), dtype=torch.uint8, device=self.device)
+                self._view_atlases = set()
+                self._install_view_atlas(ts)
             elif self.pixel:
                 self.pixels = torch.zeros((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
                 atlas = np.load(ATLAS_PATH)
@@ -264,6 +279,7 @@ class BatchedBabyAIEnv(object):
         self._missions = None
         self._obs_version = 0
         self._grid_atlases = set()      # tile sizes whose full-grid atlas is installed on the handle (render_grid)
+        self._view_atlases = getattr(self, "_view_atlases", set())      # ... whose view atlas is (render_view; 16 / 32)
         self.kernel_events = None      # bench.py: list of (tag, start_event, end_event) when enabled
         self.num_actions = 7
         self.max_mission_tokens = min(TOK_MAX, missions.max_mission_tokens(self.cfg))
@@ -311,6 +327,11 @@ class BatchedBabyAIEnv(object):
             img = self.full
         elif self.pixel and rendered:
             img = self.pixels
+        elif self.pixel and self.tile_size != 8:
+            ev = self._ev_begin()
+            self._render_view_into(self.image, None, self.num_envs, self.tile_size, self.pixels)
+            self._ev_end("render", ev)
+            img = self.pixels
         elif self.pixel:
             ev = self._ev_begin()
             _check(self.lib, self.lib.bbai_render(self.handle, self.image.data_ptr(), self.pixels.data_ptr(),
@@ -321,13 +342,88 @@ class BatchedBabyAIEnv(object):
         self._missions = Missions(self)
         return {"image": img, "direction": self.direction, "mission": self._missions}
 
-    def render_encoding(self, image=None, out=None):
-        """RGBImgPartialObsWrapper.observation for ANY encoded batch uint8[N,7,7,3] on the device (default: the current
-        one) -> uint8[N,56,56,3] (include/bbai.h bbai_render).  step() / reset() already return pixels in pixel mode; this
-        is for stored or hand-made encodings."""
+    def render_encoding(self, image=None, out=None, tile_size=None):
+        """RGBImgPartialObsWrapper(env, tile_size).observation for ANY encoded batch uint8[N,7,7,3] on the device (default: the current
+        one) -> uint8[N,7ts,7ts,3], at the batch's tile size or the one given (include/bbai.h bbai_render at 8 -> [N,56,56,3];
+        bbai_render_view at 16 / 32, any number of rows, `out` allocated when there is none of that shape).  step() / reset() already
+        return pixels in pixel mode; this is for stored or hand-made encodings."""
         image = self.image if image is None else image
+        ts = self.tile_size if tile_size is None and self.pixel and not self.full_obs else 8 if tile_size is None else check_tile_size(tile_size)
+        if ts != 8:
+            torch = self.torch
+            if image.dtype != torch.uint8 or image.device != self.device or not image.is_contiguous() or image.numel() % OBS_BYTES:
+                raise ValueError("image: contiguous uint8[k, 7, 7, 3] on %s" % (self.device,))
+            k = image.numel() // OBS_BYTES
+            if out is None and self.pixels is not None and tuple(self.pixels.shape) == (k, 7 * ts, 7 * ts, 3):
+                out = self.pixels
+            out = self._frames_out(out, (k, 7 * ts, 7 * ts, 3))
+            return self._render_view_into(image, None, k, ts, out)
         out = self.pixels if out is None else out
         _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
+        return out
+
+    def _install_view_atlas(self, ts):
+        if ts in self._view_atlases:
+            return
+        if not hasattr(self.lib, "bbai_render_view"):
+            raise EngineError("this engine library has no bbai_render_view (tile_size %d)" % ts)
+        if not os.path.isfile(VIEW_ATLAS_PATH % ts):
+            raise EngineError("tile atlas %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(tools/gen_atlas.py --tile-size %d)" % (VIEW_ATLAS_PATH % ts, ts))
+        with np.load(VIEW_ATLAS_PATH % ts) as f:
+            tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
+            lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
+        _check(self.lib, self.lib.bbai_set_view_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_view_atlas")
+        self._view_atlases.add(ts)
+
+    def _render_view_into(self, image, ids_ptr, k, ts, out):
+        """bbai_render_view: rows `ids_ptr` (None = the first k) of the encoded buffer `image` -> out uint8[k, 7ts, 7ts, 3]."""
+        self._install_view_atlas(ts)
+        _check(self.lib, self.lib.bbai_render_view(self.handle, ts, image.data_ptr(), image.numel() // OBS_BYTES, ids_ptr, k,
+                                                    out.data_ptr() if k else None, self._stream()), "bbai_render_view")
+        return out
+
+    def render_view(self, ids=None, tile_size=None, out=None):
+        """The agent's view of envs `ids` (None = every env; else an int sequence or an int64 device tensor, any order, repeats allowed) as
+        RGBImgPartialObsWrapper(env, tile_size) draws it, from the current `self.image` -> uint8[k, 7ts, 7ts, 3] on the device,
+        asynchronous on the current stream (include/bbai.h bbai_render_view; tile_size None = the batch's).  Available on any batch, also
+        an encoded one; the atlas of a tile size is installed on first use.  Writes nothing but `out` (37.6 KB a frame at 16, 150.5 KB
+        at 32); an id outside [0, num_envs) gives an all-zero frame.  tile_size=8 goes through bbai_render (56x56 frames)."""
+        torch = self.torch
+        ts = check_tile_size(self.tile_size if tile_size is None else tile_size)
+        k, ids_ptr = self._id_list(ids)
+        out = self._frames_out(out, (k, 7 * ts, 7 * ts, 3))
+        if ts != 8:
+            return self._render_view_into(self.image, ids_ptr, k, ts, out)
+        if k == 0:
+            return out
+        # bbai_render draws num_envs rows into num_envs frames: the listed rows are gathered and go through in runs of num_envs
+        if not (self.pixel and not self.full_obs and self.tile_size == 8) and not getattr(self, "_ts8_atlas", False):
+            with np.load(ATLAS_PATH) as f:
+                tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
+                lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
+            _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_atlas")
+            self._ts8_atlas = True
+        n = self.num_envs
+        with torch.cuda.device(self.dev_index):
+            enc, bad = self.image, None
+            if ids is not None:
+                bad = (self._grid_ids < 0) | (self._grid_ids >= n)
+                enc = self.image[self._grid_ids.clamp(0, n - 1)]
+            keep = []
+            for lo in range(0, k, n):
+                m = min(n, k - lo)
+                src, dst = enc[lo:lo + m], out[lo:lo + m]
+                if m < n:          # a short run: padded on both sides
+                    src = torch.cat([src, torch.zeros((n - m, 7, 7, 3), dtype=torch.uint8, device=self.device)])
+                    dst = torch.empty((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
+                _check(self.lib, self.lib.bbai_render(self.handle, src.data_ptr(), dst.data_ptr(), self._stream()), "bbai_render")
+                if m < n:
+                    out[lo:lo + m] = dst[:m]
+                keep.append((src, dst))
+            self._ts8_runs = keep      # keep alive until the launches are consumed
+            if bad is not None:
+                out[bad] = 0           # an id outside the batch: an all-zero frame, as at 16 / 32
         return out
 
     def render_grid(self, ids=None, tile_size=32, highlight=True, out=None):
@@ -442,7 +538,7 @@ class BatchedBabyAIEnv(object):
                                                       self.done.data_ptr(), 1 if self.auto_reset else 0, self.full.data_ptr(),
                                                       self._stream()), "bbai_step_full")
             return self._obs(rendered=True), self.reward, self.done, {}
-        if self.pixel and not self.full_obs and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
+        if self.pixel and not self.full_obs and self.tile_size == 8 and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
             # the wrapped env's step: transition + render as ONE call (include/bbai.h bbai_step_render)
             _check(self.lib, self.lib.bbai_step_render(self.handle, actions.data_ptr(), self.image.data_ptr(),
                                                         self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
@@ -470,6 +566,9 @@ class BatchedBabyAIEnv(object):
                 or actions.shape[1] != self.num_envs:
             raise ValueError("actions: contiguous uint8[T, %d] on %s" % (self.num_envs, self.device))
         T = int(actions.shape[0])
+        big = self.pixel and not self.full_obs and self.tile_size != 8        # tile sizes 16 / 32: encoded steps, the last frame drawn once
+        if big and tap is not None and tap.get("pixels") is not None:
+            raise ValueError("no pixel tap rows at tile size %d (only at 8)" % self.tile_size)
         log = None
         if tap is not None:
             P_ = int(tap["done"].shape[1])
@@ -486,8 +585,10 @@ class BatchedBabyAIEnv(object):
         self._actions = actions
         _check(self.lib, self.lib.bbai_rollout(self.handle, T, actions.data_ptr(), self.image.data_ptr(), self.direction.data_ptr(),
                                                 self.reward.data_ptr(), self.reward64.data_ptr(), self.done.data_ptr(), 1 if self.auto_reset else 0,
-                                                self.pixels.data_ptr() if self.pixels is not None else None, ctypes.byref(log) if log is not None else None,
+                                                self.pixels.data_ptr() if self.pixels is not None and not big else None, ctypes.byref(log) if log is not None else None,
                                                 self._stream()), "bbai_rollout")
+        if big:
+            self._render_view_into(self.image, None, self.num_envs, self.tile_size, self.pixels)
         if self.full_obs:
             self.observe_full()          # the last step's full observation (the tap log keeps its 7x7 rows)
         self._obs_version += 1

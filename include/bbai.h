@@ -147,6 +147,25 @@ int bbai_set_grid_atlas(bbai_env* env, int tile_size, const uint8_t* tiles_host,
 int bbai_render_grid(bbai_env* env, int tile_size, int highlight, const int64_t* ids_dev /* NULL = envs 0..count-1 */,
                      int64_t count, uint8_t* out_dev /* [count][H*ts][W*ts][3] */, void* stream);
 
+/* The agent's 7x7 view as pixels at tile sizes 16 and 32: RGBImgPartialObsWrapper(env, tile_size).observation (gym_minigrid
+ * wrappers.py; scripts/manual_control.py --agent_view, and 7 x 32 = 224 / 7 x 16 = 112 pixel inputs of image models).  Tile size 8 is
+ * bbai_set_atlas / bbai_render (and the delta render); there is no delta render at these sizes.
+ * bbai_set_view_atlas installs the tile atlas of one tile size (babyai_amd/data/tile_atlas_ts<size>.npz, made by tools/gen_atlas.py
+ * --tile-size): tiles uint8[n_tiles][ts][ts][3], n_tiles <= 64, and lut[agent cell][key] as bbai_set_atlas takes it (row 0 = ordinary
+ * view cell, row 1 = the agent's cell (3, 6); key = type | colour << 3 | state << 6, taken & 255); synchronous.  A handle keeps the atlas
+ * of each size installed on it.  BBAI_ERR_ARG for a tile size other than 16 / 32, a tile count out of range or a lut entry >= n_tiles.
+ * bbai_render_view reads rows of an ENCODED observation buffer image_dev uint8[rows][147] (indexed [x][y][3]: the caller's buffer, not
+ * engine state -- the current observations or stored ones) and writes frame k = the picture of row ids_dev[k] (int64 device array;
+ * NULL = rows 0 .. count - 1) into out_dev + k * 147 * ts * ts (16-byte aligned): uint8[7 ts][7 ts][3], pixel [row = view y][column =
+ * view x][rgb] -- 37 632 bytes a frame at 16, 150 528 at 32.  It writes nothing but out_dev; asynchronous on `stream`, ordered like
+ * every other call of the handle.  An id outside [0, rows) yields an all-zero frame, never an out-of-bounds read.  BBAI_ERR_STATE
+ * without an atlas of that tile size; BBAI_ERR_ARG for a tile size other than 16 / 32, count < 0, count > rows without ids, or a
+ * missing / misaligned out_dev. */
+int bbai_set_view_atlas(bbai_env* env, int tile_size, const uint8_t* tiles_host, int n_tiles, const uint8_t* lut_host /* [2][256] */);
+int bbai_render_view(bbai_env* env, int tile_size, const uint8_t* image_dev /* [rows][147] */, int64_t rows,
+                     const int64_t* ids_dev /* NULL = rows 0..count-1 */, int64_t count, uint8_t* out_dev /* [count][7*ts][7*ts][3] */,
+                     void* stream);
+
 /* The fully observable encoding: FullyObsWrapper.observation (gym_minigrid wrappers.py; restated in
  * oracle/shim/gym_minigrid/wrappers.py:39-56) -- grid.encode() of the whole W x H grid, indexed [x][y], cell = (type, colour,
  * state), the agent's cell overwritten with (10 = agent, 0 = red, agent_dir) -- on the device.

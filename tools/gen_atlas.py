@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Generate the 8-pixel tile atlas used by the k_render kernel (RGBImgPartialObsWrapper path).
+"""Generate the tile atlases of the agent's 7x7 view (RGBImgPartialObsWrapper path): the 8-pixel one used by the k_render
+kernels, the 16- and 32-pixel ones used by k_view_pixels.
 
 Tiles are rasterised by the ORACLE's restated gym_minigrid renderer
-(oracle/shim/gym_minigrid/minigrid.py Grid.render_tile, tile_size=8, 3x supersampling) and
-committed as data (babyai_amd/data/tile_atlas_ts8.npz); the product only loads the file.
-Re-run:  python tools/gen_atlas.py
+(oracle/shim/gym_minigrid/minigrid.py Grid.render_tile, 3x supersampling) and
+written to babyai_amd/data/tile_atlas_ts<size>.npz; the product only loads the files.  The tile-size-8 file is tracked; the 16 and 32
+ones are build products (build() runs this tool) whose arrays tests/golden/view_atlas/ pins.
+Re-run:  python tools/gen_atlas.py [--tile-size 8|16|32]      (default 8)
 
-Layout: tiles uint8[n_tiles, 8, 8, 3]; lut uint8[2, 256] indexed by
+Layout: tiles uint8[n_tiles, ts, ts, 3]; lut uint8[2, 256] indexed by
 key = type | colour << 3 | state << 6 of the encoded observation cell
 (lut[0] = ordinary view cell, lut[1] = the agent's own cell (3,6) which shows the carried
 object under the agent triangle).  Unknown keys map to tile 0 (unseen / un-highlighted empty).
 """
+import argparse
 import os
 import sys
 
@@ -24,14 +27,14 @@ refenv.enable_shim()
 from gym_minigrid.minigrid import (COLOR_TO_IDX, IDX_TO_COLOR, OBJECT_TO_IDX, Grid, WorldObj)  # noqa: E402
 
 
-def tile_u8(obj, agent_dir, highlight):
-    t = Grid.render_tile(obj, agent_dir=agent_dir, highlight=highlight, tile_size=8)
-    out = np.zeros((8, 8, 3), dtype=np.uint8)
-    out[:, :, :] = t          # same float -> uint8 assignment as Grid.render
-    return out
+def atlas(ts=8):
+    """(tiles uint8[n_tiles, ts, ts, 3], lut uint8[2, 256]) at tile size `ts`."""
+    def tile_u8(obj, agent_dir, highlight):
+        t = Grid.render_tile(obj, agent_dir=agent_dir, highlight=highlight, tile_size=ts)
+        out = np.zeros((ts, ts, 3), dtype=np.uint8)
+        out[:, :, :] = t          # same float -> uint8 assignment as Grid.render
+        return out
 
-
-def main():
     tiles = [tile_u8(None, None, False)]          # tile 0: unseen
     lut = np.zeros((2, 256), dtype=np.uint8)
 
@@ -58,8 +61,15 @@ def main():
     for name in ('key', 'ball', 'box'):
         for c in range(6):
             lut[1, key(OBJECT_TO_IDX[name], c, 0)] = add(tile_u8(WorldObj.decode(OBJECT_TO_IDX[name], c, 0), 3, True))
-    tiles = np.stack(tiles)
-    out = os.path.join(ROOT, 'babyai_amd', 'data', 'tile_atlas_ts8.npz')
+    return np.stack(tiles), lut
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument('--tile-size', type=int, default=8, choices=(8, 16, 32))
+    args = ap.parse_args()
+    tiles, lut = atlas(args.tile_size)
+    out = os.path.join(ROOT, 'babyai_amd', 'data', 'tile_atlas_ts%d.npz' % args.tile_size)
     np.savez_compressed(out, tiles=tiles, lut=lut)
     print('wrote', out, tiles.shape, 'tiles')
 
