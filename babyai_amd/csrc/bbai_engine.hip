@@ -23,6 +23,7 @@
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
 //   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch: demonstrations that stay on the device.
+//   bbai_statek.hpp   k_state_save / k_state_load / k_state_tokens: device snapshots of listed envs (bbai_save_state, bbai_load_state).
 //
 // Reference semantics: see bbai_step.hpp / bbai_gen.hpp / bbai_bot.hpp headers for file:line citations.
 #include <hip/hip_runtime.h>
@@ -247,6 +248,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_viewpx.hpp"
 #include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
+#include "bbai_statek.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -2140,6 +2142,54 @@ int bbai_reset_count(bbai_env* e, uint64_t* out) {
     for (int k = 0; k < SHARDS; ++k) v += shards[k * SHARD_U64];
     *out = (uint64_t)v;
     return BBAI_OK;
+}
+
+
+// ---- device snapshots (bbai_statek.hpp): the live state of listed envs, out and back in, as launches on the caller's stream ----------------
+// (They close this file on purpose: bbai_statek.hpp says why.)  Neither is a consume-tick: the look-ahead ring, the windows' bookkeeping, e->tick, the RNG streams and the gate stay as they are.
+static unsigned state_grid(int64_t count) { return (unsigned)std::min<int64_t>((count + 3) / 4, 65536); }        // one wave per list entry
+
+int bbai_save_state(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* rec, uint8_t* hot, uint64_t* stale, uint8_t* lsm, void* stream) {
+    if (!e || count < 0) ARG_FAIL("null handle or negative count");
+    if (count == 0) return BBAI_OK;
+    if (!rec || !hot || !stale) ARG_FAIL("null snapshot buffer");
+    if (((uintptr_t)rec | (uintptr_t)hot) & 15) ARG_FAIL("snapshot records and hot states must be 16-byte aligned");
+    if (!ids && count > e->n) ARG_FAIL("count > n_envs without ids");
+    if (e->cfg.rec_bytes > STATE_MAX_REC || (e->cfg.rec_bytes & 15)) ARG_FAIL("record size not covered by the snapshot kernels");
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "save_state before reset"); return BBAI_ERR_STATE; }
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    hipLaunchKernelGGL(k_state_save<0>, dim3(state_grid(count)), dim3(256), 0, s, e->cfg, e->n, ids, count, e->rec, e->inplace ? e->next_rec : nullptr, e->depth,
+                       e->hot, e->stale, e->lsm, rec, (u32x4*)hot, stale, lsm);
+    HIP_TRY(hipGetLastError());
+    return call.leave();
+}
+
+int bbai_load_state(bbai_env* e, const int64_t* ids, const int64_t* rows, int64_t count, int64_t snap_rows, const uint8_t* rec, const uint8_t* hot,
+                    const uint64_t* stale, const uint8_t* lsm, uint8_t* image, uint8_t* dirs, void* stream) {
+    if (!e || count < 0 || snap_rows < 0) ARG_FAIL("null handle or negative count");
+    if (count == 0) return BBAI_OK;
+    if (!rec || !hot || !stale || !image || !dirs) ARG_FAIL("null snapshot or observation buffer");
+    if (((uintptr_t)rec | (uintptr_t)hot) & 15) ARG_FAIL("snapshot records and hot states must be 16-byte aligned");
+    if (!ids && count > e->n) ARG_FAIL("count > n_envs without ids");
+    if (!rows && count > snap_rows) ARG_FAIL("count > snap_rows without rows");
+    if (e->cfg.rec_bytes > STATE_MAX_REC || (e->cfg.rec_bytes & 15)) ARG_FAIL("record size not covered by the snapshot kernels");
+    if (!e->seeded) { snprintf(g_err, sizeof(g_err), "load_state before seed"); return BBAI_ERR_STATE; }
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    hipLaunchKernelGGL(k_state_load<0>, dim3(state_grid(count)), dim3(256), 0, s, e->cfg, e->n, ids, rows, count, snap_rows, rec, (const u32x4*)hot, stale, lsm,
+                       e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, e->stale, e->lsm, e->vhead, e->vset, e->vplane, e->cplane, e->fcache,
+                       e->bot_state, e->bot_stack, image, dirs);
+    if (e->tokens)
+        hipLaunchKernelGGL(k_state_tokens<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 4096)), dim3(64), 0, s, e->cfg, e->n, ids, rows, count, snap_rows,
+                           e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, e->tokens);
+    HIP_TRY(hipGetLastError());
+    e->live = true;
+    return call.leave();
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // cell count, the windows' bookkeeping and its constants, the look-ahead ring's addressing and the live record of both state layouts, the
 // refill list's shape, the lane-group context of the generators.  A definition that one kernel family alone uses is in that family's header.
 // (bbai_engine.hip: the host side; it includes a header per kernel family -- bbai_stepk.hpp, bbai_pregen.hpp, bbai_ring.hpp, bbai_botk.hpp,
-// bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
+// bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp, bbai_statek.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbai_types.hpp"

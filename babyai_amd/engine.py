@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .levels import make_cfg
+from .levels import level_name, make_cfg
 from . import missions
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -90,6 +90,9 @@ def load_library():
     lib.bbai_set_token_buffer.argtypes = [P, P]
     lib.bbai_export_state.argtypes = [P, I64, I64, P, P, P]
     lib.bbai_import_state.argtypes = [P, I64, I64, P, P, P]
+    if hasattr(lib, "bbai_save_state"):
+        lib.bbai_save_state.argtypes = [P, P, I64, P, P, P, P, P]
+        lib.bbai_load_state.argtypes = [P, P, P, I64, I64, P, P, P, P, P, P, P]
     lib.bbai_get_programs.argtypes = [P, I64, I64, P]
     lib.bbai_tap.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P]
     lib.bbai_tap_ids.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P]
@@ -131,6 +134,7 @@ EXPORTED_SYMBOLS = (
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
     "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
     "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch", "bbai_set_view_atlas", "bbai_render_view",
+    "bbai_save_state", "bbai_load_state",
 )
 
 
@@ -190,6 +194,56 @@ class Missions(object):
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
+
+
+
+class EnvSnapshot(object):
+    """The live state of R envs as four tensors (include/bbai.h bbai_save_state): `rec` uint8[R, rec_bytes], `hot` uint8[R, 16], `stale`
+    int64[R] (the uint64 stale sets' bits), `lsm` uint8[R] (lastStepMatch bytes: done-action mode; zeros otherwise) -- rows as
+    export_state() returns them -- plus the level, record size and verifier mode they belong to.  Valid in any batch of the same level,
+    `rec_bytes` and done-action mode, whatever its size, state layout or look-ahead depth.  Holds no look-ahead levels, no RNG stream and no
+    expert plan.  select / cat / to are torch ops and work on CPU tensors too (a replay buffer of levels may live on the host)."""
+
+    def __init__(self, rec, hot, stale, lsm, env_id, rec_bytes, done_actions):
+        self.rec, self.hot, self.stale, self.lsm = rec, hot, stale, lsm
+        self.env_id, self.rec_bytes, self.done_actions = level_name(env_id), int(rec_bytes), bool(done_actions)
+        r = int(rec.shape[0])
+        if tuple(rec.shape) != (r, self.rec_bytes) or tuple(hot.shape) != (r, 16) or tuple(stale.shape) != (r,) or tuple(lsm.shape) != (r,):
+            raise ValueError("snapshot tensors: rec [R, %d], hot [R, 16], stale [R], lsm [R]" % self.rec_bytes)
+
+    def __len__(self):
+        return int(self.rec.shape[0])
+
+    @property
+    def device(self):
+        return self.rec.device
+
+    def _like(self, rec, hot, stale, lsm):
+        return EnvSnapshot(rec, hot, stale, lsm, self.env_id, self.rec_bytes, self.done_actions)
+
+    def select(self, rows):
+        """The snapshot of rows `rows` (an int sequence or an int64 tensor on the snapshot's device; any order, repeats allowed)."""
+        import torch
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.as_tensor(np.asarray(rows, dtype=np.int64).reshape(-1), device=self.rec.device)
+        return self._like(self.rec[rows].contiguous(), self.hot[rows].contiguous(), self.stale[rows].contiguous(), self.lsm[rows].contiguous())
+
+    @staticmethod
+    def cat(snaps):
+        """One snapshot of the rows of several (same level, record size and done-action mode; same device)."""
+        import torch
+        snaps = list(snaps)
+        if not snaps:
+            raise ValueError("EnvSnapshot.cat of nothing")
+        a = snaps[0]
+        for b in snaps[1:]:
+            if (b.env_id, b.rec_bytes, b.done_actions) != (a.env_id, a.rec_bytes, a.done_actions):
+                raise ValueError("EnvSnapshot.cat: snapshots of %s (rec_bytes %d, done_actions %s) and %s (rec_bytes %d, done_actions %s)"
+                                 % (a.env_id, a.rec_bytes, a.done_actions, b.env_id, b.rec_bytes, b.done_actions))
+        return a._like(*(torch.cat([getattr(x, k) for x in snaps]) for k in ("rec", "hot", "stale", "lsm")))
+
+    def to(self, device):
+        return self._like(self.rec.to(device), self.hot.to(device), self.stale.to(device), self.lsm.to(device))
 
 
 class BatchedBabyAIEnv(object):
@@ -634,6 +688,70 @@ class BatchedBabyAIEnv(object):
         assert rec.shape == (count, self.cfg.rec_bytes) and hot.shape == (count, 16) and stale.shape == (count,)
         _check(self.lib, self.lib.bbai_import_state(self.handle, first, count, rec.ctypes.data, hot.ctypes.data,
                                                      stale.ctypes.data), "bbai_import_state")
+
+    # ---- device snapshots (include/bbai.h bbai_save_state / bbai_load_state) -----------------------------------------
+    def save_state(self, ids=None):
+        """The live state of envs `ids` (None = every env; else an int sequence or an int64 device tensor, any order) as an EnvSnapshot on
+        this batch's device: one launch on the current stream, no host trip.  Row k = env ids[k]; an id outside [0, num_envs) leaves its
+        row zeroed."""
+        torch = self.torch
+        k, ids_ptr = self._id_list(ids)
+        with torch.cuda.device(self.dev_index):
+            u8 = dict(dtype=torch.uint8, device=self.device)
+            snap = EnvSnapshot(torch.zeros((k, self.cfg.rec_bytes), **u8), torch.zeros((k, 16), **u8),
+                               torch.zeros((k,), dtype=torch.int64, device=self.device), torch.zeros((k,), **u8),
+                               self.env_id, self.cfg.rec_bytes, self.done_actions)
+        _check(self.lib, self.lib.bbai_save_state(self.handle, ids_ptr, k, snap.rec.data_ptr(), snap.hot.data_ptr(), snap.stale.data_ptr(),
+                                                   snap.lsm.data_ptr(), self._stream()), "bbai_save_state")
+        return snap
+
+    def _load_args(self, snap, ids, rows):
+        """load_state's checks, before any device work: ValueError for a snapshot of another level, record size or done-action mode, for
+        host-side `ids` with duplicates and for lists of different lengths."""
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("load_state takes an EnvSnapshot")
+        if snap.env_id != level_name(self.env_id):
+            raise ValueError("snapshot of level %s loaded into a batch of %s" % (snap.env_id, level_name(self.env_id)))
+        if snap.rec_bytes != self.cfg.rec_bytes:
+            raise ValueError("snapshot with %d-byte records, this batch has %d" % (snap.rec_bytes, self.cfg.rec_bytes))
+        if snap.done_actions != self.done_actions:
+            raise ValueError("snapshot taken with done_actions=%s, this batch runs with done_actions=%s" % (snap.done_actions, self.done_actions))
+        if ids is not None and not isinstance(ids, self.torch.Tensor):
+            host = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if len(np.unique(host)) != len(host):
+                raise ValueError("load_state: an env is listed twice")
+        k = self.num_envs if ids is None else int(len(ids))
+        kr = len(snap) if rows is None else int(len(rows))
+        if rows is None and ids is None and kr < k:
+            raise ValueError("load_state without ids and rows needs a snapshot of all %d envs, got %d rows" % (k, kr))
+        if (rows is not None or ids is not None) and kr != k:
+            raise ValueError("load_state: %d envs listed for %d rows" % (k, kr))
+        return k
+
+    def load_state(self, snap, ids=None, rows=None):
+        """Put envs `ids` (None = every env) into the states of snapshot rows `rows` (None = row k into ids[k]; else an int sequence or an
+        int64 device tensor, repeats allowed: one row may go into many envs) and return the observation dict as reset() does, the listed
+        envs' rows holding gen_obs() of their loaded states.  One launch on the current stream (+ the batch's render in pixel /
+        full_obs mode); no other env changes, and a loaded env goes on with its own next level when the loaded episode ends.  A snapshot
+        on another device is copied over first.  ValueError: see _load_args; the same env twice in a DEVICE id list is undefined as to
+        which row it gets."""
+        torch = self.torch
+        self._load_args(snap, ids, rows)
+        if snap.device != self.device:
+            snap = snap.to(self.device)
+        tensors = tuple(t.contiguous() for t in (snap.rec, snap.hot, snap.stale, snap.lsm))
+        if tensors[0].dtype != torch.uint8 or tensors[1].dtype != torch.uint8 or tensors[2].dtype != torch.int64 or tensors[3].dtype != torch.uint8:
+            raise ValueError("snapshot tensors: uint8 rec / hot / lsm, int64 stale")
+        k, ids_ptr = self._id_list(ids)
+        ids_keep = self._grid_ids if ids is not None else None
+        rows_ptr = None
+        if rows is not None:
+            _, rows_ptr = self._id_list(rows)
+        self._snap_keep = (tensors, ids_keep, self._grid_ids if rows is not None else None)      # alive until the launch is consumed
+        _check(self.lib, self.lib.bbai_load_state(self.handle, ids_ptr, rows_ptr, k, len(snap), tensors[0].data_ptr(), tensors[1].data_ptr(),
+                                                   tensors[2].data_ptr(), tensors[3].data_ptr(), self.image.data_ptr(),
+                                                   self.direction.data_ptr(), self._stream()), "bbai_load_state")
+        return self._obs()
 
     def save_checkpoint(self):
         """The whole batch as one host blob (np.uint8): live state, RNG streams, look-ahead ring, window bookkeeping,

@@ -153,6 +153,14 @@ class _VecBase(object):
         return iter((self._obs_list(obs), tuple(float(r) for r in reward), tuple(bool(d) for d in done),
                      tuple({} for _ in range(n))))
 
+    def save_state(self, ids=None):
+        """The listed envs' live state as an EnvSnapshot on the device (BatchedBabyAIEnv.save_state)."""
+        return self.engine.save_state(ids)
+
+    def load_state(self, snap, ids=None, rows=None):
+        """Snapshot rows into the listed envs (BatchedBabyAIEnv.load_state); returns the obs list of the whole batch, as reset() does."""
+        return self._obs_list(self.engine.load_state(snap, ids, rows))
+
     def render(self):
         raise NotImplementedError
 

@@ -196,6 +196,33 @@ int bbai_import_state(bbai_env* env, int64_t first, int64_t count, const uint8_t
                       const uint8_t* hot_host, const uint64_t* stale_host);
 int bbai_get_programs(bbai_env* env, int64_t first, int64_t count, uint8_t* prog_host /* 112 B each */);
 
+/* Device snapshots: the live state of LISTED envs out of a handle and back into one, as one launch on `stream` -- no host trip, no
+ * synchronisation, no allocation; ordered like every other call of the handle.  For level replay (keep a level's first state, replay it
+ * later in whichever env is free), look-ahead (one state into seven envs, one action each), backplay and returns to stored states.
+ * A snapshot of R rows is four caller-owned device arrays: rec uint8[R][rec_bytes] and hot uint8[R][16] (both 16-byte aligned), stale
+ * uint64[R] -- row for row the bytes bbai_export_state returns for that env -- and lsm uint8[R], the env's lastStepMatch byte in the
+ * done-action verifier mode (0 otherwise), which is what makes a rewind exact in that mode (bbai_import_state clears it).  It holds an
+ * env's LIVE state only: not its look-ahead ring, not its RNG stream, not the expert's plan.  A snapshot is valid in any handle of the
+ * same level, rec_bytes and done-action mode, whatever its batch size, state layout or ring depth.
+ * bbai_save_state writes row k from env ids_dev[k] (NULL: env k).
+ * bbai_load_state loads row rows_dev[k] (NULL: row k) into env ids_dev[k] (NULL: env k): record, hot state (the env keeps its own place
+ * in its look-ahead ring: hot[15] of the row is ignored), stale set, lastStepMatch; rebuilds what the handle derives from the record
+ * (verifier view, window plane / C plane row, front-cell cache); and writes the env's observation -- gen_obs() of the loaded state -- into
+ * row ids_dev[k] of image_dev uint8[n][147] and dir_dev uint8[n].  It writes no other env's bytes and is no consume-tick: the ring, the
+ * windows' bookkeeping and the RNG streams are untouched, so when the loaded episode ends the env goes on with its OWN next level.
+ * (A snapshot taken right after bbai_reset on a PutNext*Carrying level holds the state AFTER the object was handed to the agent: its
+ * gen_obs() differs from the observation bbai_reset returned in that object's cell and the agent's.)  Where the expert's state is
+ * allocated the env's next bbai_bot_act starts a fresh Bot.  A registered token buffer gets the loaded missions' tokens in the listed
+ * envs' rows.  The registered render target is NOT touched: a caller with one renders afterwards (bbai_render), as after bbai_reset.
+ * An id outside [0, n_envs) or a row outside [0, snap_rows) skips that entry; the same row may go to many envs; the same env listed
+ * twice gets one of its rows, which one is undefined.  count == 0 is a no-op; BBAI_ERR_ARG for a null handle, a null or misaligned
+ * required buffer or a negative count. */
+int bbai_save_state(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..count-1 */, int64_t count, uint8_t* rec_dev, uint8_t* hot_dev,
+                    uint64_t* stale_dev, uint8_t* lsm_dev /* may be NULL */, void* stream);
+int bbai_load_state(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..count-1 */, const int64_t* rows_dev /* NULL = row k */, int64_t count,
+                    int64_t snap_rows, const uint8_t* rec_dev, const uint8_t* hot_dev, const uint64_t* stale_dev,
+                    const uint8_t* lsm_dev /* NULL = zeros */, uint8_t* image_dev, uint8_t* dir_dev, void* stream);
+
 /* Checkpoint / resume of a whole batch (the reference checkpoints only its model, babyai/utils/model.py:29-32; an
  * auto-resetting env batch additionally needs its RNG streams): the blob holds the live state, every env's MT19937
  * stream, the look-ahead ring with its window bookkeeping, the counters and -- when bbai_bot_act has been used -- the
