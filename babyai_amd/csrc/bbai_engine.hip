@@ -24,6 +24,7 @@
 //                     k_gae (bbai_gae).
 //   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch: demonstrations that stay on the device.
 //   bbai_statek.hpp   k_state_save / k_state_load / k_state_tokens: device snapshots of listed envs (bbai_save_state, bbai_load_state).
+//   bbai_reseedk.hpp  k_reseed_seed / k_reseed_consume: env.seed(s); env.reset() for listed envs of a live batch (bbai_reseed).
 //
 // Reference semantics: see bbai_step.hpp / bbai_gen.hpp / bbai_bot.hpp headers for file:line citations.
 #include <hip/hip_runtime.h>
@@ -237,6 +238,14 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int bot_eager;        // BBAI_BOT_EAGER (default 1): expand the first search tree at the top of every decision
     int64_t bot_threads;
     uint64_t* bot_stats;  // [2] decisions that ended in a dead bot: by the reference's rules / by our capacity limits
+    // bbai_reseed's scratch (reseed_scratch: allocated at the first call): a work list and sub-list counters shaped like gen_list / gen_count, a
+    // `pending` / `first_slot` plane of its own, the envs a call has claimed (bbai_reseedk.hpp), and the events that order the call
+    int32_t* rs_list;     // [SHARDS][gen_sublist_cap(n)]
+    uint32_t* rs_count;   // [SHARDS][GEN_COUNT_U32]
+    uint8_t* rs_pending;  // [n] zero between calls (the generator clears what it served)
+    uint8_t* rs_first;    // [n] always zero: a reseeded ring is generated from slot 0
+    uint32_t* rs_claim;   // [(n + 31) / 32] zero between calls
+    hipEvent_t ev_rs_call, ev_rs_done, ev_rs_part[MAX_SIDES];
 };
 
 #include "bbai_stepk.hpp"
@@ -249,6 +258,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
 #include "bbai_statek.hpp"
+#include "bbai_reseedk.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -571,12 +581,16 @@ void bbai_destroy(bbai_env* e) {
     if (e->ev_splitB) (void)hipEventDestroy(e->ev_splitB);
     if (e->ev_consumed) (void)hipEventDestroy(e->ev_consumed);
     if (e->ev_switch) (void)hipEventDestroy(e->ev_switch);
+    if (e->ev_rs_call) (void)hipEventDestroy(e->ev_rs_call);
+    if (e->ev_rs_done) (void)hipEventDestroy(e->ev_rs_done);
+    for (int k = 0; k < MAX_SIDES; ++k) if (e->ev_rs_part[k]) (void)hipEventDestroy(e->ev_rs_part[k]);
     for (int k = 0; k < NWIN; ++k) if (e->ev_refill[k]) (void)hipEventDestroy(e->ev_refill[k]);
     for (int k = 0; k < 3; ++k) for (int i = 0; i < PROF_RING; ++i) if (e->prof[k][i].a) { (void)hipEventDestroy(e->prof[k][i].a); (void)hipEventDestroy(e->prof[k][i].b); }
     void* bot_ptrs[] = {e->bot_state, e->bot_work, e->bot_stats, e->bot_rows};
     for (void* p : bot_ptrs) if (p) (void)hipFree(p);
     void* ptrs[] = {e->rec, e->hot, e->stale, e->mt, e->mti, e->vhead, e->vset, e->next_rec, e->next_hot, e->pending, e->first_slot, e->win_meta, e->totals, e->flow, e->gen_list, e->gen_count, e->reset_list, e->counters,
-                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow, e->rt_dmask};
+                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow, e->rt_dmask,
+                    e->rs_list, e->rs_count, e->rs_pending, e->rs_first, e->rs_claim};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int k = 0; k < 3; ++k) { if (e->grid_atlas[k]) (void)hipFree(e->grid_atlas[k]); if (e->grid_lut[k]) (void)hipFree(e->grid_lut[k]); }
     for (int k = 0; k < 2; ++k) { if (e->view_atlas[k]) (void)hipFree(e->view_atlas[k]); if (e->view_lut[k]) (void)hipFree(e->view_lut[k]); }
@@ -589,40 +603,43 @@ void bbai_destroy(bbai_env* e) {
 // k_pregen is instantiated per level family so that a launch carries only that family's mission code, and per group
 // width G (envs per wave = 64 / G; BBAI_PREGEN_GROUP, default 32: two envs per wave)
 template <int G>
-static void launch_pregen_g(const bbai_env* e, unsigned groups, bool listed /* false: dense -- every env, the whole grid works */, uint8_t* pending, const uint8_t* first_slot, int side) {
+static void launch_pregen_g(const bbai_env* e, unsigned groups, bool listed /* false: dense -- every env, the whole grid works */, uint8_t* pending, const uint8_t* first_slot, int side,
+                            const int32_t* list /* NULL: the side's own work list and counters (a window's refill) */, const uint32_t* list_count) {
     unsigned long long* fails = e->flow + FLOW_GEN_FAILURES;
     const dim3 g((groups + 64 / G - 1) / (64 / G)), b(64);
     // Demand-sized groups only where a level is cheap (single rooms, <= 60 us per group): a maze level costs a group ~300 us,
     // and GoTo at 131 072 envs stalls the step stream with 4 entries per group (0.0534 vs 0.0385 ms per step,
     // profiles/r04/pregen_min_ab.jsonl) -- mazes keep the whole grid.
     const int min_groups = e->cfg.num_rows * e->cfg.num_cols > 1 ? 0 : e->pregen_min;
-#define PREGEN_LAUNCH(KK, OO) hipLaunchKernelGGL((k_pregen<KK, G, OO>), g, b, 0, e->sides[side], e->cfg, e->n, e->next_rec, e->next_hot, e->mt, e->mti, e->gen_lists[side], \
-                                                listed ? e->gen_counts[side] : nullptr, e->depth, pending, first_slot, fails, min_groups, e->pregen_per_group, e->next_obs)
+#define PREGEN_LAUNCH(KK, OO) hipLaunchKernelGGL((k_pregen<KK, G, OO>), g, b, 0, e->sides[side], e->cfg, e->n, e->next_rec, e->next_hot, e->mt, e->mti, list ? list : e->gen_lists[side], \
+                                                listed ? (list ? list_count : e->gen_counts[side]) : nullptr, e->depth, pending, first_slot, fails, min_groups, e->pregen_per_group, e->next_obs)
     if (e->cfg.kind == K_LEVELGEN) { if (e->next_obs) PREGEN_LAUNCH(K_LEVELGEN, true); else PREGEN_LAUNCH(K_LEVELGEN, false); }
     else if (e->cfg.kind == K_BONUS) { if (e->next_obs) PREGEN_LAUNCH(K_BONUS, true); else PREGEN_LAUNCH(K_BONUS, false); }
     else { if (e->next_obs) PREGEN_LAUNCH(K_GOTO, true); else PREGEN_LAUNCH(K_GOTO, false); }
 #undef PREGEN_LAUNCH
 }
 // k_pregen_lane lives in a translation unit of its own (bbai_genlane.hip: compiled without machine-CSE, see there)
-static void launch_pregen_lane(const bbai_env* e, int64_t entries_hint, bool listed, uint8_t* pending, const uint8_t* first_slot, int side) {
+static void launch_pregen_lane(const bbai_env* e, int64_t entries_hint, bool listed, uint8_t* pending, const uint8_t* first_slot, int side,
+                               const int32_t* list, const uint32_t* list_count) {
     LaneLaunch a;
     a.cfg = e->cfg; a.n = e->n; a.next_rec = e->next_rec; a.next_hot = e->next_hot; a.mt = e->mt; a.mtt = e->mtt; a.mtpar = e->mtpar; a.mti = e->mti;
-    a.gen_list = e->gen_lists[side]; a.gen_count = listed ? e->gen_counts[side] : nullptr; a.depth = e->depth; a.pending = pending; a.first_slot = first_slot;
+    a.gen_list = list ? list : e->gen_lists[side]; a.gen_count = listed ? (list ? list_count : e->gen_counts[side]) : nullptr; a.depth = e->depth; a.pending = pending; a.first_slot = first_slot;
     a.fails = e->flow + FLOW_GEN_FAILURES; a.next_obs = e->next_obs; a.tmpl = e->lane_tmpl; a.lane_words = e->lane_words;
     a.blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((entries_hint + 63) / 64, e->lane_blocks));
     a.stream = e->sides[side];
     bbai_lane_launch(a);
 }
-static void launch_pregen(const bbai_env* e, unsigned groups, bool listed, uint8_t* pending, const uint8_t* first_slot, int64_t entries_hint, int side = 0) {
-    if (e->pregen_lane) { launch_pregen_lane(e, entries_hint, listed, pending, first_slot, side); return; }
+static void launch_pregen(const bbai_env* e, unsigned groups, bool listed, uint8_t* pending, const uint8_t* first_slot, int64_t entries_hint, int side = 0,
+                          const int32_t* list = nullptr /* bbai_reseed: its own work list and counters instead of the side's */, const uint32_t* list_count = nullptr) {
+    if (e->pregen_lane) { launch_pregen_lane(e, entries_hint, listed, pending, first_slot, side, list, list_count); return; }
     // Measured (profiles/r03/gen_rate_by_group_width.jsonl, pregen_group_width_in_bench.jsonl): levels per second of a bulk
     // fill 64 -> 32 -> 16 lanes per env: BossLevel 1 : 1.16 : 1.18, GoTo 1 : 1.13 : 1.17, PickupLoc 1 : 1.20 : 1.27,
     // GoToLocal 1 : 1.25 : 1.36; inside the step loop 32 is never behind 64 (GoToLocal 65 536 envs -3 %, PickupLoc 262 144
     // -6 %, GoTo 131 072 +-0) while 16 costs the step kernels of GoTo 131 072 9 % (fewer, fatter generator waves next to
     // them: 200 VGPRs and 20 KB of LDS each).
-    if (e->pregen_group == 64) launch_pregen_g<64>(e, groups, listed, pending, first_slot, side);
-    else if (e->pregen_group == 16) launch_pregen_g<16>(e, groups, listed, pending, first_slot, side);
-    else launch_pregen_g<32>(e, groups, listed, pending, first_slot, side);
+    if (e->pregen_group == 64) launch_pregen_g<64>(e, groups, listed, pending, first_slot, side, list, list_count);
+    else if (e->pregen_group == 16) launch_pregen_g<16>(e, groups, listed, pending, first_slot, side, list, list_count);
+    else launch_pregen_g<32>(e, groups, listed, pending, first_slot, side, list, list_count);
 }
 
 extern "C" {
@@ -2186,6 +2203,76 @@ int bbai_load_state(bbai_env* e, const int64_t* ids, const int64_t* rows, int64_
                        e->bot_state, e->bot_stack, image, dirs);
     if (e->tokens)
         hipLaunchKernelGGL(k_state_tokens<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 4096)), dim3(64), 0, s, e->cfg, e->n, ids, rows, count, snap_rows,
+                           e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, e->tokens);
+    HIP_TRY(hipGetLastError());
+    e->live = true;
+    return call.leave();
+}
+
+// ---- env.seed(s); env.reset() for listed envs of a live batch (bbai_reseedk.hpp) ------------------------------------------------------------
+// (Behind the snapshots, for the same reason: its kernels' code lies behind every earlier kernel's.)
+// Not a consume-tick: e->tick stays, no gate, no refill launch.  What orders it is events alone:
+//   1. the first look-ahead stream waits for the caller's stream (the call's ids and seeds; every step enqueued before) and for the other look-ahead
+//      streams -- so it stands behind EVERY refill launched so far; there k_reseed_seed and the generation of the listed envs' rings run (an
+//      env's MT19937 state keeps one writer at a time: its refills before, this generation, its refills after -- the latter behind ev_consumed of
+//      a window_end the caller's stream enqueues after this call);
+//   2. the caller's stream waits for the end of that generation, and only then consumes slot 0 of the new rings (k_reseed_consume).
+// After step 1 every closed window's refill has landed -- all their `pending` bytes are zero -- so the current window's buffer is the only one that can
+// hold a listed env, and k_reseed_seed clears it there.  k_reseed_consume then books the env's reset into that buffer like any finished env's.
+static int reseed_scratch(bbai_env* e) {
+    if (e->rs_claim) return BBAI_OK;          // (allocated last)
+    const size_t n = (size_t)e->n;
+    if (!e->ev_rs_call) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_call, hipEventDisableTiming));
+    if (!e->ev_rs_done) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_done, hipEventDisableTiming));
+    for (int k = 1; k < MAX_SIDES; ++k) if (!e->ev_rs_part[k]) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_part[k], hipEventDisableTiming));
+    if (!e->rs_list) HIP_TRY(hipMalloc((void**)&e->rs_list, (size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4));
+    if (!e->rs_count) HIP_TRY(hipMalloc((void**)&e->rs_count, SHARDS * GEN_COUNT_U32 * 4));
+    if (!e->rs_pending) { HIP_TRY(hipMalloc((void**)&e->rs_pending, n)); HIP_TRY(hipMemset(e->rs_pending, 0, n)); }
+    if (!e->rs_first) { HIP_TRY(hipMalloc((void**)&e->rs_first, n)); HIP_TRY(hipMemset(e->rs_first, 0, n)); }
+    uint32_t* claim = nullptr;
+    HIP_TRY(hipMalloc((void**)&claim, (n + 31) / 32 * 4));
+    if (hipMemset(claim, 0, (n + 31) / 32 * 4) != hipSuccess) { (void)hipFree(claim); snprintf(g_err, sizeof(g_err), "reseed: hipMemset failed"); return BBAI_ERR_HIP; }
+    e->rs_claim = claim;
+    return BBAI_OK;
+}
+
+int bbai_reseed(bbai_env* e, const int64_t* ids, const uint64_t* seeds, int64_t count, uint8_t* image, uint8_t* dirs, void* stream) {
+    if (!e || count < 0) ARG_FAIL("null handle or negative count");
+    if (!seeds || !image || !dirs) ARG_FAIL("null seed list or observation buffer");
+    if (!ids && count > e->n) ARG_FAIL("count > n_envs without ids");
+    if (!e->seeded) { snprintf(g_err, sizeof(g_err), "reseed before seed"); return BBAI_ERR_STATE; }
+    if (!e->live && !(ids == nullptr && count == e->n)) {
+        snprintf(g_err, sizeof(g_err), "reseed of listed envs before reset (a handle that was never reset takes every env: ids = NULL, count = n_envs)");
+        return BBAI_ERR_STATE;
+    }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    BBAI_TRY(reseed_scratch(e));
+    const TickPos tp = tick_pos(e);           // (at a window's first tick: the window about to open -- its gate, still to come, clears only its meta line)
+    uint8_t* const cur_pending = e->pending + (size_t)tp.wb * e->n;
+    uint8_t* const cur_first = e->first_slot + (size_t)tp.wb * e->n;
+    hipStream_t g = e->side;
+    HIP_TRY(hipEventRecord(e->ev_rs_call, s));
+    HIP_TRY(hipStreamWaitEvent(g, e->ev_rs_call, 0));
+    for (int k = 1; k < e->n_sides; ++k) {
+        HIP_TRY(hipEventRecord(e->ev_rs_part[k], e->sides[k]));
+        HIP_TRY(hipStreamWaitEvent(g, e->ev_rs_part[k], 0));
+    }
+    HIP_TRY(hipMemsetAsync(e->rs_count, 0, SHARDS * GEN_COUNT_U32 * 4, g));
+    hipLaunchKernelGGL(k_reseed_seed<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 65536)), dim3(64), 0, g, e->n, ids, seeds, count, e->mt, e->mti, e->mtpar,
+                       e->hot, e->next_hot, e->depth, e->inplace, cur_pending, e->rs_pending, e->rs_first, e->rs_claim, e->rs_list, e->rs_count);
+    launch_pregen(e, pregen_grid(e, count), true, e->rs_pending, e->rs_first, count, 0, e->rs_list, e->rs_count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->ev_rs_done, g));
+    HIP_TRY(hipStreamWaitEvent(s, e->ev_rs_done, 0));
+    hipLaunchKernelGGL(k_reseed_consume<0>, dim3(state_grid(count)), dim3(256), 0, s, e->cfg, e->n, ids, count, e->rs_claim, e->rec, e->hot, e->stale, e->next_rec, e->next_hot,
+                       e->vhead, e->vset, e->totals, e->depth, cur_pending, cur_first, e->win_meta + (size_t)tp.wb * META_U32, image, dirs, e->vplane, e->fcache, e->lsm,
+                       e->inplace, e->cplane, e->bot_state, e->bot_stack);
+    if (e->tokens)
+        hipLaunchKernelGGL(k_state_tokens<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 4096)), dim3(64), 0, s, e->cfg, e->n, ids, (const int64_t*)nullptr, count, count,
                            e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, e->tokens);
     HIP_TRY(hipGetLastError());
     e->live = true;

@@ -2,7 +2,7 @@
 // cell count, the windows' bookkeeping and its constants, the look-ahead ring's addressing and the live record of both state layouts, the
 // refill list's shape, the lane-group context of the generators.  A definition that one kernel family alone uses is in that family's header.
 // (bbai_engine.hip: the host side; it includes a header per kernel family -- bbai_stepk.hpp, bbai_pregen.hpp, bbai_ring.hpp, bbai_botk.hpp,
-// bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp, bbai_statek.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
+// bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp, bbai_statek.hpp, bbai_reseedk.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbai_types.hpp"
@@ -33,7 +33,14 @@ static_assert(AGENT_CELL == 3 * VIEW + 6, "the agent stands in the middle of the
 //     w - 2 has landed".  A reset storm (a million maze envs timing out on the same tick: 37 ms of generator time) then runs
 //     UNDER the following windows instead of stopping the step stream, as long as no env finishes B more times meanwhile.
 //   * NWIN = 34 window buffers (pending / first_slot / meta): up to 33 refills can be outstanding (B + 1 of them for B <= 32).
-// tests/test_ring_protocol.py models the rule (sufficient, and the ring depths stay tight).
+//   * bbai_reseed (bbai_reseedk.hpp) is no consume-tick, but it books the listed env's reset into the CURRENT window like any finished
+//     env's: after clearing the env's byte there (its whole ring is regenerated: what it consumed before needs no refill), pending 1,
+//     first slot 0.  One env can so consume B + 1 slots in one window (a reseed in front of the window's first tick, then a finish on
+//     every tick).  M records that truthfully through the same atomicMax, the sum over the open windows then exceeds B while this
+//     window is among them, and k_gate simply holds the next window until THIS window's refill has landed; the env's ring was full at
+//     the reseed, so the B + 1 <= 2B levels are there.  The call waits for every refill launched before it, so no other window holds a
+//     byte of a listed env.
+// tests/test_ring_protocol.py models the rule (sufficient, and the ring depths stay tight); tests/test_ring_protocol_reseed.py adds the reseed.
 constexpr int NWIN = 34;                // window buffers (above): at most 33 refills outstanding, whatever B
 constexpr int META_U32 = 32;            // uint32 per window buffer's meta line: [0] = M when > 1 (atomicMax)
 constexpr int SHARDS = 64;              // cache lines the reset total is spread over (k_step: shard = block & 63)

@@ -93,6 +93,8 @@ def load_library():
     if hasattr(lib, "bbai_save_state"):
         lib.bbai_save_state.argtypes = [P, P, I64, P, P, P, P, P]
         lib.bbai_load_state.argtypes = [P, P, P, I64, I64, P, P, P, P, P, P, P]
+    if hasattr(lib, "bbai_reseed"):
+        lib.bbai_reseed.argtypes = [P, P, P, I64, P, P, P]
     lib.bbai_get_programs.argtypes = [P, I64, I64, P]
     lib.bbai_tap.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P]
     lib.bbai_tap_ids.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P]
@@ -134,7 +136,7 @@ EXPORTED_SYMBOLS = (
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
     "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
     "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch", "bbai_set_view_atlas", "bbai_render_view",
-    "bbai_save_state", "bbai_load_state",
+    "bbai_save_state", "bbai_load_state", "bbai_reseed",
 )
 
 
@@ -751,6 +753,54 @@ class BatchedBabyAIEnv(object):
         _check(self.lib, self.lib.bbai_load_state(self.handle, ids_ptr, rows_ptr, k, len(snap), tensors[0].data_ptr(), tensors[1].data_ptr(),
                                                    tensors[2].data_ptr(), tensors[3].data_ptr(), self.image.data_ptr(),
                                                    self.direction.data_ptr(), self._stream()), "bbai_load_state")
+        return self._obs()
+
+    # ---- per-episode seeds (include/bbai.h bbai_reseed) ---------------------------------------------------------------
+    def _reseed_args(self, ids, seeds):
+        """reseed's checks and conversions, before any device work: (k, ids tensor or None, seeds tensor int64[k] on the device).
+        ValueError for host-side `ids` with duplicates, for lists of different lengths and for negative seeds."""
+        torch = self.torch
+        if ids is not None and not isinstance(ids, torch.Tensor):
+            host = np.asarray(ids, dtype=np.int64).reshape(-1)
+            host = host[(host >= 0) & (host < self.num_envs)]          # (padding names no env)
+            if len(np.unique(host)) != len(host):
+                raise ValueError("reseed: an env is listed twice")
+        k = self.num_envs if ids is None else int(len(ids))
+        if isinstance(seeds, torch.Tensor):
+            if seeds.dim() != 1 or seeds.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or seeds.device != self.device:
+                raise ValueError("seeds: int64 / uint64 [k] on %s" % (self.device,))
+            if int(seeds.shape[0]) != k:
+                raise ValueError("reseed: %d envs listed for %d seeds" % (k, int(seeds.shape[0])))
+            seeds_t = seeds.contiguous().view(torch.int64)          # (the same bits; the device does not check their sign)
+        else:
+            if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:
+                host = np.ascontiguousarray(seeds).reshape(-1)
+            else:
+                vals = [int(v) for v in np.asarray(seeds, dtype=object).reshape(-1)]
+                if any(v < 0 for v in vals):
+                    raise ValueError("reseed: negative seed")
+                if any(v >= 1 << 64 for v in vals):
+                    raise ValueError("reseed: seeds are uint64")
+                host = np.array(vals, dtype=np.uint64)
+            if len(host) != k:
+                raise ValueError("reseed: %d envs listed for %d seeds" % (k, len(host)))
+            seeds_t = torch.as_tensor(host.view(np.int64), device=self.device) if k else torch.zeros((0,), dtype=torch.int64, device=self.device)
+        return k, seeds_t
+
+    def reseed(self, ids, seeds):
+        """`env[ids[k]].seed(seeds[k]); env[ids[k]].reset()` for the listed envs of a live batch (ids None = every env; an int sequence,
+        an ndarray or an int64 device tensor; seeds: ints, a uint64 ndarray or an int64 / uint64 device tensor), on the current stream
+        without a host synchronisation: each listed env's level stream restarts from its seed, the env starts level 0 of it -- a frozen
+        env (auto_reset=False) is live again -- and every other env goes on as if nothing had happened.  Returns the observation dict as
+        reset() does, the listed rows holding the new episodes' first observations.  An id outside [0, num_envs) is skipped (pad with
+        -1); ValueError: see _reseed_args; the same env twice in a DEVICE id list is undefined as to which seed it gets."""
+        k, seeds_t = self._reseed_args(ids, seeds)
+        if k == 0:
+            return self._obs()
+        _, ids_ptr = self._id_list(ids)
+        self._reseed_keep = (seeds_t, self._grid_ids if ids is not None else None)       # alive until the launch is consumed
+        _check(self.lib, self.lib.bbai_reseed(self.handle, ids_ptr, seeds_t.data_ptr(), k, self.image.data_ptr(), self.direction.data_ptr(),
+                                               self._stream()), "bbai_reseed")
         return self._obs()
 
     def save_checkpoint(self):

@@ -44,12 +44,77 @@ class AgentPolicy(object):
                                      tuple(bool(d) for d in done.cpu().numpy()))
 
 
+def _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every):
+    """evaluate_policy(pool=k): min(k, episodes) envs play all the seeds.  At every poll the envs that have finished are read out and
+    reseeded (BatchedBabyAIEnv.reseed: env.seed(s); env.reset() of the listed envs) with the next unplayed seeds, until none are left;
+    an env without a seed left stays frozen.  An env waits frozen between its episode's end and the next poll, so `t`, the global frame
+    count, is not a frame count of any episode: an episode's frames are counted from the frame it started at."""
+    import torch
+    n = min(int(pool), episodes)
+    env = BatchedBabyAIEnv(env_name, n, device=device, pixel=pixel, auto_reset=False)
+    try:
+        env.seed(np.arange(n, dtype=np.uint64) + np.uint64(seed))
+        instr = env.enable_instr_tokens()
+        obs = env.reset()
+        dev = env.device
+        episode = torch.arange(n, dtype=torch.int64, device=dev)          # the episode an env plays; -1 = none left for it
+        started = torch.zeros(n, dtype=torch.int64, device=dev)           # global frame count at its start
+        frames = torch.zeros(n, dtype=torch.int64, device=dev)            # 0 = still running
+        returns = torch.zeros(n, dtype=torch.float64, device=dev)
+        start = torch.ones(n, dtype=torch.uint8, device=dev)
+        out_frames, out_returns = np.zeros(episodes, dtype=np.int64), np.zeros(episodes, dtype=np.float64)
+        next_ep, playing, t = n, n, 0
+        while playing:
+            t += 1
+            action = policy({"image": obs["image"], "direction": obs["direction"], "instr": instr, "episode_start": start}, t)
+            obs, _, done, _ = env.step(action)
+            start = torch.zeros_like(start)
+            just = (done != 0) & (frames == 0) & (episode >= 0)
+            returns += env.reward64 * just
+            frames = torch.where(just, t - started, frames)
+            if t % max(1, int(poll_every)) != 0:
+                continue
+            fin = torch.nonzero(frames != 0).reshape(-1)
+            if fin.numel() == 0:
+                continue
+            eps = episode[fin].cpu().numpy()
+            out_frames[eps] = frames[fin].cpu().numpy()
+            out_returns[eps] = returns[fin].cpu().numpy()
+            k = min(int(fin.numel()), episodes - next_ep)
+            frames[fin] = 0
+            returns[fin] = 0
+            episode[fin[k:]] = -1
+            playing -= int(fin.numel()) - k
+            if k:
+                again = fin[:k].contiguous()
+                new_eps = np.arange(next_ep, next_ep + k, dtype=np.int64)
+                obs = env.reseed(again, new_eps.astype(np.uint64) + np.uint64(seed))
+                episode[again] = torch.as_tensor(new_eps, device=dev)
+                started[again] = t
+                start[again] = 1
+                next_ep += k
+        return {"num_frames_per_episode": out_frames.tolist(), "return_per_episode": out_returns.tolist(),
+                "seed_per_episode": list(range(seed, seed + episodes))}
+    finally:
+        env.close()
+
+
 def evaluate_policy(policy, env_name, seed, episodes, pixel=False, device="cuda:0", chunk=262144, poll_every=16,
-                    agent=None):
+                    agent=None, pool=None):
     """Run `episodes` episodes (seeds seed .. seed+episodes-1) to completion; returns the reference's `logs` dict
     (num_frames_per_episode, return_per_episode, seed_per_episode).  `agent`: wrap a reference-style agent instead of a
-    tensor policy.  `poll_every`: frames between two host checks of "is everybody done" (frozen envs cost nothing)."""
+    tensor policy.  `poll_every`: frames between two host checks of "is everybody done" (frozen envs cost nothing).
+    `pool=k`: instead of one env per episode, min(k, episodes) envs play all the seeds, a finished env being reseeded with the next
+    unplayed seed at the next poll (_evaluate_pool); `obs` then has one more key, `episode_start` (uint8 [N]: the env's row is the
+    first observation of an episode), `t` stays the global frame count, and the logs -- in seed order -- equal the default path's for
+    any policy that is a pure function of the observation.  Not for a stateful `agent` (ValueError)."""
     import torch
+    if pool is not None:
+        if agent is not None:
+            raise ValueError("evaluate_policy: pool= serves tensor policies only, not agent=")
+        if int(pool) < 1:
+            raise ValueError("evaluate_policy: pool must be at least 1")
+        return _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every)
     logs = {"num_frames_per_episode": [], "return_per_episode": [], "seed_per_episode": []}
     for first in range(0, episodes, chunk):
         n = min(chunk, episodes - first)

@@ -161,6 +161,11 @@ class _VecBase(object):
         """Snapshot rows into the listed envs (BatchedBabyAIEnv.load_state); returns the obs list of the whole batch, as reset() does."""
         return self._obs_list(self.engine.load_state(snap, ids, rows))
 
+    def reseed(self, ids, seeds):
+        """env.seed(s); env.reset() for the listed envs (BatchedBabyAIEnv.reseed: evaluate.py:64-71, make_agent_demos.py:93 seed per
+        episode); returns the obs list of the whole batch, as reset() does."""
+        return self._obs_list(self.engine.reseed(ids, seeds))
+
     def render(self):
         raise NotImplementedError
 
@@ -194,6 +199,14 @@ class BatchedManyEnvs(_VecBase):
         obs, reward, done, info = super().step(actions)
         self.done = list(done)
         return iter((obs, reward, done, info))
+
+    def reseed(self, ids, seeds):
+        obs = super().reseed(ids, seeds)
+        listed = range(self.num_envs) if ids is None else np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids, dtype=np.int64).reshape(-1)
+        for i in listed:
+            if 0 <= int(i) < self.num_envs:
+                self.done[int(i)] = False          # (a reseeded env is live again)
+        return obs
 
 
 class Actions(object):

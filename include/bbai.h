@@ -223,6 +223,26 @@ int bbai_load_state(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..coun
                     int64_t snap_rows, const uint8_t* rec_dev, const uint8_t* hot_dev, const uint64_t* stale_dev,
                     const uint8_t* lsm_dev /* NULL = zeros */, uint8_t* image_dev, uint8_t* dir_dev, void* stream);
 
+/* env.seed(s); env.reset() for LISTED envs of a live batch, on `stream`, with no host synchronisation, allocation or host copy (the scratch
+ * memory of a handle's first call aside).  In the reference a seed belongs to an EPISODE: ManyEnvs.seed(seeds); reset() before every
+ * evaluation round (babyai/evaluate.py:64-71,105-106), env.seed(seed + len(demos)) before every demonstration
+ * (scripts/make_agent_demos.py:93), env.seed(args.seed + episode_num) (scripts/enjoy.py:123), and per episode in
+ * scripts/train_intelligent_expert.py:115.  bbai_seed serves a whole batch from the host; this call serves entry k as
+ * env[ids_dev[k]].seed(seeds_dev[k]); env[ids_dev[k]].reset():
+ * the env's MT19937 stream restarts from the seed (the sha512 + init_by_array of bbai_seed), LevelGen.locked_room restarts at None, the env's
+ * whole look-ahead ring is regenerated from the new stream, the env is put into level 0 of it -- a frozen env is live again -- and that
+ * level's first observation is written to row ids_dev[k] of image_dev uint8[n][147] and dir_dev uint8[n].  Per listed env: the stale set
+ * and the lastStepMatch byte are cleared, the next bbai_bot_act starts a fresh Bot where the expert's state is allocated, a registered
+ * token buffer gets the new mission's row, and bbai_reset_count grows by one.  Every other env goes on exactly as if nothing had happened.
+ * It is no consume-tick; the registered render target is NOT touched (render afterwards, as after bbai_reset).  The call's latency is that of
+ * ONE env's ring generated in sequence (ring depth x one level), however few envs are listed.
+ * An id outside [0, n_envs) skips the entry (pad a fixed-length list with -1); the same env listed twice is a caller error (it gets one of
+ * its seeds).  BBAI_ERR_ARG, before any device work, for a null handle, null seeds, null outputs, a negative count or count > n_envs without
+ * ids; BBAI_ERR_STATE for a handle that was never seeded, and for one that was seeded but not yet reset unless every env is listed (ids_dev =
+ * NULL, count = n_envs).  count == 0 is a no-op. */
+int bbai_reseed(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..count-1 */, const uint64_t* seeds_dev /* [count] */,
+                int64_t count, uint8_t* image_dev, uint8_t* dir_dev, void* stream);
+
 /* Checkpoint / resume of a whole batch (the reference checkpoints only its model, babyai/utils/model.py:29-32; an
  * auto-resetting env batch additionally needs its RNG streams): the blob holds the live state, every env's MT19937
  * stream, the look-ahead ring with its window bookkeeping, the counters and -- when bbai_bot_act has been used -- the
