@@ -3,6 +3,9 @@
 //   k_demo_spans  one chunk of bbai_bot_rollout history -> every stream's first solved episode (demos.py scan_chunk)
 //   k_demo_pack   the spans of up to C history chunks   -> the store's flat arrays
 //   k_demo_batch  a sorted list of demos of a store     -> the flat batch of imitation.py:226-251 (or a sub-store)
+//   k_demo_jobs   one chunk of history of a POOL of envs that play listed seeds (DemoStore.collect_seeds) -> the episodes that ended,
+//                 kept or dropped, and the next seed of every env that finished
+//   k_demo_pack_list  k_demo_pack for a list of (stream, first step, length) records in a ring of history chunks
 // The two copies write ALIGNED 16-byte chunks of one contiguous destination; a chunk's bytes come from at most two source
 // runs (147-byte history rows in k_demo_pack, whole demos in k_demo_batch), each fetched as two aligned 16-byte loads
 // and byte-aligned in registers.  Every unaligned 16-byte window that is fetched lies INSIDE a source run (a chunk that
@@ -136,6 +139,79 @@ __global__ __launch_bounds__(64) void k_demo_spans(int64_t n, int chunk, const u
 }
 
 // ------------------------------------------------------------------------------------------
+// k_demo_jobs : lane = env of a POOL that plays a list of seeds, one episode per seed (DemoStore.collect_seeds: the listed-seed contract of
+// scripts/train_intelligent_expert.py:106-147 generate_demos -- env.seed(s); env.reset(), the expert plays THAT episode, kept iff it ends with
+// reward > 0 and without a bot exception).  job[i] = the position in the seed list env i is playing (-1: idle), start[i] = the global step its
+// episode began at; episodes begin on a chunk's first row only (reseeds happen between chunks).  done / gave_up / reward are this chunk's
+// [chunk][n], read as k_demo_spans reads them.  An env whose episode ends in this chunk -- the FIRST done row -- appends the record
+// (env, first step, length, job) if the episode is kept, and claims the next unplayed job: ids_out[i] = i, seeds_out[i] = its seed for
+// bbai_reseed, start[i] = the next chunk's first row; with the list exhausted it goes idle.  Every other env gets ids_out[i] = -1 (bbai_reseed
+// skips it).  counters: [0] job cursor (in / out; may pass n_jobs by the claims that found nothing), [1] episodes finished (running total),
+// [2] records and [3] frames of this call (zeroed by the entry).  Per wave: one ballot and one returning add for the claims, one for the
+// records, one add each for the two totals -- none per lane, none in the row loop.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_demo_jobs(int64_t n, int chunk, const uint8_t* __restrict__ done, const uint8_t* __restrict__ gave_up,
+                                                  const float* __restrict__ reward, int g0, int32_t* __restrict__ job, int32_t* __restrict__ start,
+                                                  const uint64_t* __restrict__ job_seeds, int64_t n_jobs, int64_t* __restrict__ ids_out,
+                                                  uint64_t* __restrict__ seeds_out, int32_t* __restrict__ rec, unsigned long long* __restrict__ counters) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int lane = (int)threadIdx.x;
+    bool fin = false, keep = false;
+    int32_t mine = -1, first = 0, len = 0;
+    if (i < n) {
+        mine = job[i];
+        if (mine >= 0) {
+            for (int t = 0; t < chunk; ++t) {
+                const int64_t k = (int64_t)t * n + i;
+                if (!done[k]) continue;
+                fin = true;
+                keep = gave_up[k] == 0 && reward[k] > 0.0f;
+                first = start[i];
+                len = g0 + t - first + 1;
+                break;
+            }
+        }
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long fin_bal = __ballot(fin), keep_bal = __ballot(keep);
+    int sum = keep ? len : 0;                   // frames of the wave's kept episodes
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    unsigned long long job_base = 0, rec_base = 0;
+    if (lane == 0) {
+        if (fin_bal) {
+            const unsigned long long c = (unsigned long long)__popcll(fin_bal);
+            job_base = atomicAdd(counters, c);
+            atomicAdd(counters + 1, c);
+        }
+        if (keep_bal) {
+            rec_base = atomicAdd(counters + 2, (unsigned long long)__popcll(keep_bal));
+            atomicAdd(counters + 3, (unsigned long long)sum);
+        }
+    }
+    job_base = __shfl(job_base, 0);
+    rec_base = __shfl(rec_base, 0);
+    if (i >= n) return;
+    if (keep) {
+        int32_t* r = rec + 4 * (int64_t)(rec_base + (unsigned long long)__popcll(keep_bal & below));
+        r[0] = (int32_t)i; r[1] = first; r[2] = len; r[3] = mine;
+    }
+    int64_t id = -1;
+    if (fin) {
+        const unsigned long long next = job_base + (unsigned long long)__popcll(fin_bal & below);
+        if (next < (unsigned long long)n_jobs) {
+            id = i;
+            seeds_out[i] = job_seeds[next];
+            job[i] = (int32_t)next;
+            start[i] = g0 + chunk;
+        } else {
+            job[i] = -1;
+        }
+    }
+    ids_out[i] = id;
+}
+
+// ------------------------------------------------------------------------------------------
 // k_demo_pack : blocks [0, img_blocks) copy the frames (8 KiB of the store's image array each), the blocks behind them
 // write direction / action (lane = 4 frames, one aligned dword of each) and the token rows (lane = 8 of a row's 72 bytes).
 // Frame f of the store = history row g = span[k][0] + (f - offset[k]) of stream k, i.e. row g % T of chunk g / T.
@@ -144,15 +220,36 @@ struct DemoPackArgs {
     int64_t n, frames; int T; int64_t img_blocks, meta_blocks;
     const DemoChunkPtrs* __restrict__ chunks; const int32_t* __restrict__ span; const int64_t* __restrict__ offset;
     uint8_t* image; uint8_t* dir; uint8_t* action; uint8_t* tokens;
+    // demo k lies in stream k, its first history row is span[k][0], chunk q of the history is entry q of the table
+    __device__ __forceinline__ int64_t streams() const { return n; }
+    __device__ __forceinline__ int64_t stream(int64_t k) const { return k; }
+    __device__ __forceinline__ int32_t first(int64_t k) const { return span[2 * k]; }
+    __device__ __forceinline__ int slot(int q) const { return q; }
 };
 
-__device__ __forceinline__ int64_t demo_pack_row(const DemoPackArgs& a, int64_t k, int64_t g, int& c) {
-    c = (int)(g / a.T);
-    return (g - (int64_t)c * a.T) * a.n + k;
+// The list form (bbai_demo_pack_list): demo k is the record rec[k] = (stream, first step, length, job) that k_demo_jobs appended, and
+// the history is a RING of R chunks: global row g is row g % T of entry (g / T) % R of the table.
+struct DemoPackListArgs {
+    int64_t n, frames; int T; int64_t img_blocks, meta_blocks;
+    const DemoChunkPtrs* __restrict__ chunks; const int32_t* __restrict__ rec; const int64_t* __restrict__ offset;
+    uint8_t* image; uint8_t* dir; uint8_t* action; uint8_t* tokens;
+    int64_t n_streams; int R;
+    __device__ __forceinline__ int64_t streams() const { return n_streams; }
+    __device__ __forceinline__ int64_t stream(int64_t k) const { return rec[4 * k]; }
+    __device__ __forceinline__ int32_t first(int64_t k) const { return rec[4 * k + 1]; }
+    __device__ __forceinline__ int slot(int q) const { return q % R; }
+};
+
+template <class Args>
+__device__ __forceinline__ int64_t demo_pack_row(const Args& a, int64_t k, int64_t g, int& c) {
+    const int q = (int)(g / a.T);
+    c = a.slot(q);
+    return (g - (int64_t)q * a.T) * a.streams() + a.stream(k);
 }
 
 // source address of frame `rel` (relative to the block's first frame) in the history
-__device__ __forceinline__ const uint8_t* demo_pack_src(const DemoPackArgs& a, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo, int rel) {
+template <class Args>
+__device__ __forceinline__ const uint8_t* demo_pack_src(const Args& a, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo, int rel) {
     const int j = demo_find_lds(s_rel, rel);
     int c;
     const int64_t row = demo_pack_row(a, k_lo + j, (int64_t)s_g0[j] + (rel - s_rel[j]), c);
@@ -160,7 +257,8 @@ __device__ __forceinline__ const uint8_t* demo_pack_src(const DemoPackArgs& a, c
 }
 
 // the piece of the chunk at byte x relative to the block's first frame f_lo
-__device__ __forceinline__ void demo_pack_piece(const DemoPackArgs& a, DemoPiece& p, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo,
+template <class Args>
+__device__ __forceinline__ void demo_pack_piece(const Args& a, DemoPiece& p, const int32_t* s_rel, const int32_t* s_g0, int64_t k_lo,
                                                 int64_t f_lo, uint32_t x) {
     const uint32_t fr = __umulhi(x, DEMO_DIV147), r = x - fr * DEMO_ROW;
     const uint8_t* s0 = demo_pack_src(a, s_rel, s_g0, k_lo, (int)fr);
@@ -170,7 +268,8 @@ __device__ __forceinline__ void demo_pack_piece(const DemoPackArgs& a, DemoPiece
     p.load(tail, s1, 16 - (DEMO_ROW - r));
 }
 
-__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
+template <class Args>
+__device__ __forceinline__ void demo_pack_body(const Args& a) {
     __shared__ int32_t s_rel[DEMO_SLICE + 1];   // first frame of the block's demos, relative to the block's first frame
     __shared__ int32_t s_g0[DEMO_SLICE];        // span[k][0] of those demos
     __shared__ int64_t s_klo;                   // the first of them
@@ -181,7 +280,7 @@ __global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
         const int64_t k = p / 9;
         if (k >= a.n) return;
         int c;
-        const int64_t row = demo_pack_row(a, k, a.span[2 * k], c);
+        const int64_t row = demo_pack_row(a, k, a.first(k), c);
         const int piece = (int)(p - k * 9);
         ((uint2*)a.tokens)[p] = ((const uint2*)(a.chunks[c].tokens + row * 72))[piece];
         return;
@@ -196,7 +295,7 @@ __global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
             const int64_t f = f0 + i;
             while (a.offset[k + 1] <= f) ++k;
             int c;
-            const int64_t row = demo_pack_row(a, k, a.span[2 * k] + (f - a.offset[k]), c);
+            const int64_t row = demo_pack_row(a, k, a.first(k) + (f - a.offset[k]), c);
             d |= (uint32_t)a.chunks[c].dir[row] << (8 * i);
             act |= (uint32_t)a.chunks[c].action[row] << (8 * i);
         }
@@ -213,7 +312,7 @@ __global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
         const int64_t k = k0 + tid;
         const int64_t rel = k <= a.n ? a.offset[k] - f_lo : (int64_t)0x7fffffff;
         s_rel[tid] = (int32_t)(rel < 0x7fffffff ? rel : 0x7fffffff);
-        s_g0[tid] = k < a.n ? a.span[2 * k] : 0;
+        s_g0[tid] = k < a.n ? a.first(k) : 0;
         if (tid == 0) { s_rel[DEMO_SLICE] = 0x7fffffff; s_klo = k0; }
     }
     __syncthreads();
@@ -228,6 +327,9 @@ __global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) {
     if (v0) demo_store(a.image, q0, p0.get(), total);
     if (v1) demo_store(a.image, q1, p1.get(), total);
 }
+
+__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack(DemoPackArgs a) { demo_pack_body(a); }
+__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_pack_list(DemoPackListArgs a) { demo_pack_body(a); }
 
 // ------------------------------------------------------------------------------------------
 // k_demo_batch : the batch gather.  order[b] = the store's demo that comes b-th, dst_start[b] its first frame in the result

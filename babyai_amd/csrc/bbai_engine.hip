@@ -22,7 +22,7 @@
 //   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32.  (render_view_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
-//   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch: demonstrations that stay on the device.
+//   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch / k_demo_jobs / k_demo_pack_list: demonstrations that stay on the device.
 //   bbai_statek.hpp   k_state_save / k_state_load / k_state_tokens: device snapshots of listed envs (bbai_save_state, bbai_load_state).
 //   bbai_reseedk.hpp  k_reseed_seed / k_reseed_consume: env.seed(s); env.reset() for listed envs of a live batch (bbai_reseed).
 //
@@ -1983,7 +1983,7 @@ int bbai_gae(int64_t num_envs, int num_frames, const float* rewards, const float
     return BBAI_OK;
 }
 
-// The three entries of the demo store (bbai_demo.hpp): handle-free like bbai_gae, launched on the current device.
+// The entries of the demo store (bbai_demo.hpp): handle-free like bbai_gae, launched on the current device.
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 int bbai_demo_spans(int64_t n, int chunk, const uint8_t* done, const uint8_t* gave_up, const float* reward, int64_t g0, int filter_steps,
@@ -2012,6 +2012,38 @@ int bbai_demo_pack(int64_t n, int64_t frames, int chunk_steps, const bbai_demo_c
     a.image = image_out; a.dir = dir_out; a.action = action_out; a.tokens = tokens_out;
     if (a.img_blocks + a.meta_blocks + tok_blocks > 0x7fffffff) ARG_FAIL("store too large for one launch");
     hipLaunchKernelGGL(k_demo_pack, dim3((unsigned)(a.img_blocks + a.meta_blocks + tok_blocks)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+int bbai_demo_jobs(int64_t n, int chunk, const uint8_t* done, const uint8_t* gave_up, const float* reward, int64_t g0, int32_t* job, int32_t* start,
+                   const uint64_t* job_seeds, int64_t n_jobs, int64_t* ids_out, uint64_t* seeds_out, int32_t* records_out, uint64_t* counters,
+                   void* stream) {
+    if (n <= 0 || chunk <= 0 || !done || !gave_up || !reward || !job || !start || !job_seeds || !ids_out || !seeds_out || !records_out || !counters)
+        ARG_FAIL("null pointer or empty chunk");
+    if (g0 < 0 || g0 + chunk > 0x7fffffff || n_jobs < 0 || n_jobs > 0x7fffffff) ARG_FAIL("step index or job count out of range");
+    HIP_TRY(hipMemsetAsync(counters + 2, 0, 2 * sizeof(uint64_t), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_demo_jobs, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, chunk, done, gave_up, reward, (int)g0, job, start,
+                       job_seeds, n_jobs, ids_out, seeds_out, records_out, (unsigned long long*)counters);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+int bbai_demo_pack_list(int64_t count, int64_t frames, int64_t n_streams, int chunk_steps, int ring_slots, const bbai_demo_chunk* chunks,
+                        const int32_t* records, const int64_t* offset, uint8_t* image_out, uint8_t* dir_out, uint8_t* action_out, uint8_t* tokens_out,
+                        void* stream) {
+    if (count <= 0 || frames < count || n_streams <= 0 || chunk_steps <= 0 || ring_slots <= 0 || !chunks || !records || !offset || !image_out || !dir_out ||
+        !action_out || !tokens_out) ARG_FAIL("null pointer or empty list");
+    if (!aligned16(image_out) || !aligned16(dir_out) || !aligned16(action_out) || !aligned16(tokens_out)) ARG_FAIL("outputs must be 16-byte aligned");
+    DemoPackListArgs a;
+    a.n = count; a.frames = frames; a.T = chunk_steps; a.n_streams = n_streams; a.R = ring_slots;
+    a.img_blocks = (frames * (int64_t)DEMO_ROW + DEMO_BLOCK_BYTES - 1) / DEMO_BLOCK_BYTES;
+    a.meta_blocks = ((frames + 3) / 4 + DEMO_BLOCK - 1) / DEMO_BLOCK;
+    const int64_t tok_blocks = (count * 9 + DEMO_BLOCK - 1) / DEMO_BLOCK;
+    a.chunks = (const DemoChunkPtrs*)chunks; a.rec = records; a.offset = offset;
+    a.image = image_out; a.dir = dir_out; a.action = action_out; a.tokens = tokens_out;
+    if (a.img_blocks + a.meta_blocks + tok_blocks > 0x7fffffff) ARG_FAIL("list too large for one launch");
+    hipLaunchKernelGGL(k_demo_pack_list, dim3((unsigned)(a.img_blocks + a.meta_blocks + tok_blocks)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }

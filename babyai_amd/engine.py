@@ -106,6 +106,9 @@ def load_library():
         lib.bbai_demo_spans.argtypes = [I64, I32, P, P, P, I64, I32, P, P, P, P, P]
         lib.bbai_demo_pack.argtypes = [I64, I64, I32, P, P, P, P, P, P, P, P]
         lib.bbai_demo_batch.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]
+    if hasattr(lib, "bbai_demo_jobs"):
+        lib.bbai_demo_jobs.argtypes = [I64, I32, P, P, P, I64, P, P, P, I64, P, P, P, P, P]
+        lib.bbai_demo_pack_list.argtypes = [I64, I64, I64, I32, I32, P, P, P, P, P, P, P, P]
     lib.bbai_set_call_events.argtypes = [P, I32]
     lib.bbai_profile.argtypes = [P, I32]
     lib.bbai_profile_read.argtypes = [P, P, P]
@@ -136,7 +139,7 @@ EXPORTED_SYMBOLS = (
     "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
     "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
     "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch", "bbai_set_view_atlas", "bbai_render_view",
-    "bbai_save_state", "bbai_load_state", "bbai_reseed",
+    "bbai_save_state", "bbai_load_state", "bbai_reseed", "bbai_demo_jobs", "bbai_demo_pack_list",
 )
 
 
@@ -852,26 +855,35 @@ class BatchedBabyAIEnv(object):
         _check(self.lib, self.lib.bbai_bot_act(self.handle, prev_ptr, out.data_ptr(), self._stream()), "bbai_bot_act")
         return out
 
-    def bot_rollout(self, steps, tokens=False):
+    def bot_rollout(self, steps, tokens=False, out=None):
         """`steps` expert decisions + auto-reset steps for every env with no host round trip in between (include/bbai.h
         bbai_bot_rollout: the inner loop of scripts/make_agent_demos.py:71-137).  Returns device tensors [steps, N, ...]:
         image / direction (and tokens, uint8[steps, N, 72] mission token ids, if asked) = what the expert decided on at
         each step, action = its decision (RESET_ENV where it gave up: gave_up = 1), reward, done = the step's results.
-        Afterwards self.image / self.direction hold the current observation as after step()."""
+        Afterwards self.image / self.direction hold the current observation as after step().  `out`: a dict of such tensors (what an earlier
+        call returned, or preallocated ones of the same shapes and types) to write into instead of fresh ones -- a history slot that is
+        reused allocates nothing."""
         torch = self.torch
         T, n = int(steps), self.num_envs
         if not self.auto_reset:
             raise EngineError("bot_rollout steps with ParallelEnv semantics: construct the env with auto_reset=True")
-        with torch.cuda.device(self.dev_index):
-            u8 = dict(dtype=torch.uint8, device=self.device)
-            out = {"image": torch.empty((T, n, 7, 7, 3), **u8), "direction": torch.empty((T, n), **u8),
-                   "action": torch.empty((T, n), **u8), "reward": torch.empty((T, n), dtype=torch.float32, device=self.device),
-                   "done": torch.empty((T, n), **u8), "gave_up": torch.empty((T, n), **u8)}
-            tok_ptr = None
+        shapes = {"image": (T, n, 7, 7, 3), "direction": (T, n), "action": (T, n), "reward": (T, n), "done": (T, n), "gave_up": (T, n)}
+        if tokens:
+            shapes["tokens"] = (T, n, TOK_MAX)
+        if out is not None:
+            for k, shape in shapes.items():
+                t = out.get(k)
+                if t is None or tuple(t.shape) != shape or t.dtype != (torch.float32 if k == "reward" else torch.uint8) or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError("bot_rollout: out[%r] must be a contiguous %s%s on %s" % (k, "float32" if k == "reward" else "uint8", list(shape), self.device))
             if tokens:
                 self.enable_instr_tokens()
-                out["tokens"] = torch.empty((T, n, TOK_MAX), **u8)
-                tok_ptr = out["tokens"].data_ptr()
+        else:
+            with torch.cuda.device(self.dev_index):
+                out = {k: torch.empty(shape, dtype=torch.float32 if k == "reward" else torch.uint8, device=self.device) for k, shape in shapes.items()}
+                if tokens:
+                    self.enable_instr_tokens()
+        tok_ptr = out["tokens"].data_ptr() if tokens else None
         _check(self.lib, self.lib.bbai_bot_rollout(self.handle, T, self.image.data_ptr(), self.direction.data_ptr(),
                                                     out["image"].data_ptr(), out["direction"].data_ptr(), tok_ptr,
                                                     out["action"].data_ptr(), out["reward"].data_ptr(), out["done"].data_ptr(),

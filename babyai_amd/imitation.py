@@ -15,6 +15,9 @@ the flat batch of imitation.py:226-251 and `run_batch` / `run_epoch` are `run_ep
 over it (pinned to the reference's own functions by tests/test_imitation_host.py).  ROCm tensors go through the kernels of
 babyai_amd/csrc/bbai_demo.hpp (include/bbai.h bbai_demo_spans / bbai_demo_pack / bbai_demo_batch); host tensors take the same
 steps in torch ops, as `rollout.gae_env_major` does, so that the pin tests run without a GPU.
+
+`DemoStore.collect_seeds` (one demonstration per LISTED seed, a pool of envs playing the list), `DemoStore.extend` and
+`grow_training_set` are scripts/train_intelligent_expert.py:106-176 on the same footing (bbai_demo_jobs / bbai_demo_pack_list).
 """
 import ctypes
 
@@ -134,26 +137,102 @@ class DemoBatch(object):
 
 
 class DemoStore(object):
-    def __init__(self, image, direction, action, tokens, offset_host):
+    def __init__(self, image, direction, action, tokens, offset_host=None, offset=None):
+        """`offset_host` (int64[D + 1] on the host) or `offset` (the same on the store's device: the host mirror is then read when it is
+        first asked for) or both."""
         import torch
         self.image, self.direction, self.action, self.tokens = image, direction, action, tokens
-        self.offset_host = np.ascontiguousarray(offset_host, dtype=np.int64)
-        self.offset = torch.as_tensor(self.offset_host, device=image.device)
         self.device = image.device
-        assert image.shape[0] == direction.shape[0] == action.shape[0] == int(self.offset_host[-1])
-        assert tokens.shape[0] == len(self.offset_host) - 1
+        self._count, self._frames = int(tokens.shape[0]), int(image.shape[0])
+        assert image.shape[0] == direction.shape[0] == action.shape[0]
+        if offset_host is not None:
+            self._offset_host = np.ascontiguousarray(offset_host, dtype=np.int64)
+            assert self._frames == int(self._offset_host[-1]) and self._count == len(self._offset_host) - 1
+            offset = torch.as_tensor(self._offset_host, device=image.device) if offset is None else offset
+        else:
+            self._offset_host = None
+        assert offset.shape[0] == self._count + 1 and offset.dtype == torch.int64 and offset.device == image.device
+        self.offset = offset
         self._ntok = None
+        self._buf = None                        # extend(): the buffers with room to grow; the attributes above are views of their filled prefix
 
     def __len__(self):
-        return len(self.offset_host) - 1
+        return self._count
 
     @property
     def num_frames(self):
-        return int(self.offset_host[-1])
+        return self._frames
+
+    @property
+    def offset_host(self):
+        if self._offset_host is None:
+            self._offset_host = np.ascontiguousarray(self.offset.cpu().numpy(), dtype=np.int64)
+        return self._offset_host
 
     @property
     def lengths(self):
         return np.diff(self.offset_host)
+
+    @property
+    def capacity(self):
+        """(frames, demos) the store can hold before `extend` allocates again"""
+        return (int(self._buf["direction"].shape[0]), int(self._buf["tokens"].shape[0])) if self._buf else (self._frames, self._count)
+
+    def _reserve(self, frames, demos):
+        """Buffers for at least `frames` / `demos`; a buffer that is too small is replaced by one of TWICE what is needed, so that a run of
+        extends copies every frame a bounded number of times.  The image buffer keeps 16 spare bytes behind its last frame: k_demo_batch
+        reads the aligned 16-byte words around its runs."""
+        import torch
+        cap_f, cap_d = self.capacity if self._buf else (-1, -1)
+        if frames <= cap_f and demos <= cap_d:
+            return
+        new_f = cap_f if frames <= cap_f else 2 * frames
+        new_d = cap_d if demos <= cap_d else 2 * demos
+        new_f, new_d = max(new_f, 1), max(new_d, 1)
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        buf = {"image": torch.empty(new_f * 147 + 16, **u8), "direction": torch.empty(new_f, **u8), "action": torch.empty(new_f, **u8),
+               "tokens": torch.empty((new_d, TOK_MAX), **u8), "offset": torch.zeros(new_d + 1, dtype=torch.int64, device=self.device)}
+        F, D = self._frames, self._count
+        buf["image"][:F * 147].copy_(self.image.reshape(-1))
+        buf["direction"][:F].copy_(self.direction)
+        buf["action"][:F].copy_(self.action)
+        buf["tokens"][:D].copy_(self.tokens)
+        buf["offset"][:D + 1].copy_(self.offset)
+        self._buf = buf
+        self._view()
+
+    def _view(self):
+        b, F, D = self._buf, self._frames, self._count
+        self.image, self.direction, self.action = b["image"][:F * 147].view(F, 7, 7, 3), b["direction"][:F], b["action"][:F]
+        self.tokens, self.offset = b["tokens"][:D], b["offset"][:D + 1]
+
+    def extend(self, other):
+        """Append the demonstrations of `other` (a store on the same device), in place: `train_demos.extend(new_demos)` of
+        scripts/train_intelligent_expert.py:171.  Nothing crosses to the host; the host mirror of `offset` follows if both stores have one."""
+        if len(other) == 0:
+            return self
+        assert other.device == self.device, "extend: both stores on one device"
+        F, D, f, d = self._frames, self._count, other.num_frames, len(other)
+        self._reserve(F + f, D + d)
+        b = self._buf
+        b["image"][F * 147:(F + f) * 147].copy_(other.image.reshape(-1))
+        b["direction"][F:F + f].copy_(other.direction)
+        b["action"][F:F + f].copy_(other.action)
+        b["tokens"][D:D + d].copy_(other.tokens)
+        b["offset"][D + 1:D + d + 1].copy_(other.offset[1:] + F)
+        if self._offset_host is not None and other._offset_host is not None:
+            self._offset_host = np.concatenate([self._offset_host, other._offset_host[1:] + F])
+        else:
+            self._offset_host = None
+        self._frames, self._count, self._ntok = F + f, D + d, None
+        self._view()
+        return self
+
+    @classmethod
+    def empty(cls, device="cpu"):
+        import torch
+        z = lambda *shape: torch.zeros(shape, dtype=torch.uint8, device=device)
+        return cls(z(0, 7, 7, 3), z(0), z(0), z(0, TOK_MAX), np.zeros(1, np.int64))
 
     # ---- ways in ----
     @classmethod
@@ -193,6 +272,14 @@ class DemoStore(object):
             return cls(*parts[0])
         lens = np.concatenate([np.diff(p[4]) for p in parts])
         return cls(*[torch.cat([p[i] for p in parts]) for i in range(4)], np.concatenate([[0], np.cumsum(lens)]))
+
+    @classmethod
+    def collect_seeds(cls, env_name, seeds, device="cuda:0", pool=32768, chunk=None, env=None):
+        """One demonstration per LISTED seed (`generate_demos(env_name, seeds)` of scripts/train_intelligent_expert.py:106-147): for every
+        seeds[j], in order, the episode that `env.seed(seeds[j]); env.reset()` starts, played by the expert, kept iff it ends with
+        reward > 0 and the expert did not give up.  -> (store of the kept demonstrations in the order of `seeds`, kept = their positions in
+        `seeds`, int64 on the host).  min(pool, len(seeds)) envs play the list (see _collect_seeds)."""
+        return _collect_seeds(cls, env_name, seeds, device, pool, chunk, env)
 
     # ---- ways out ----
     def to_reference(self, pack=None):
@@ -281,7 +368,7 @@ def _collect_batch(env_name, seed, n, device, filter_steps, max_steps):
         env.reset()
         dev = env.device
         budget = max_steps if max_steps is not None else 64 * env.max_steps_bound
-        chunk = max(1, min(128, max(16, env.max_steps_bound // 4), budget))
+        chunk = collect_chunk(env.max_steps_bound, budget)
         free_b, _ = torch.cuda.mem_get_info(dev)
         chunk_bytes = chunk * n * (147 + 72 + 6 + 4)
         max_chunks = max(2, int(free_b // 2 // max(1, chunk_bytes)))          # the history's memory bound of generate_demos
@@ -334,6 +421,251 @@ def _pack(hist, span, chunk):
                                        direction.data_ptr(), action.data_ptr(), tokens.data_ptr(), stream), "bbai_demo_pack")
         torch.cuda.current_stream(dev).synchronize()                       # the history may be freed (and the env closed) after this
     return image, direction, action, tokens, offset_host
+
+
+def collect_chunk(max_steps_bound, budget=None):
+    """Steps per bot_rollout call of `collect` and `collect_seeds`."""
+    chunk = min(128, max(16, max_steps_bound // 4))
+    return max(1, chunk if budget is None else min(chunk, budget))
+
+
+def demo_jobs(done, gave_up, reward, g0, job, start, job_seeds, ids_out, seeds_out, records, counters):
+    """One chunk of history of a pool of envs that play a list of seeds (include/bbai.h bbai_demo_jobs): done / gave_up / reward [chunk, n] of
+    one bot_rollout call whose row 0 is global step g0; job int32[n] (position in the list, -1 = idle) and start int32[n] (global step the
+    episode began at), updated in place; job_seeds int64[J] (the list, uint64 bit patterns); ids_out / seeds_out int64[n] = the lists for
+    `reseed` (ids_out = -1 where the env claimed nothing); records int32[n, 4] = (env, first step, length, job) of the episodes kept in
+    this call; counters int64[4] = job cursor (in / out), finished (running total), records and frames of this call.  ROCm tensors:
+    k_demo_jobs, which hands the jobs out wave by wave in whatever order the waves arrive; host tensors: the same in torch ops, jobs in
+    env order."""
+    import torch
+    chunk, n = done.shape
+    J = int(job_seeds.shape[0])
+    if done.is_cuda:
+        from .engine import _check
+        for t, dt in ((done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), (job, torch.int32), (start, torch.int32), (job_seeds, torch.int64),
+                      (ids_out, torch.int64), (seeds_out, torch.int64), (records, torch.int32), (counters, torch.int64)):
+            assert t.is_contiguous() and t.dtype == dt and t.device == done.device
+        assert job.shape[0] == start.shape[0] == ids_out.shape[0] == seeds_out.shape[0] == n and tuple(records.shape) == (n, 4) and counters.shape[0] == 4
+        with torch.cuda.device(done.device):
+            lib, stream = _lib_stream(done.device)
+            _check(lib, lib.bbai_demo_jobs(n, chunk, done.data_ptr(), gave_up.data_ptr(), reward.data_ptr(), int(g0), job.data_ptr(), start.data_ptr(),
+                                           job_seeds.data_ptr(), J, ids_out.data_ptr(), seeds_out.data_ptr(), records.data_ptr(), counters.data_ptr(),
+                                           stream), "bbai_demo_jobs")
+        return counters
+    cols = torch.arange(n)
+    done_b = done != 0
+    fin = done_b.any(dim=0) & (job >= 0)
+    first = done_b.to(torch.uint8).argmax(dim=0)                         # the first done row of every column
+    keep = fin & (gave_up[first, cols] == 0) & (reward[first, cols] > 0)
+    kept = keep.nonzero().reshape(-1)
+    lens = (g0 + first[kept] - start[kept] + 1).to(torch.int32)
+    records[:len(kept)] = torch.stack([kept.to(torch.int32), start[kept], lens, job[kept]], dim=1)
+    done_ = fin.nonzero().reshape(-1)
+    nxt = int(counters[0]) + torch.arange(len(done_))
+    ok = nxt < J
+    ids_out.fill_(-1)
+    ids_out[done_[ok]] = done_[ok]
+    seeds_out[done_[ok]] = job_seeds[nxt[ok]]
+    job[done_] = torch.where(ok, nxt, torch.full_like(nxt, -1)).to(torch.int32)
+    start[done_[ok]] = g0 + chunk
+    counters[0] += len(done_)
+    counters[1] += len(done_)
+    counters[2] = len(kept)
+    counters[3] = int(lens.sum())
+    return counters
+
+
+def demo_pack_list(ring, chunk, records, frames, table=None):
+    """The records of `demo_jobs` -> a store of their demonstrations, in the records' order (include/bbai.h bbai_demo_pack_list).  `ring`: the
+    R history slots (bot_rollout results of `chunk` steps with tokens), global step g = row g % chunk of slot (g // chunk) % R; records
+    int32[k, 4] on the slots' device; frames = the sum of their lengths (known from demo_jobs' counters: nothing is read back here).
+    `table`: the device table of the slots' pointers, if the caller keeps one."""
+    import torch
+    dev, R, k = records.device, len(ring), int(records.shape[0])
+    n = int(ring[0]["done"].shape[1])
+    offset = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(records[:, 2].to(torch.int64), 0, out=offset[1:])
+    if records.is_cuda:
+        from .engine import _check
+        assert records.is_contiguous() and records.dtype == torch.int32
+        if table is None:
+            table = ring_table(ring)
+        with torch.cuda.device(dev):
+            u8 = dict(dtype=torch.uint8, device=dev)
+            image, direction = torch.empty((frames, 7, 7, 3), **u8), torch.empty(frames, **u8)
+            action, tokens = torch.empty(frames, **u8), torch.empty((k, TOK_MAX), **u8)
+            lib, stream = _lib_stream(dev)
+            _check(lib, lib.bbai_demo_pack_list(k, frames, n, chunk, R, table.data_ptr(), records.data_ptr(), offset.data_ptr(), image.data_ptr(),
+                                                direction.data_ptr(), action.data_ptr(), tokens.data_ptr(), stream), "bbai_demo_pack_list")
+        return DemoStore(image, direction, action, tokens, offset=offset)
+    rec = records.to(torch.int64)
+    demo = torch.repeat_interleave(torch.arange(k), rec[:, 2])
+    g = rec[demo, 1] + torch.arange(frames) - offset[demo]
+    slot, row, env = (g // chunk) % R, g % chunk, rec[demo, 0]
+    hist = {key: torch.stack([r[key] for r in ring]) for key in ("image", "direction", "action", "tokens")}          # [R, chunk, n, ...]
+    g1 = rec[:, 1]
+    return DemoStore(hist["image"][slot, row, env], hist["direction"][slot, row, env], hist["action"][slot, row, env],
+                     hist["tokens"][(g1 // chunk) % R, g1 % chunk, rec[:, 0]], offset.numpy().copy(), offset)
+
+
+def ring_table(ring):
+    """The device table of bbai_demo_chunk entries of history slots.  The pack kernels fetch the aligned 16-byte words around the rows they
+    need (include/bbai.h): every array must start 16-byte aligned in an allocation padded to a multiple of 16 bytes, as torch's caching
+    allocator hands them out (blocks start 512-byte aligned and are rounded up to 512 bytes)."""
+    import torch
+    keys = ("image", "direction", "action", "tokens")
+    for r in ring:
+        for k in keys:
+            assert r[k].data_ptr() % 16 == 0
+    return torch.as_tensor(np.array([[r[k].data_ptr() for k in keys] for r in ring], dtype=np.int64), device=ring[0]["image"].device)
+
+
+def _seed_array(seeds):
+    """uint64[J] from any sequence or array of integers below 2^64"""
+    if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:
+        return np.ascontiguousarray(seeds).reshape(-1)
+    vals = [int(v) for v in np.asarray(seeds, dtype=object).reshape(-1)]
+    if any(v < 0 or v >= 1 << 64 for v in vals):
+        raise ValueError("collect_seeds: seeds are integers in [0, 2^64)")
+    return np.array(vals, dtype=np.uint64)
+
+
+ROUND_EVENTS = None         # measurement aid (tools/seed_demos_bench.py): a list collects (part, start event, end event) of every round of collect_seeds
+
+
+class _Timed(object):
+    """`with _Timed(dev, part):` brackets a part of a round by HIP events on the current stream while ROUND_EVENTS is a list."""
+
+    def __init__(self, dev, part):
+        self.on = ROUND_EVENTS is not None and dev.type == "cuda"
+        self.dev, self.part = dev, part
+
+    def __enter__(self):
+        if self.on:
+            import torch
+            self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            self.ev[0].record(torch.cuda.current_stream(self.dev))
+
+    def __exit__(self, *exc):
+        if self.on:
+            import torch
+            self.ev[1].record(torch.cuda.current_stream(self.dev))
+            ROUND_EVENTS.append((self.part, self.ev[0], self.ev[1]))
+
+
+def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
+    """A pool of P = min(pool, J) auto-resetting envs plays the J listed seeds, rounds of `chunk` expert steps each: bot_rollout into the next
+    slot of a ring of history slots, one k_demo_jobs launch (which episodes ended, which are kept, who plays what next), one read of its four
+    counters -- the round's only synchronisation --, a reseed of the envs that finished with the device lists the kernel wrote, and, if
+    anything was kept, one k_demo_pack_list launch into a part that the staging store is extended by.  An env that finished goes on through
+    its stream until the round ends (rows nobody reads); an episode therefore always starts on a round's first row and ends within
+    max_steps_bound steps, so a ring of ceil(max_steps_bound / chunk) + 1 slots never overwrites a row that a live episode needs.  The
+    staging order depends on which wave claimed what; the result -- the staging store's demos sorted by job -- does not.  `env`: any
+    object with num_envs, device, max_steps_bound, bot_rollout(steps, tokens, out), reseed(ids, seeds) and close(), already created on the
+    first num_envs seeds with auto-reset, token rows on and reset() behind it (the host build in the tests); pool = its size."""
+    import torch
+    seeds_h = _seed_array(seeds)
+    J = len(seeds_h)
+    if J == 0:
+        return cls.empty(env.device if env is not None else ("cpu" if not torch.cuda.is_available() else device)), np.zeros(0, np.int64)
+    own = env is None
+    if own:
+        from .engine import BatchedBabyAIEnv
+        if int(pool) < 1:
+            raise ValueError("collect_seeds: pool must be at least 1")
+        env = BatchedBabyAIEnv(env_name, min(int(pool), J), device=device, seeds=seeds_h[:min(int(pool), J)], auto_reset=True)
+    try:
+        P, dev = int(env.num_envs), torch.device(env.device)
+        if P > J:
+            raise ValueError("collect_seeds: %d envs for %d seeds" % (P, J))
+        if own:
+            env.enable_instr_tokens()
+            env.reset()
+        bound = int(env.max_steps_bound)
+        chunk = collect_chunk(bound) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("collect_seeds: chunk must be at least 1")
+        R = -(-bound // chunk) + 1
+        if dev.type == "cuda":
+            free_b, _ = torch.cuda.mem_get_info(dev)
+            need = R * chunk * P * 229
+            if need > free_b // 2:
+                fit = max(1, int(free_b // 2 // (R * chunk * 229)))
+                raise ValueError("collect_seeds: the history ring of %d slots x %d steps x %d envs needs %.1f GB, more than half of the free device "
+                                 "memory: use pool=%d or less" % (R, chunk, P, need / 1e9, fit))
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        job, start = torch.arange(P, **i32), torch.zeros(P, **i32)
+        job_seeds = torch.as_tensor(seeds_h.view(np.int64), device=dev)
+        ids_out, seeds_out = torch.full((P,), -1, **i64), torch.zeros(P, **i64)
+        records = torch.zeros((P, 4), **i32)
+        counters = torch.as_tensor(np.array([P, 0, 0, 0], dtype=np.int64), device=dev)
+        ring = [{"image": torch.empty((chunk, P, 7, 7, 3), **u8), "direction": torch.empty((chunk, P), **u8), "action": torch.empty((chunk, P), **u8),
+                 "reward": torch.empty((chunk, P), dtype=torch.float32, device=dev), "done": torch.empty((chunk, P), **u8),
+                 "gave_up": torch.empty((chunk, P), **u8), "tokens": torch.empty((chunk, P, TOK_MAX), **u8)} for _ in range(R)]
+        table = ring_table(ring) if dev.type == "cuda" else None
+        staging, kept_records = cls.empty(dev), []
+        g0 = rnd = finished = 0
+        cursor = P
+        while finished < J:
+            if g0 + 2 * chunk > 0x7fffffff:
+                raise RuntimeError("collect_seeds: the global step index would pass 2^31: use a larger pool, or fewer seeds per call")
+            slot = ring[rnd % R]
+            with _Timed(dev, "bot_rollout"):
+                env.bot_rollout(chunk, tokens=True, out=slot)
+            with _Timed(dev, "k_demo_jobs"):
+                demo_jobs(slot["done"], slot["gave_up"], slot["reward"], g0, job, start, job_seeds, ids_out, seeds_out, records, counters)
+            c = counters.cpu().numpy()                                          # 8 bytes per counter: the round's one synchronisation
+            claimed, ended, nrec, frames = int(c[0]) - cursor, int(c[1]) - finished, int(c[2]), int(c[3])
+            if claimed and cursor < J:
+                with _Timed(dev, "reseed"):
+                    env.reseed(ids_out, seeds_out)
+            if nrec:
+                rec = records[:nrec].clone()
+                kept_records.append(rec)
+                with _Timed(dev, "pack"):
+                    part = demo_pack_list(ring, chunk, rec, frames, table)
+                with _Timed(dev, "extend"):
+                    staging.extend(part)
+            cursor, finished = cursor + claimed, finished + ended
+            g0 += chunk
+            rnd += 1
+        if not kept_records:
+            return cls.empty(dev), np.zeros(0, np.int64)
+        jobs = torch.cat(kept_records)[:, 3].cpu().numpy().astype(np.int64)
+        order = np.argsort(jobs, kind="stable")
+        result = staging.select(order)
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()                       # the ring may be freed (and the env closed) after this
+        return result, jobs[order]
+    finally:
+        if own:
+            env.close()
+
+
+def grow_training_set(store, policy, env_name, eval_seed, grow_factor, num_eval_demos, device="cuda:0", pixel=False, pool=None, max_rounds=64):
+    """`grow_training_set` of scripts/train_intelligent_expert.py:150-176, step for step: until `store` holds int(len(store) * grow_factor)
+    demonstrations, evaluate `policy` (a tensor policy of `evaluate.evaluate_policy`) on num_eval_demos fresh seeds from eval_seed on (:158-160),
+    move eval_seed past them (:166), take the seeds of the episodes with return <= 0 in episode order, cut to the number still missing
+    (:162-165, :168), have the expert make one demonstration for each (`DemoStore.collect_seeds`, :169) and extend the store (:171).  Returns
+    the new eval_seed (:176).  `pool`: the env pool of both the evaluation and the collection (None: one env per evaluation episode, the
+    default pool of collect_seeds).  The reference loops for ever under a learner that never fails -- or whose failures the expert cannot
+    solve either; here `max_rounds` evaluations in a row that add nothing raise RuntimeError."""
+    from .evaluate import evaluate_policy
+    target = int(len(store) * grow_factor)
+    idle = 0
+    while len(store) < target:
+        logs = evaluate_policy(policy, env_name, eval_seed, num_eval_demos, pixel=pixel, device=device, pool=pool)
+        eval_seed += num_eval_demos
+        fail = [s for s, r in zip(logs["seed_per_episode"], logs["return_per_episode"]) if r <= 0][:target - len(store)]
+        before = len(store)
+        if fail:
+            new, _ = DemoStore.collect_seeds(env_name, fail, device=device, **({} if pool is None else {"pool": pool}))
+            store.extend(new)
+        idle = 0 if len(store) > before else idle + 1
+        if idle >= max_rounds:
+            raise RuntimeError("grow_training_set: %d evaluations in a row added no demonstration" % idle)
+    return eval_seed
 
 
 def run_batch(acmodel, batch, recurrence, entropy_coef, optimizer=None):

@@ -374,6 +374,31 @@ typedef struct bbai_demo_chunk { const uint8_t* image; const uint8_t* dir; const
 int bbai_demo_pack(int64_t n, int64_t frames, int chunk_steps, const bbai_demo_chunk* chunks_dev, const int32_t* span_dev,
                    const int64_t* offset_dev, uint8_t* image_out, uint8_t* dir_out, uint8_t* action_out, uint8_t* tokens_out, void* stream);
 
+/* Expert demonstrations for LISTED seeds (babyai_amd/imitation.py DemoStore.collect_seeds).  The reference's
+ * scripts/train_intelligent_expert.py:106-147 generate_demos(env_name, seeds) plays ONE episode per listed seed -- env.seed(seed);
+ * env.reset() (:115-116), BotAgent acts until done (:121-133) -- and keeps it iff reward > 0 (:134-139); reward == 0 is logged and dropped
+ * (:140-141), a bot exception skips the seed (:142-144).  Its caller grow_training_set (:150-176) asks for the seeds the learner failed on.
+ * Here a POOL of n envs plays the list: after every bbai_bot_rollout chunk, bbai_demo_jobs finds the envs whose episode ended (the first done
+ * row of the chunk's column), appends a record for every kept one -- gave_up == 0 and reward > 0 on that row -- and hands each of them the
+ * next unplayed position of the list, as the fixed-length, -1-padded id / seed lists that bbai_reseed takes.
+ *   job_dev int32[n]    in / out: the list position env i plays, -1 = idle;     start_dev int32[n]: the global step its episode began at
+ *   job_seeds_dev       uint64[n_jobs], the list;     g0: global step index of the chunk's row 0 (episodes begin on a chunk's row 0 only)
+ *   ids_out int64[n] / seeds_out uint64[n]: env i itself and its new seed where it claimed a job, ids_out = -1 everywhere else
+ *   records_out int32[n][4]: (env, first step, length, job) of the episodes kept in this call, in no particular order
+ *   counters_dev uint64[4]: [0] job cursor (in / out; the caller starts it at the number of jobs already handed out, it may end above
+ *   n_jobs), [1] episodes finished so far (running total), [2] records and [3] their frames in THIS call (zeroed by the call). */
+int bbai_demo_jobs(int64_t n, int chunk, const uint8_t* done_dev, const uint8_t* gave_up_dev, const float* reward_dev, int64_t g0, int32_t* job_dev,
+                   int32_t* start_dev, const uint64_t* job_seeds_dev, int64_t n_jobs, int64_t* ids_out, uint64_t* seeds_out, int32_t* records_out,
+                   uint64_t* counters_dev, void* stream);
+
+/* bbai_demo_pack for a list of records of bbai_demo_jobs (what train_intelligent_expert.py:139 appends per kept seed): demo k = rows
+ * records[k][1] .. + records[k][2] - 1 of stream records[k][0], and the history is a RING of ring_slots chunks of chunk_steps rows
+ * [t][n_streams] each: global step g = row g % chunk_steps of table entry (g / chunk_steps) % ring_slots.  offset_dev int64[count + 1] =
+ * exclusive prefix sum of the lengths, frames = offset[count].  Chunks and outputs aligned and padded as for bbai_demo_pack. */
+int bbai_demo_pack_list(int64_t count, int64_t frames, int64_t n_streams, int chunk_steps, int ring_slots, const bbai_demo_chunk* chunks_dev,
+                        const int32_t* records_dev, const int64_t* offset_dev, uint8_t* image_out, uint8_t* dir_out, uint8_t* action_out,
+                        uint8_t* tokens_out, void* stream);
+
 /* A list of demonstrations of a store -> one flat batch (babyai/imitation.py:226-251 without transform_demos' Python lists): demo
  * order_dev[b] of the store (offset_dev int64[D + 1], src_image / src_action) becomes frames dst_start_dev[b] .. dst_start_dev[b + 1]
  * (int64[count + 1], last entry = frames).  Batch form: action_out int64[frames], done_out uint8[frames] (1 on a demo's last frame),
