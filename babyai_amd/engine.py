@@ -48,99 +48,110 @@ def check_tile_size(tile_size):
     return ts
 
 
-def load_library():
-    """dlopen the HIP engine; raises EngineError (never falls back to a CPU path)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise EngineError("HIP engine %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
-    # torch first: the PyTorch-ROCm wheel carries its own libamdhip64; whichever HIP runtime is mapped first serves
-    # the whole process, and the engine must share torch's (device pointers and streams cross the boundary).
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-    lib.bbai_version.restype = ctypes.c_int
-    lib.bbai_last_error.restype = ctypes.c_char_p
-    lib.bbai_fill_layout.argtypes = [P]
-    lib.bbai_create.argtypes = [P, I64, I32, ctypes.POINTER(P)]
-    lib.bbai_destroy.argtypes = [P]
-    lib.bbai_destroy.restype = None
-    lib.bbai_seed.argtypes = [P, P, I64]
-    lib.bbai_reset.argtypes = [P, P, P, P]
-    lib.bbai_step.argtypes = [P, P, P, P, P, P, P, I32, P]
-    if hasattr(lib, "bbai_step_render"):        # (A/B runs against older experiment builds, BBAI_ENGINE_LIB: they lack the newer entries)
-        lib.bbai_step_render.argtypes = [P, P, P, P, P, P, P, I32, P, P]
-    lib.bbai_set_atlas.argtypes = [P, P, I32, P]
-    lib.bbai_render.argtypes = [P, P, P, P]
-    if hasattr(lib, "bbai_set_render_target"):
-        lib.bbai_set_render_target.argtypes = [P, P]
-        lib.bbai_render_invalidate.argtypes = [P]
-    if hasattr(lib, "bbai_render_shadow"):
-        lib.bbai_render_shadow.argtypes = [P, P, P]
-    if hasattr(lib, "bbai_render_grid"):
-        lib.bbai_set_grid_atlas.argtypes = [P, I32, P, I32, P]
-        lib.bbai_render_grid.argtypes = [P, I32, I32, P, I64, P, P]
-    if hasattr(lib, "bbai_render_view"):
-        lib.bbai_set_view_atlas.argtypes = [P, I32, P, I32, P]
-        lib.bbai_render_view.argtypes = [P, I32, P, I64, P, I64, P, P]
-    if hasattr(lib, "bbai_observe_full"):
-        lib.bbai_observe_full.argtypes = [P, P, I64, P, P]
-        lib.bbai_step_full.argtypes = [P, P, P, P, P, P, P, I32, P, P]
-    lib.bbai_set_token_buffer.argtypes = [P, P]
-    lib.bbai_export_state.argtypes = [P, I64, I64, P, P, P]
-    lib.bbai_import_state.argtypes = [P, I64, I64, P, P, P]
-    if hasattr(lib, "bbai_save_state"):
-        lib.bbai_save_state.argtypes = [P, P, I64, P, P, P, P, P]
-        lib.bbai_load_state.argtypes = [P, P, P, I64, I64, P, P, P, P, P, P, P]
-    if hasattr(lib, "bbai_reseed"):
-        lib.bbai_reseed.argtypes = [P, P, P, I64, P, P, P]
-    lib.bbai_get_programs.argtypes = [P, I64, I64, P]
-    lib.bbai_tap.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P]
-    lib.bbai_tap_ids.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P]
-    if hasattr(lib, "bbai_step_tapped"):
-        lib.bbai_step_tap_set.argtypes = [P, P, I64]
-        lib.bbai_step_tapped.argtypes = [P, P, P, P, P, P, P, I32, P, P, P, P, P]
-    lib.bbai_gae.argtypes = [I64, I32, P, P, P, P, P, ctypes.c_double, ctypes.c_double, P, P, P]
-    if hasattr(lib, "bbai_demo_spans"):
-        lib.bbai_demo_spans.argtypes = [I64, I32, P, P, P, I64, I32, P, P, P, P, P]
-        lib.bbai_demo_pack.argtypes = [I64, I64, I32, P, P, P, P, P, P, P, P]
-        lib.bbai_demo_batch.argtypes = [I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]
-    if hasattr(lib, "bbai_demo_jobs"):
-        lib.bbai_demo_jobs.argtypes = [I64, I32, P, P, P, I64, P, P, P, I64, P, P, P, P, P]
-        lib.bbai_demo_pack_list.argtypes = [I64, I64, I64, I32, I32, P, P, P, P, P, P, P, P]
-    lib.bbai_set_call_events.argtypes = [P, I32]
-    lib.bbai_profile.argtypes = [P, I32]
-    lib.bbai_profile_read.argtypes = [P, P, P]
-    lib.bbai_checkpoint_bytes.argtypes = [P]
-    lib.bbai_checkpoint_bytes.restype = I64
-    lib.bbai_checkpoint_save.argtypes = [P, P, I64]
-    lib.bbai_checkpoint_load.argtypes = [P, P, I64]
-    lib.bbai_reset_count.argtypes = [P, P]
-    lib.bbai_generator_failures.argtypes = [P, P]
-    lib.bbai_bot_act.argtypes = [P, P, P, P]
-    lib.bbai_bot_stats.argtypes = [P, P, P]
-    lib.bbai_bot_rollout.argtypes = [P, I32, P, P, P, P, P, P, P, P, P, P]
-    lib.bbai_set_done_actions.argtypes = [P, I32]
-    lib.bbai_rollout.argtypes = [P, I32, P, P, P, P, P, P, I32, P, P, P]
-    lib.bbai_set_option.argtypes = [P, ctypes.c_char_p, I64]
-    lib.bbai_get_option.argtypes = [P, ctypes.c_char_p, ctypes.POINTER(I64)]
-    lib.bbai_get_done_actions.argtypes = [P]
-    _lib = lib
+P, I64, I32, F64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+_STEP = [P, P, P, P, P, P, P, I32]      # env, actions, image, direction, reward, reward64, done, auto_reset: how every stepping entry begins
+
+# include/bbai.h as ctypes sees it, in the header's order: entry -> (restype, argtypes).  tests/test_binding_host.py holds every row to its prototype.
+ABI = {
+    "bbai_version": (I32, []),
+    "bbai_last_error": (ctypes.c_char_p, []),
+    "bbai_fill_layout": (I32, [P]),
+    "bbai_create": (I32, [P, I64, I32, ctypes.POINTER(P)]),
+    "bbai_destroy": (None, [P]),
+    "bbai_seed": (I32, [P, P, I64]),
+    "bbai_reset": (I32, [P, P, P, P]),
+    "bbai_step": (I32, _STEP + [P]),
+    "bbai_set_atlas": (I32, [P, P, I32, P]),
+    "bbai_render": (I32, [P, P, P, P]),
+    "bbai_step_render": (I32, _STEP + [P, P]),
+    "bbai_set_render_target": (I32, [P, P]),
+    "bbai_render_invalidate": (I32, [P]),
+    "bbai_render_shadow": (I32, [P, P, P]),
+    "bbai_set_grid_atlas": (I32, [P, I32, P, I32, P]),
+    "bbai_render_grid": (I32, [P, I32, I32, P, I64, P, P]),
+    "bbai_set_view_atlas": (I32, [P, I32, P, I32, P]),
+    "bbai_render_view": (I32, [P, I32, P, I64, P, I64, P, P]),
+    "bbai_observe_full": (I32, [P, P, I64, P, P]),
+    "bbai_step_full": (I32, _STEP + [P, P]),
+    "bbai_set_token_buffer": (I32, [P, P]),
+    "bbai_export_state": (I32, [P, I64, I64, P, P, P]),
+    "bbai_import_state": (I32, [P, I64, I64, P, P, P]),
+    "bbai_get_programs": (I32, [P, I64, I64, P]),
+    "bbai_save_state": (I32, [P, P, I64, P, P, P, P, P]),
+    "bbai_load_state": (I32, [P, P, P, I64, I64, P, P, P, P, P, P, P]),
+    "bbai_reseed": (I32, [P, P, P, I64, P, P, P]),
+    "bbai_checkpoint_bytes": (I64, [P]),
+    "bbai_checkpoint_save": (I32, [P, P, I64]),
+    "bbai_checkpoint_load": (I32, [P, P, I64]),
+    "bbai_bot_act": (I32, [P, P, P, P]),
+    "bbai_bot_rollout": (I32, [P, I32, P, P, P, P, P, P, P, P, P, P]),
+    "bbai_bot_stats": (I32, [P, P, P]),
+    "bbai_tap": (I32, [I64, I64] + [P] * 11),
+    "bbai_tap_ids": (I32, [I64, I64] + [P] * 12),
+    "bbai_step_tap_set": (I32, [P, P, I64]),
+    "bbai_step_tapped": (I32, _STEP + [P, P, P, P, P]),
+    "bbai_rollout": (I32, [P, I32, P, P, P, P, P, P, I32, P, P, P]),
+    "bbai_gae": (I32, [I64, I32, P, P, P, P, P, F64, F64, P, P, P]),
+    "bbai_demo_spans": (I32, [I64, I32, P, P, P, I64, I32, P, P, P, P, P]),
+    "bbai_demo_pack": (I32, [I64, I64, I32] + [P] * 8),
+    "bbai_demo_jobs": (I32, [I64, I32, P, P, P, I64, P, P, P, I64, P, P, P, P, P]),
+    "bbai_demo_pack_list": (I32, [I64, I64, I64, I32, I32] + [P] * 8),
+    "bbai_demo_batch": (I32, [I64, I64] + [P] * 14),
+    "bbai_profile": (I32, [P, I32]),
+    "bbai_profile_read": (I32, [P, P, P]),
+    "bbai_set_call_events": (I32, [P, I32]),
+    "bbai_set_done_actions": (I32, [P, I32]),
+    "bbai_get_done_actions": (I32, [P]),
+    "bbai_set_option": (I32, [P, ctypes.c_char_p, I64]),
+    "bbai_get_option": (I32, [P, ctypes.c_char_p, ctypes.POINTER(I64)]),
+    "bbai_reset_count": (I32, [P, P]),
+    "bbai_generator_failures": (I32, [P, P]),
+}
+EXPORTED_SYMBOLS = tuple(ABI)
+
+
+def bind(lib):
+    """Give every entry of ABI that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older experiment
+    builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
-EXPORTED_SYMBOLS = (
-    "bbai_version", "bbai_last_error", "bbai_fill_layout", "bbai_create", "bbai_destroy", "bbai_seed",
-    "bbai_reset", "bbai_step", "bbai_set_atlas", "bbai_render", "bbai_set_token_buffer", "bbai_export_state", "bbai_import_state",
-    "bbai_get_programs", "bbai_reset_count", "bbai_generator_failures", "bbai_bot_act", "bbai_bot_stats",
-    "bbai_checkpoint_bytes", "bbai_checkpoint_save", "bbai_checkpoint_load", "bbai_profile", "bbai_profile_read", "bbai_gae", "bbai_tap",
-    "bbai_tap_ids", "bbai_set_call_events", "bbai_bot_rollout", "bbai_set_done_actions", "bbai_get_done_actions",
-    "bbai_set_option", "bbai_get_option", "bbai_rollout", "bbai_step_render", "bbai_step_tap_set", "bbai_step_tapped",
-    "bbai_set_render_target", "bbai_render_invalidate", "bbai_render_shadow", "bbai_set_grid_atlas", "bbai_render_grid", "bbai_observe_full", "bbai_step_full",
-    "bbai_demo_spans", "bbai_demo_pack", "bbai_demo_batch", "bbai_set_view_atlas", "bbai_render_view",
-    "bbai_save_state", "bbai_load_state", "bbai_reseed", "bbai_demo_jobs", "bbai_demo_pack_list",
-)
+def load_library():
+    """dlopen the HIP engine; raises EngineError (never falls back to a CPU path)."""
+    global _lib
+    if _lib is None:
+        if not os.path.isfile(LIB_PATH):
+            raise EngineError("HIP engine %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
+        # torch first: the PyTorch-ROCm wheel carries its own libamdhip64; whichever HIP runtime is mapped first serves
+        # the whole process, and the engine must share torch's (device pointers and streams cross the boundary).
+        import torch  # noqa: F401
+        _lib = bind(ctypes.CDLL(LIB_PATH))
+    return _lib
+
+
+def seeds_u64(seeds, what):
+    """uint64[k] on the host from a seed list: a uint64 ndarray as it is, else any sequence or array of integers in [0, 2^64) -- ValueError
+    ("negative" / "uint64", after `what`) for a value outside."""
+    if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:
+        return np.ascontiguousarray(seeds).reshape(-1)
+    vals = [int(v) for v in np.asarray(seeds if isinstance(seeds, np.ndarray) else list(seeds), dtype=object).reshape(-1)]
+    if any(v < 0 for v in vals):
+        raise ValueError("%s: negative seed" % what)
+    if any(v >= 1 << 64 for v in vals):
+        raise ValueError("%s: seeds are uint64" % what)
+    return np.array(vals, dtype=np.uint64)
+
+
+def load_atlas(path, tool):
+    """(tiles, lut) of a tile atlas file as contiguous uint8; `tool`: what writes the file, for the EngineError if it is not there."""
+    if not os.path.isfile(path):
+        raise EngineError("tile atlas %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` (%s)" % (path, tool))
+    with np.load(path) as f:
+        return np.ascontiguousarray(f["tiles"], dtype=np.uint8), np.ascontiguousarray(f["lut"], dtype=np.uint8)
 
 
 def _check(lib, rc, what):
@@ -305,6 +316,13 @@ class BatchedBabyAIEnv(object):
         if done_actions is not None:
             _check(self.lib, self.lib.bbai_set_done_actions(self.handle, 1 if done_actions else 0), "bbai_set_done_actions")
         self.done_actions = bool(self.lib.bbai_get_done_actions(self.handle))
+        self._missions = None
+        self._obs_version = 0
+        self._atlases = set()          # (picture, tile size) of the tile atlases installed on the handle (_install_atlas)
+        self._hold = {}                # entry -> the tensors its last call handed to the device: alive until that entry's next call
+        self.instr = None              # enable_instr_tokens(): uint8[N, 72]
+        self._bot_out = None           # bot_actions(): its default output
+        self._step_tap = 0             # set_step_tap(): how many envs step_tapped() logs
         n = self.num_envs
         with torch.cuda.device(self.dev_index):
             self.image = torch.zeros((n, 7, 7, 3), dtype=torch.uint8, device=self.device)
@@ -323,22 +341,15 @@ class BatchedBabyAIEnv(object):
                 # RGBImgPartialObsWrapper(env, 16 | 32): whole frames by bbai_render_view -- no bbai_set_atlas, no registered target
                 ts = self.tile_size
                 self.pixels = torch.zeros((n, 7 * ts, 7 * ts, 3), dtype=torch.uint8, device=self.device)
-                self._view_atlases = set()
-                self._install_view_atlas(ts)
+                self._install_atlas("view", ts)
             elif self.pixel:
                 self.pixels = torch.zeros((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
-                atlas = np.load(ATLAS_PATH)
-                tiles = np.ascontiguousarray(atlas["tiles"], dtype=np.uint8)
-                lut = np.ascontiguousarray(atlas["lut"], dtype=np.uint8)
-                _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0],
-                                                          lut.ctypes.data), "bbai_set_atlas")
+                self._install_atlas("view", 8)
                 # renders into self.pixels store only the lines that changed (include/bbai.h bbai_set_render_target)
                 if hasattr(self.lib, "bbai_set_render_target"):
                     _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
-        self._missions = None
-        self._obs_version = 0
-        self._grid_atlases = set()      # tile sizes whose full-grid atlas is installed on the handle (render_grid)
-        self._view_atlases = getattr(self, "_view_atlases", set())      # ... whose view atlas is (render_view; 16 / 32)
+        # (the five output tensors are never replaced: their pointers are taken once, see _step_out)
+        self._out_ptrs = tuple(t.data_ptr() for t in (self.image, self.direction, self.reward, self.reward64, self.done))
         self.kernel_events = None      # bench.py: list of (tag, start_event, end_event) when enabled
         self.num_actions = 7
         self.max_mission_tokens = min(TOK_MAX, missions.max_mission_tokens(self.cfg))
@@ -351,8 +362,7 @@ class BatchedBabyAIEnv(object):
         """env.seed(s) for every env: an int base (env i gets base + i) or a sequence."""
         if isinstance(seeds, (int, np.integer)):
             seeds = np.arange(self.num_envs, dtype=np.uint64) + np.uint64(seeds)
-        seeds = np.ascontiguousarray(np.asarray(list(seeds) if not isinstance(seeds, np.ndarray) else seeds,
-                                                dtype=np.uint64))
+        seeds = seeds_u64(seeds, "seed")
         if seeds.shape != (self.num_envs,):
             raise ValueError("need %d seeds, got shape %s" % (self.num_envs, seeds.shape))
         _check(self.lib, self.lib.bbai_seed(self.handle, seeds.ctypes.data, self.num_envs), "bbai_seed")
@@ -397,9 +407,21 @@ class BatchedBabyAIEnv(object):
                                                    self._stream()), "bbai_render")
             self._ev_end("render", ev)
             img = self.pixels
+        return self._obs_dict(img)
+
+    def _moved_on(self):
+        """Behind every call that steps or replaces envs: the mission views handed out so far belong to an earlier step (Missions._fetch)."""
         self._obs_version += 1
+
+    def _obs_dict(self, img):
+        """The observation dict of the step, reset or load that was just enqueued, with its own mission view."""
+        self._moved_on()
         self._missions = Missions(self)
         return {"image": img, "direction": self.direction, "mission": self._missions}
+
+    def _step_out(self):
+        """What every stepping entry takes behind its actions (include/bbai.h bbai_step): image, direction, reward, reward64, done, auto_reset."""
+        return self._out_ptrs + (1 if self.auto_reset else 0,)
 
     def render_encoding(self, image=None, out=None, tile_size=None):
         """RGBImgPartialObsWrapper(env, tile_size).observation for ANY encoded batch uint8[N,7,7,3] on the device (default: the current
@@ -421,23 +443,27 @@ class BatchedBabyAIEnv(object):
         _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
         return out
 
-    def _install_view_atlas(self, ts):
-        if ts in self._view_atlases:
+    def _install_atlas(self, picture, ts):
+        """The tile atlas of `picture` at tile size ts on the handle, on first use: "view" = the agent's 7x7 view (8: bbai_render's 56x56 atlas;
+        16 / 32: bbai_render_view's), "grid" = the full grid (bbai_render_grid)."""
+        if (picture, ts) in self._atlases:
             return
-        if not hasattr(self.lib, "bbai_render_view"):
-            raise EngineError("this engine library has no bbai_render_view (tile_size %d)" % ts)
-        if not os.path.isfile(VIEW_ATLAS_PATH % ts):
-            raise EngineError("tile atlas %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(tools/gen_atlas.py --tile-size %d)" % (VIEW_ATLAS_PATH % ts, ts))
-        with np.load(VIEW_ATLAS_PATH % ts) as f:
-            tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
-            lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
-        _check(self.lib, self.lib.bbai_set_view_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_view_atlas")
-        self._view_atlases.add(ts)
+        if picture == "grid":
+            tiles, lut = load_atlas(GRID_ATLAS_PATH % ts, "tools/gen_grid_atlas.py")
+            _check(self.lib, self.lib.bbai_set_grid_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_grid_atlas")
+        elif ts == 8:
+            tiles, lut = load_atlas(ATLAS_PATH, "tools/gen_atlas.py")
+            _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_atlas")
+        else:
+            if not hasattr(self.lib, "bbai_render_view"):
+                raise EngineError("this engine library has no bbai_render_view (tile_size %d)" % ts)
+            tiles, lut = load_atlas(VIEW_ATLAS_PATH % ts, "tools/gen_atlas.py --tile-size %d" % ts)
+            _check(self.lib, self.lib.bbai_set_view_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_view_atlas")
+        self._atlases.add((picture, ts))
 
     def _render_view_into(self, image, ids_ptr, k, ts, out):
         """bbai_render_view: rows `ids_ptr` (None = the first k) of the encoded buffer `image` -> out uint8[k, 7ts, 7ts, 3]."""
-        self._install_view_atlas(ts)
+        self._install_atlas("view", ts)
         _check(self.lib, self.lib.bbai_render_view(self.handle, ts, image.data_ptr(), image.numel() // OBS_BYTES, ids_ptr, k,
                                                     out.data_ptr() if k else None, self._stream()), "bbai_render_view")
         return out
@@ -450,25 +476,21 @@ class BatchedBabyAIEnv(object):
         at 32); an id outside [0, num_envs) gives an all-zero frame.  tile_size=8 goes through bbai_render (56x56 frames)."""
         torch = self.torch
         ts = check_tile_size(self.tile_size if tile_size is None else tile_size)
-        k, ids_ptr = self._id_list(ids)
+        k, ids_ptr, ids_t = self._ids(ids)
         out = self._frames_out(out, (k, 7 * ts, 7 * ts, 3))
         if ts != 8:
+            self._hold["render_view"] = ids_t
             return self._render_view_into(self.image, ids_ptr, k, ts, out)
         if k == 0:
             return out
         # bbai_render draws num_envs rows into num_envs frames: the listed rows are gathered and go through in runs of num_envs
-        if not (self.pixel and not self.full_obs and self.tile_size == 8) and not getattr(self, "_ts8_atlas", False):
-            with np.load(ATLAS_PATH) as f:
-                tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
-                lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
-            _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_atlas")
-            self._ts8_atlas = True
+        self._install_atlas("view", 8)
         n = self.num_envs
         with torch.cuda.device(self.dev_index):
             enc, bad = self.image, None
-            if ids is not None:
-                bad = (self._grid_ids < 0) | (self._grid_ids >= n)
-                enc = self.image[self._grid_ids.clamp(0, n - 1)]
+            if ids_t is not None:
+                bad = (ids_t < 0) | (ids_t >= n)
+                enc = self.image[ids_t.clamp(0, n - 1)]
             keep = []
             for lo in range(0, k, n):
                 m = min(n, k - lo)
@@ -480,7 +502,7 @@ class BatchedBabyAIEnv(object):
                 if m < n:
                     out[lo:lo + m] = dst[:m]
                 keep.append((src, dst))
-            self._ts8_runs = keep      # keep alive until the launches are consumed
+            self._hold["render_view"] = (ids_t, keep)
             if bad is not None:
                 out[bad] = 0           # an id outside the batch: an all-zero frame, as at 16 / 32
         return out
@@ -490,37 +512,37 @@ class BatchedBabyAIEnv(object):
         an int64 device tensor, any order, repeats allowed) -> uint8[k, H*ts, W*ts, 3] on the device, asynchronous on the current stream
         (include/bbai.h bbai_render_grid).  Reads the current state and writes nothing but `out`; an id outside [0, num_envs) gives an
         all-zero frame.  The atlas of a tile size is installed on first use."""
-        torch = self.torch
-        ts = int(tile_size)
-        if ts not in GRID_TILE_SIZES:
-            raise ValueError("tile_size %r: the engine has atlases for %s only (tools/gen_grid_atlas.py makes them)" % (tile_size, GRID_TILE_SIZES))
-        if ts not in self._grid_atlases:
-            if not os.path.isfile(GRID_ATLAS_PATH % ts):
-                raise EngineError("tile atlas %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                                  "(tools/gen_grid_atlas.py)" % (GRID_ATLAS_PATH % ts))
-            with np.load(GRID_ATLAS_PATH % ts) as f:
-                tiles = np.ascontiguousarray(f["tiles"], dtype=np.uint8)
-                lut = np.ascontiguousarray(f["lut"], dtype=np.uint8)
-            _check(self.lib, self.lib.bbai_set_grid_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_grid_atlas")
-            self._grid_atlases.add(ts)
-        k, ids_ptr = self._id_list(ids)
+        ts = check_tile_size(tile_size)
+        self._install_atlas("grid", ts)
+        k, ids_ptr, self._hold["render_grid"] = self._ids(ids)
         out = self._frames_out(out, (k, self.cfg.H * ts, self.cfg.W * ts, 3))
         _check(self.lib, self.lib.bbai_render_grid(self.handle, ts, 1 if highlight else 0, ids_ptr, k, out.data_ptr() if k else None,
                                                     self._stream()), "bbai_render_grid")
         return out
 
-    def _id_list(self, ids):
-        """(k, device pointer or None) of an env id list: None = every env; an int sequence or an int64 device tensor."""
+    def _ids(self, ids):
+        """An env id list -- None = every env; an int sequence, an ndarray or an int64 device tensor -- as (k, device pointer, int64[k] tensor
+        on the device), pointer and tensor None for every env.  The caller keeps the tensor in self._hold until its launch is consumed."""
         torch = self.torch
         if ids is None:
-            return self.num_envs, None
+            return self.num_envs, None, None
         if not isinstance(ids, torch.Tensor):
             ids = torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1), device=self.device)
         if ids.dtype != torch.int64 or ids.device != self.device or ids.dim() != 1:
             raise ValueError("ids: int64[k] on %s" % (self.device,))
         ids = ids.contiguous()
-        self._grid_ids = ids            # keep alive until the launch is consumed
-        return int(ids.shape[0]), ids.data_ptr()
+        return int(ids.shape[0]), ids.data_ptr(), ids
+
+    def _no_env_twice(self, what, ids, padding=False):
+        """ValueError if a HOST-side id list names an env twice (a device list is not read back: there it is undefined which entry wins).
+        padding=True: ids outside [0, num_envs) name no env and may repeat (reseed)."""
+        if ids is None or isinstance(ids, self.torch.Tensor):
+            return
+        host = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if padding:
+            host = host[(host >= 0) & (host < self.num_envs)]
+        if len(np.unique(host)) != len(host):
+            raise ValueError("%s: an env is listed twice" % what)
 
     def _frames_out(self, out, shape):
         torch = self.torch
@@ -541,7 +563,7 @@ class BatchedBabyAIEnv(object):
             out = self.full
         if self.full_obs and self.pixel:
             return self.render_grid(ids, tile_size=self.tile_size, highlight=False, out=out)
-        k, ids_ptr = self._id_list(ids)
+        k, ids_ptr, self._hold["observe_full"] = self._ids(ids)
         out = self._frames_out(out, (k, self.cfg.W, self.cfg.H, 3))
         _check(self.lib, self.lib.bbai_observe_full(self.handle, ids_ptr, k, out.data_ptr() if k else None, self._stream()),
                "bbai_observe_full")
@@ -588,26 +610,19 @@ class BatchedBabyAIEnv(object):
             actions = actions.to(device=self.device, dtype=torch.uint8).contiguous()
         if actions.numel() != self.num_envs:
             raise ValueError("need %d actions" % self.num_envs)
-        self._actions = actions     # keep alive until the launch is consumed
+        self._hold["actions"] = actions
         ev = self._ev_begin()
         if self.full_obs and not self.pixel and self.kernel_events is None:
             # FullyObsWrapper's step: transition + the full observation of every env as ONE call (include/bbai.h bbai_step_full)
-            _check(self.lib, self.lib.bbai_step_full(self.handle, actions.data_ptr(), self.image.data_ptr(),
-                                                      self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
-                                                      self.done.data_ptr(), 1 if self.auto_reset else 0, self.full.data_ptr(),
-                                                      self._stream()), "bbai_step_full")
+            _check(self.lib, self.lib.bbai_step_full(self.handle, actions.data_ptr(), *self._step_out(), self.full.data_ptr(), self._stream()),
+                   "bbai_step_full")
             return self._obs(rendered=True), self.reward, self.done, {}
         if self.pixel and not self.full_obs and self.tile_size == 8 and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
             # the wrapped env's step: transition + render as ONE call (include/bbai.h bbai_step_render)
-            _check(self.lib, self.lib.bbai_step_render(self.handle, actions.data_ptr(), self.image.data_ptr(),
-                                                        self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
-                                                        self.done.data_ptr(), 1 if self.auto_reset else 0, self.pixels.data_ptr(),
-                                                        self._stream()), "bbai_step_render")
+            _check(self.lib, self.lib.bbai_step_render(self.handle, actions.data_ptr(), *self._step_out(), self.pixels.data_ptr(), self._stream()),
+                   "bbai_step_render")
             return self._obs(rendered=True), self.reward, self.done, {}
-        _check(self.lib, self.lib.bbai_step(self.handle, actions.data_ptr(), self.image.data_ptr(),
-                                             self.direction.data_ptr(), self.reward.data_ptr(), self.reward64.data_ptr(),
-                                             self.done.data_ptr(),
-                                             1 if self.auto_reset else 0, self._stream()), "bbai_step")
+        _check(self.lib, self.lib.bbai_step(self.handle, actions.data_ptr(), *self._step_out(), self._stream()), "bbai_step")
         self._ev_end("step", ev)
         return self._obs(), self.reward, self.done, {}
 
@@ -641,19 +656,15 @@ class BatchedBabyAIEnv(object):
                          tap["reward64"].data_ptr(), tap["done"].data_ptr(), pix.data_ptr() if pix is not None else None, int(obs_row0), int(row0))
             if tap["image"].shape[0] < obs_row0 + T or tap["done"].shape[0] < row0 + T:
                 raise ValueError("tap log has too few rows for %d steps" % T)
-        self._actions = actions
-        _check(self.lib, self.lib.bbai_rollout(self.handle, T, actions.data_ptr(), self.image.data_ptr(), self.direction.data_ptr(),
-                                                self.reward.data_ptr(), self.reward64.data_ptr(), self.done.data_ptr(), 1 if self.auto_reset else 0,
+        self._hold["actions"] = actions
+        _check(self.lib, self.lib.bbai_rollout(self.handle, T, actions.data_ptr(), *self._step_out(),
                                                 self.pixels.data_ptr() if self.pixels is not None and not big else None, ctypes.byref(log) if log is not None else None,
                                                 self._stream()), "bbai_rollout")
         if big:
             self._render_view_into(self.image, None, self.num_envs, self.tile_size, self.pixels)
         if self.full_obs:
             self.observe_full()          # the last step's full observation (the tap log keeps its 7x7 rows)
-        self._obs_version += 1
-        self._missions = Missions(self)
-        image = self.full if self.full_obs else self.pixels if self.pixel else self.image
-        return {"image": image, "direction": self.direction, "mission": self._missions}
+        return self._obs_dict(self.full if self.full_obs else self.pixels if self.pixel else self.image)
 
     # ---- state access -------------------------------------------------------------------
     def programs(self, first=0, count=None):
@@ -700,7 +711,7 @@ class BatchedBabyAIEnv(object):
         this batch's device: one launch on the current stream, no host trip.  Row k = env ids[k]; an id outside [0, num_envs) leaves its
         row zeroed."""
         torch = self.torch
-        k, ids_ptr = self._id_list(ids)
+        k, ids_ptr, self._hold["save_state"] = self._ids(ids)
         with torch.cuda.device(self.dev_index):
             u8 = dict(dtype=torch.uint8, device=self.device)
             snap = EnvSnapshot(torch.zeros((k, self.cfg.rec_bytes), **u8), torch.zeros((k, 16), **u8),
@@ -721,17 +732,13 @@ class BatchedBabyAIEnv(object):
             raise ValueError("snapshot with %d-byte records, this batch has %d" % (snap.rec_bytes, self.cfg.rec_bytes))
         if snap.done_actions != self.done_actions:
             raise ValueError("snapshot taken with done_actions=%s, this batch runs with done_actions=%s" % (snap.done_actions, self.done_actions))
-        if ids is not None and not isinstance(ids, self.torch.Tensor):
-            host = np.asarray(ids, dtype=np.int64).reshape(-1)
-            if len(np.unique(host)) != len(host):
-                raise ValueError("load_state: an env is listed twice")
+        self._no_env_twice("load_state", ids)
         k = self.num_envs if ids is None else int(len(ids))
         kr = len(snap) if rows is None else int(len(rows))
         if rows is None and ids is None and kr < k:
             raise ValueError("load_state without ids and rows needs a snapshot of all %d envs, got %d rows" % (k, kr))
         if (rows is not None or ids is not None) and kr != k:
             raise ValueError("load_state: %d envs listed for %d rows" % (k, kr))
-        return k
 
     def load_state(self, snap, ids=None, rows=None):
         """Put envs `ids` (None = every env) into the states of snapshot rows `rows` (None = row k into ids[k]; else an int sequence or an
@@ -747,12 +754,9 @@ class BatchedBabyAIEnv(object):
         tensors = tuple(t.contiguous() for t in (snap.rec, snap.hot, snap.stale, snap.lsm))
         if tensors[0].dtype != torch.uint8 or tensors[1].dtype != torch.uint8 or tensors[2].dtype != torch.int64 or tensors[3].dtype != torch.uint8:
             raise ValueError("snapshot tensors: uint8 rec / hot / lsm, int64 stale")
-        k, ids_ptr = self._id_list(ids)
-        ids_keep = self._grid_ids if ids is not None else None
-        rows_ptr = None
-        if rows is not None:
-            _, rows_ptr = self._id_list(rows)
-        self._snap_keep = (tensors, ids_keep, self._grid_ids if rows is not None else None)      # alive until the launch is consumed
+        k, ids_ptr, ids_t = self._ids(ids)
+        _, rows_ptr, rows_t = self._ids(rows)
+        self._hold["load_state"] = (tensors, ids_t, rows_t)
         _check(self.lib, self.lib.bbai_load_state(self.handle, ids_ptr, rows_ptr, k, len(snap), tensors[0].data_ptr(), tensors[1].data_ptr(),
                                                    tensors[2].data_ptr(), tensors[3].data_ptr(), self.image.data_ptr(),
                                                    self.direction.data_ptr(), self._stream()), "bbai_load_state")
@@ -760,34 +764,20 @@ class BatchedBabyAIEnv(object):
 
     # ---- per-episode seeds (include/bbai.h bbai_reseed) ---------------------------------------------------------------
     def _reseed_args(self, ids, seeds):
-        """reseed's checks and conversions, before any device work: (k, ids tensor or None, seeds tensor int64[k] on the device).
-        ValueError for host-side `ids` with duplicates, for lists of different lengths and for negative seeds."""
+        """reseed's checks and conversions, before the id list goes to the device: (k, seeds tensor int64[k] on the device).  ValueError for
+        host-side `ids` that list an env twice, for lists of different lengths and for seeds outside uint64 ("negative")."""
         torch = self.torch
-        if ids is not None and not isinstance(ids, torch.Tensor):
-            host = np.asarray(ids, dtype=np.int64).reshape(-1)
-            host = host[(host >= 0) & (host < self.num_envs)]          # (padding names no env)
-            if len(np.unique(host)) != len(host):
-                raise ValueError("reseed: an env is listed twice")
+        self._no_env_twice("reseed", ids, padding=True)
         k = self.num_envs if ids is None else int(len(ids))
         if isinstance(seeds, torch.Tensor):
             if seeds.dim() != 1 or seeds.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or seeds.device != self.device:
                 raise ValueError("seeds: int64 / uint64 [k] on %s" % (self.device,))
-            if int(seeds.shape[0]) != k:
-                raise ValueError("reseed: %d envs listed for %d seeds" % (k, int(seeds.shape[0])))
             seeds_t = seeds.contiguous().view(torch.int64)          # (the same bits; the device does not check their sign)
         else:
-            if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:
-                host = np.ascontiguousarray(seeds).reshape(-1)
-            else:
-                vals = [int(v) for v in np.asarray(seeds, dtype=object).reshape(-1)]
-                if any(v < 0 for v in vals):
-                    raise ValueError("reseed: negative seed")
-                if any(v >= 1 << 64 for v in vals):
-                    raise ValueError("reseed: seeds are uint64")
-                host = np.array(vals, dtype=np.uint64)
-            if len(host) != k:
-                raise ValueError("reseed: %d envs listed for %d seeds" % (k, len(host)))
-            seeds_t = torch.as_tensor(host.view(np.int64), device=self.device) if k else torch.zeros((0,), dtype=torch.int64, device=self.device)
+            host = seeds_u64(seeds, "reseed")
+            seeds_t = torch.as_tensor(host.view(np.int64), device=self.device) if len(host) else torch.zeros((0,), dtype=torch.int64, device=self.device)
+        if int(seeds_t.shape[0]) != k:
+            raise ValueError("reseed: %d envs listed for %d seeds" % (k, int(seeds_t.shape[0])))
         return k, seeds_t
 
     def reseed(self, ids, seeds):
@@ -800,8 +790,8 @@ class BatchedBabyAIEnv(object):
         k, seeds_t = self._reseed_args(ids, seeds)
         if k == 0:
             return self._obs()
-        _, ids_ptr = self._id_list(ids)
-        self._reseed_keep = (seeds_t, self._grid_ids if ids is not None else None)       # alive until the launch is consumed
+        _, ids_ptr, ids_t = self._ids(ids)
+        self._hold["reseed"] = (ids_t, seeds_t)
         _check(self.lib, self.lib.bbai_reseed(self.handle, ids_ptr, seeds_t.data_ptr(), k, self.image.data_ptr(), self.direction.data_ptr(),
                                                self._stream()), "bbai_reseed")
         return self._obs()
@@ -819,13 +809,13 @@ class BatchedBabyAIEnv(object):
         is not part of the blob: callers that need it keep `image` / `direction` next to it (or step once)."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         _check(self.lib, self.lib.bbai_checkpoint_load(self.handle, blob.ctypes.data, blob.size), "bbai_checkpoint_load")
-        if getattr(self, "instr", None) is not None:        # refill the caller-owned token rows from the loaded programs
+        if self.instr is not None:        # refill the caller-owned token rows from the loaded programs
             _check(self.lib, self.lib.bbai_set_token_buffer(self.handle, self.instr.data_ptr()), "bbai_set_token_buffer")
 
     def enable_instr_tokens(self):
         """Keep `self.instr` (uint8[N, 72] on the device) filled with the mission token ids of the current
         episodes -- the tensor fast path that replaces per-step regex tokenisation (format.py:59-75)."""
-        if getattr(self, "instr", None) is None:
+        if self.instr is None:
             with self.torch.cuda.device(self.dev_index):
                 self.instr = self.torch.zeros((self.num_envs, TOK_MAX), dtype=self.torch.uint8, device=self.device)
             _check(self.lib, self.lib.bbai_set_token_buffer(self.handle, self.instr.data_ptr()), "bbai_set_token_buffer")
@@ -840,7 +830,7 @@ class BatchedBabyAIEnv(object):
         actions the envs were really stepped with since the last call (advising mode), None = the suggestions."""
         torch = self.torch
         if out is None:
-            if getattr(self, "_bot_out", None) is None:
+            if self._bot_out is None:
                 self._bot_out = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
             out = self._bot_out
         prev_ptr = None
@@ -850,7 +840,7 @@ class BatchedBabyAIEnv(object):
             prev_actions = prev_actions.to(device=self.device, dtype=torch.uint8).contiguous()
             if prev_actions.numel() != self.num_envs:
                 raise ValueError("need %d previous actions" % self.num_envs)
-            self._bot_prev = prev_actions        # keep alive until the launch is consumed
+            self._hold["bot_act"] = prev_actions
             prev_ptr = prev_actions.data_ptr()
         _check(self.lib, self.lib.bbai_bot_act(self.handle, prev_ptr, out.data_ptr(), self._stream()), "bbai_bot_act")
         return out
@@ -888,7 +878,7 @@ class BatchedBabyAIEnv(object):
                                                     out["image"].data_ptr(), out["direction"].data_ptr(), tok_ptr,
                                                     out["action"].data_ptr(), out["reward"].data_ptr(), out["done"].data_ptr(),
                                                     out["gave_up"].data_ptr(), self._stream()), "bbai_bot_rollout")
-        self._obs_version += 1
+        self._moved_on()
         return out
 
     def bot_stats(self):
@@ -928,14 +918,12 @@ class BatchedBabyAIEnv(object):
         `actions`: uint8[num_envs] on the device."""
         if actions.dtype != self.torch.uint8 or actions.device != self.device or not actions.is_contiguous() or actions.numel() != self.num_envs:
             raise ValueError("actions: contiguous uint8[%d] on %s" % (self.num_envs, self.device))
-        if int(done_out.shape[0]) != getattr(self, "_step_tap", 0):
-            raise ValueError("log rows for %d envs, set_step_tap() listed %d" % (int(done_out.shape[0]), getattr(self, "_step_tap", 0)))
-        self._actions = actions
-        _check(self.lib, self.lib.bbai_step_tapped(self.handle, actions.data_ptr(), self.image.data_ptr(), self.direction.data_ptr(),
-                                                    self.reward.data_ptr(), self.reward64.data_ptr(), self.done.data_ptr(),
-                                                    1 if self.auto_reset else 0, image_out.data_ptr(), dir_out.data_ptr(),
+        if int(done_out.shape[0]) != self._step_tap:
+            raise ValueError("log rows for %d envs, set_step_tap() listed %d" % (int(done_out.shape[0]), self._step_tap))
+        self._hold["actions"] = actions
+        _check(self.lib, self.lib.bbai_step_tapped(self.handle, actions.data_ptr(), *self._step_out(), image_out.data_ptr(), dir_out.data_ptr(),
                                                     reward64_out.data_ptr(), done_out.data_ptr(), self._stream()), "bbai_step_tapped")
-        self._obs_version += 1
+        self._moved_on()
         return self.reward, self.done
 
     def set_call_events(self, enable=True):

@@ -29,10 +29,27 @@ from .preprocess import TensorDict, remap_table
 TOK_MAX = 72
 
 
-def _lib_stream(device):
+def _launch(entry, *args):
+    """One call of a handle-free entry of include/bbai.h on the current stream of its tensors' device.  A tensor argument goes in as its
+    pointer, `(tensor, dtype)` as its pointer after a check of the type, None as a null pointer, anything else as it is; the stream goes
+    last.  Every tensor must be contiguous and on the first one's device."""
     import torch
-    from .engine import load_library
-    return load_library(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    from .engine import load_library, _check
+    args = [a if isinstance(a, tuple) else (a, None) for a in args]
+    dev = next(a.device for a, _ in args if isinstance(a, torch.Tensor))
+    for a, dt in args:
+        assert not isinstance(a, torch.Tensor) or (a.is_contiguous() and a.device == dev and dt in (None, a.dtype)), entry
+    with torch.cuda.device(dev):
+        lib = load_library()
+        _check(lib, getattr(lib, entry)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a, _ in args],
+                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), entry)
+
+
+def _store_buffers(frames, demos, dev):
+    """Fresh image, direction, action and token buffers of a store of `demos` demonstrations with `frames` frames."""
+    import torch
+    u8 = dict(dtype=torch.uint8, device=dev)
+    return torch.empty((frames, 7, 7, 3), **u8), torch.empty(frames, **u8), torch.empty(frames, **u8), torch.empty((demos, TOK_MAX), **u8)
 
 
 def demo_spans(done, gave_up, reward, g0, filter_steps, last_done, open_, span, open_count=None):
@@ -43,15 +60,10 @@ def demo_spans(done, gave_up, reward, g0, filter_steps, last_done, open_, span, 
     import torch
     chunk, n = done.shape
     if done.is_cuda:
-        from .engine import _check
-        for t, dt in ((done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), (last_done, torch.int32), (open_, torch.uint8), (span, torch.int32)):
-            assert t.is_contiguous() and t.dtype == dt and t.device == done.device
-        with torch.cuda.device(done.device):
-            if open_count is None:
-                open_count = torch.zeros(1, dtype=torch.int64, device=done.device)
-            lib, stream = _lib_stream(done.device)
-            _check(lib, lib.bbai_demo_spans(n, chunk, done.data_ptr(), gave_up.data_ptr(), reward.data_ptr(), int(g0), int(filter_steps),
-                                            last_done.data_ptr(), open_.data_ptr(), span.data_ptr(), open_count.data_ptr(), stream), "bbai_demo_spans")
+        if open_count is None:
+            open_count = torch.zeros(1, dtype=torch.int64, device=done.device)
+        _launch("bbai_demo_spans", n, chunk, (done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), int(g0), int(filter_steps),
+                (last_done, torch.int32), (open_, torch.uint8), (span, torch.int32), open_count)
         return open_count
     done_b = done != 0
     idx = torch.arange(g0, g0 + chunk, dtype=torch.int32).unsqueeze(1)                       # [chunk, 1]
@@ -84,15 +96,8 @@ def _gather(offset, order, dst_start, frames, src_image, src_dir, src_action, ba
     else:
         out = [torch.empty(frames, dtype=torch.uint8, device=dev), torch.empty(frames, dtype=torch.uint8, device=dev)]
     if src_image.is_cuda:
-        from .engine import _check
-        for t in (offset, order, dst_start, src_image, src_dir, src_action):
-            assert t.is_contiguous() and t.device == dev
-        ptrs = [t.data_ptr() for t in out]
-        args = ptrs + [None, None] if batch_form else [None] * 4 + ptrs
-        with torch.cuda.device(dev):
-            lib, stream = _lib_stream(dev)
-            _check(lib, lib.bbai_demo_batch(B, frames, order.data_ptr(), dst_start.data_ptr(), offset.data_ptr(), src_image.data_ptr(),
-                                            src_dir.data_ptr(), src_action.data_ptr(), image.data_ptr(), *(args + [stream])), "bbai_demo_batch")
+        _launch("bbai_demo_batch", B, frames, order, dst_start, offset, src_image, src_dir, src_action, image,
+                *(out + [None, None] if batch_form else [None] * 4 + out))
         return [image] + out
     lens = dst_start[1:] - dst_start[:-1]
     episode = torch.repeat_interleave(torch.arange(B), lens)
@@ -361,7 +366,7 @@ class DemoStore(object):
 def _collect_batch(env_name, seed, n, device, filter_steps, max_steps):
     """One batch of streams of `DemoStore.collect` (demos._generate_batch with the scan and the gather left on the device)."""
     import torch
-    from .engine import BatchedBabyAIEnv, _check
+    from .engine import BatchedBabyAIEnv
     env = BatchedBabyAIEnv(env_name, n, device=device, seeds=[seed + k for k in range(n)], auto_reset=True)
     try:
         env.enable_instr_tokens()
@@ -398,28 +403,15 @@ def _pack(hist, span, chunk):
     """The spans of a batch of streams (int32[n, 2] on the device) in the history chunks `hist` (bot_rollout results of `chunk` steps each)
     -> (image, direction, action, tokens, offset_host): k_demo_pack."""
     import torch
-    from .engine import _check
     dev, n = span.device, int(span.shape[0])
     lens = (span[:, 1] - span[:, 0] + 1).to(torch.int64)
     offset = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum(lens, 0, out=offset[1:])
     offset_host = offset.cpu().numpy()                                     # the batch's lengths: the one other read
     frames = int(offset_host[-1])
-    # k_demo_pack fetches the aligned 16-byte words around the history rows it needs (include/bbai.h): every chunk array must start
-    # 16-byte aligned in an allocation padded to a multiple of 16 bytes.  torch's caching allocator hands out blocks that start
-    # 512-byte aligned and are rounded up to 512 bytes, whatever chunk * n * 147 is.
-    for r in hist:
-        for k in ("image", "direction", "action", "tokens"):
-            assert r[k].data_ptr() % 16 == 0
-    table = torch.as_tensor(np.array([[r[k].data_ptr() for k in ("image", "direction", "action", "tokens")] for r in hist], dtype=np.int64), device=dev)
-    with torch.cuda.device(dev):
-        u8 = dict(dtype=torch.uint8, device=dev)
-        image, direction = torch.empty((frames, 7, 7, 3), **u8), torch.empty(frames, **u8)
-        action, tokens = torch.empty(frames, **u8), torch.empty((n, TOK_MAX), **u8)
-        lib, stream = _lib_stream(dev)
-        _check(lib, lib.bbai_demo_pack(n, frames, chunk, table.data_ptr(), span.data_ptr(), offset.data_ptr(), image.data_ptr(),
-                                       direction.data_ptr(), action.data_ptr(), tokens.data_ptr(), stream), "bbai_demo_pack")
-        torch.cuda.current_stream(dev).synchronize()                       # the history may be freed (and the env closed) after this
+    image, direction, action, tokens = _store_buffers(frames, n, dev)
+    _launch("bbai_demo_pack", n, frames, chunk, ring_table(hist), span, offset, image, direction, action, tokens)
+    torch.cuda.current_stream(dev).synchronize()                       # the history may be freed (and the env closed) after this
     return image, direction, action, tokens, offset_host
 
 
@@ -441,16 +433,10 @@ def demo_jobs(done, gave_up, reward, g0, job, start, job_seeds, ids_out, seeds_o
     chunk, n = done.shape
     J = int(job_seeds.shape[0])
     if done.is_cuda:
-        from .engine import _check
-        for t, dt in ((done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), (job, torch.int32), (start, torch.int32), (job_seeds, torch.int64),
-                      (ids_out, torch.int64), (seeds_out, torch.int64), (records, torch.int32), (counters, torch.int64)):
-            assert t.is_contiguous() and t.dtype == dt and t.device == done.device
         assert job.shape[0] == start.shape[0] == ids_out.shape[0] == seeds_out.shape[0] == n and tuple(records.shape) == (n, 4) and counters.shape[0] == 4
-        with torch.cuda.device(done.device):
-            lib, stream = _lib_stream(done.device)
-            _check(lib, lib.bbai_demo_jobs(n, chunk, done.data_ptr(), gave_up.data_ptr(), reward.data_ptr(), int(g0), job.data_ptr(), start.data_ptr(),
-                                           job_seeds.data_ptr(), J, ids_out.data_ptr(), seeds_out.data_ptr(), records.data_ptr(), counters.data_ptr(),
-                                           stream), "bbai_demo_jobs")
+        _launch("bbai_demo_jobs", n, chunk, (done, torch.uint8), (gave_up, torch.uint8), (reward, torch.float32), int(g0), (job, torch.int32),
+                (start, torch.int32), (job_seeds, torch.int64), J, (ids_out, torch.int64), (seeds_out, torch.int64), (records, torch.int32),
+                (counters, torch.int64))
         return counters
     cols = torch.arange(n)
     done_b = done != 0
@@ -486,17 +472,9 @@ def demo_pack_list(ring, chunk, records, frames, table=None):
     offset = torch.zeros(k + 1, dtype=torch.int64, device=dev)
     torch.cumsum(records[:, 2].to(torch.int64), 0, out=offset[1:])
     if records.is_cuda:
-        from .engine import _check
-        assert records.is_contiguous() and records.dtype == torch.int32
-        if table is None:
-            table = ring_table(ring)
-        with torch.cuda.device(dev):
-            u8 = dict(dtype=torch.uint8, device=dev)
-            image, direction = torch.empty((frames, 7, 7, 3), **u8), torch.empty(frames, **u8)
-            action, tokens = torch.empty(frames, **u8), torch.empty((k, TOK_MAX), **u8)
-            lib, stream = _lib_stream(dev)
-            _check(lib, lib.bbai_demo_pack_list(k, frames, n, chunk, R, table.data_ptr(), records.data_ptr(), offset.data_ptr(), image.data_ptr(),
-                                                direction.data_ptr(), action.data_ptr(), tokens.data_ptr(), stream), "bbai_demo_pack_list")
+        image, direction, action, tokens = _store_buffers(frames, k, dev)
+        _launch("bbai_demo_pack_list", k, frames, n, chunk, R, ring_table(ring) if table is None else table, (records, torch.int32), offset,
+                image, direction, action, tokens)
         return DemoStore(image, direction, action, tokens, offset=offset)
     rec = records.to(torch.int64)
     demo = torch.repeat_interleave(torch.arange(k), rec[:, 2])
@@ -518,16 +496,6 @@ def ring_table(ring):
         for k in keys:
             assert r[k].data_ptr() % 16 == 0
     return torch.as_tensor(np.array([[r[k].data_ptr() for k in keys] for r in ring], dtype=np.int64), device=ring[0]["image"].device)
-
-
-def _seed_array(seeds):
-    """uint64[J] from any sequence or array of integers below 2^64"""
-    if isinstance(seeds, np.ndarray) and seeds.dtype == np.uint64:
-        return np.ascontiguousarray(seeds).reshape(-1)
-    vals = [int(v) for v in np.asarray(seeds, dtype=object).reshape(-1)]
-    if any(v < 0 or v >= 1 << 64 for v in vals):
-        raise ValueError("collect_seeds: seeds are integers in [0, 2^64)")
-    return np.array(vals, dtype=np.uint64)
 
 
 ROUND_EVENTS = None         # measurement aid (tools/seed_demos_bench.py): a list collects (part, start event, end event) of every round of collect_seeds
@@ -564,7 +532,8 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
     object with num_envs, device, max_steps_bound, bot_rollout(steps, tokens, out), reseed(ids, seeds) and close(), already created on the
     first num_envs seeds with auto-reset, token rows on and reset() behind it (the host build in the tests); pool = its size."""
     import torch
-    seeds_h = _seed_array(seeds)
+    from .engine import seeds_u64
+    seeds_h = seeds_u64(seeds, "collect_seeds")
     J = len(seeds_h)
     if J == 0:
         return cls.empty(env.device if env is not None else ("cpu" if not torch.cuda.is_available() else device)), np.zeros(0, np.int64)

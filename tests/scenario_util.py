@@ -351,17 +351,16 @@ ENTRIES = ("step", "ticks", "ticks_frozen", "rollout_tokens", "step_tapped", "ds
 def _abi_reseed(env, ids, seeds):
     from babyai_amd.engine import _check
     k, seeds_t = env._reseed_args(ids, seeds)
-    _, ids_ptr = env._id_list(ids)
-    env._reseed_keep = (seeds_t, env._grid_ids if ids is not None else None)
+    _, ids_ptr, ids_t = env._ids(ids)
+    env._hold["reseed"] = (ids_t, seeds_t)
     _check(env.lib, env.lib.bbai_reseed(env.handle, ids_ptr, seeds_t.data_ptr(), k, env.image.data_ptr(), env.direction.data_ptr(), env._stream()), "bbai_reseed")
 
 
 def _abi_load(env, snap, ids, rows):
     from babyai_amd.engine import _check
-    k, ids_ptr = env._id_list(ids)
-    ids_keep = env._grid_ids
-    _, rows_ptr = env._id_list(rows)
-    env._snap_keep = (snap, ids_keep, env._grid_ids)
+    k, ids_ptr, ids_t = env._ids(ids)
+    _, rows_ptr, rows_t = env._ids(rows)
+    env._hold["load_state"] = (snap, ids_t, rows_t)
     _check(env.lib, env.lib.bbai_load_state(env.handle, ids_ptr, rows_ptr, k, len(snap), snap.rec.data_ptr(), snap.hot.data_ptr(), snap.stale.data_ptr(),
                                              snap.lsm.data_ptr(), env.image.data_ptr(), env.direction.data_ptr(), env._stream()), "bbai_load_state")
 

@@ -23,10 +23,10 @@ def test_library_exports_all_symbols():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401  (same load order as the product: torch's HIP runtime first)
-    lib = ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
+    from babyai_amd import engine
+    lib = engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
     for sym in declared_symbols():
         assert hasattr(lib, sym), sym
-    lib.bbai_version.restype = ctypes.c_int
     assert lib.bbai_version() >= 100
 
 
@@ -35,8 +35,8 @@ def test_layout_python_twin_matches_native():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401
-    lib = ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
-    lib.bbai_fill_layout.argtypes = [ctypes.c_void_p]
+    from babyai_amd import engine
+    lib = engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
     for name in LEVELS:
         cfg = make_cfg(name)
         twin = LevelCfg.from_buffer_copy(cfg)

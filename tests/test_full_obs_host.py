@@ -137,12 +137,9 @@ def test_header_declares_and_library_exports_the_full_obs_entries():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401  (torch's HIP runtime first, as the product loads it)
-    lib = ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
+    lib = engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
     for name in NAMES:
         assert hasattr(lib, name), name
-    P = ctypes.c_void_p
-    lib.bbai_observe_full.argtypes = [P, P, ctypes.c_int64, P, P]
-    lib.bbai_step_full.argtypes = [P, P, P, P, P, P, P, ctypes.c_int, P, P]
     assert lib.bbai_observe_full(None, None, 1, None, None) == -1                       # BBAI_ERR_ARG: null handle
     assert lib.bbai_step_full(None, None, None, None, None, None, None, 1, None, None) == -1
 

@@ -209,3 +209,47 @@ def test_delta_registered_buffer_alignment(gpu, offset):
         assert torch.equal(a.pixels, b.pixels) and torch.equal(buf, b.pixels), t
     assert a.get_option("render_delta_valid") == (1 if offset == 0 else 0)
     assert raw[:base].eq(0).all() and raw[base + n * 9408:].eq(0).all()
+
+
+@pytest.mark.gpu
+def test_step_then_render_fallback_equals_the_fused_step(gpu, monkeypatch):
+    """A library without bbai_step_render and bbai_set_render_target (an older experiment build): the binding registers no target and steps,
+    then renders -- the same pixels, encodings, rewards and dones as the fused call, step for step, per-env resets included."""
+    import torch
+    from babyai_amd import engine
+    from babyai_amd.engine import BatchedBabyAIEnv
+    lacks = ("bbai_step_render", "bbai_set_render_target")
+
+    class Older(object):
+        def __init__(self, lib):
+            self._real = lib
+
+        def __getattr__(self, name):
+            if name in lacks:
+                raise AttributeError(name)
+            return getattr(self._real, name)
+
+    n, T, level = 65, 48, "BabyAI-GoToLocal-v0"          # a full wave plus one env
+    real = engine.load_library()
+    a = BatchedBabyAIEnv(level, n, device=gpu, pixel=True, seeds=31)
+    _open.append(a)
+    monkeypatch.setattr(engine, "_lib", Older(real))
+    b = BatchedBabyAIEnv(level, n, device=gpu, pixel=True, seeds=31)
+    _open.append(b)
+    monkeypatch.undo()
+    assert a.lib is real and all(hasattr(a.lib, name) for name in lacks)
+    assert not any(hasattr(b.lib, name) for name in lacks) and hasattr(b.lib, "bbai_step")
+    a.reset()
+    b.reset()
+    assert torch.equal(a.pixels, b.pixels) and torch.equal(a.image, b.image)
+    rng = np.random.RandomState(7)
+    for t in range(T):
+        act = rng.randint(0, 7, size=n).astype(np.uint8)
+        if t % 8 == 7:
+            act[rng.choice(n, size=5, replace=False)] = BatchedBabyAIEnv.RESET_ENV
+        act = torch.as_tensor(act, device=gpu)
+        oa, ra, da, _ = a.step(act)
+        ob, rb, db, _ = b.step(act)
+        assert oa["image"] is a.pixels and ob["image"] is b.pixels
+        for k in ("pixels", "image", "reward", "done"):
+            assert torch.equal(getattr(a, k), getattr(b, k)), (k, t)

@@ -29,9 +29,7 @@ def test_render_grid_rejects_unknown_tile_sizes_without_a_gpu():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401
-    lib = ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
-    P = ctypes.c_void_p
-    lib.bbai_render_grid.argtypes = [P, ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P]
-    lib.bbai_set_grid_atlas.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P]
+    from babyai_amd import engine
+    lib = engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
     assert lib.bbai_render_grid(None, 8, 1, None, 1, None, None) == -1
     assert lib.bbai_set_grid_atlas(None, 12, None, 1, None) == -1

@@ -16,7 +16,8 @@ def _lib():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401  (torch's HIP runtime first, as the product loads it)
-    return ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
+    from babyai_amd import engine
+    return engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
 
 
 def test_header_declares_the_entry():
@@ -31,8 +32,6 @@ def test_library_exports_the_entry():
 
 def test_null_handle_calls_are_argument_errors():
     lib = _lib()
-    P, I64 = ctypes.c_void_p, ctypes.c_int64
-    lib.bbai_reseed.argtypes = [P, P, P, I64, P, P, P]
     buf = (ctypes.c_uint64 * 4)()
     for count in (0, 1, -1):
         assert lib.bbai_reseed(None, None, None, count, None, None, None) == -1

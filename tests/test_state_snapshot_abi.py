@@ -16,7 +16,8 @@ def _lib():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401  (torch's HIP runtime first, as the product loads it)
-    return ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
+    from babyai_amd import engine
+    return engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
 
 
 def test_header_declares_the_snapshot_entries():
@@ -34,9 +35,6 @@ def test_library_exports_the_snapshot_entries():
 
 def test_null_handle_calls_are_argument_errors():
     lib = _lib()
-    P, I64 = ctypes.c_void_p, ctypes.c_int64
-    lib.bbai_save_state.argtypes = [P, P, I64, P, P, P, P, P]
-    lib.bbai_load_state.argtypes = [P, P, P, I64, I64, P, P, P, P, P, P, P]
     for count in (0, 1, -1):
         assert lib.bbai_save_state(None, None, count, None, None, None, None, None) == -1
         assert lib.bbai_load_state(None, None, None, count, 1, None, None, None, None, None, None, None) == -1

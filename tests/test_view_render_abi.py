@@ -15,7 +15,8 @@ def _lib():
     import __graft_entry__
     __graft_entry__.build()
     import torch  # noqa: F401  (torch's HIP runtime first, as the product loads it)
-    return ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so"))
+    from babyai_amd import engine
+    return engine.bind(ctypes.CDLL(os.path.join(ROOT, "babyai_amd", "libbbai_hip.so")))
 
 
 def test_header_declares_the_view_render_entries():
@@ -33,9 +34,6 @@ def test_library_exports_the_view_render_entries():
 
 def test_null_handle_calls_are_argument_errors():
     lib = _lib()
-    P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-    lib.bbai_set_view_atlas.argtypes = [P, I32, P, I32, P]
-    lib.bbai_render_view.argtypes = [P, I32, P, I64, P, I64, P, P]
     for ts in (16, 32, 8, 12):
         assert lib.bbai_set_view_atlas(None, ts, None, 1, None) == -1
         assert lib.bbai_render_view(None, ts, None, 1, None, 1, None, None) == -1
