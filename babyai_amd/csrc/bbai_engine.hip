@@ -53,10 +53,12 @@ using namespace bbai;
 static_assert(sizeof(bbai_level_cfg) == sizeof(LevelCfg), "C ABI cfg mirrors bbai::LevelCfg");
 
 static thread_local char g_err[512] = "";
+static thread_local hipError_t g_hip = hipSuccess;      // the HIP error behind the latest BBAI_ERR_HIP (for callers that word the failure themselves)
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess) {                                                               \
+            g_hip = e_;                                                                       \
             snprintf(g_err, sizeof(g_err), "%s:%d %s -> %s", __FILE__, __LINE__, #expr,       \
                      hipGetErrorString(e_));                                                  \
             return BBAI_ERR_HIP;                                                              \
@@ -90,6 +92,64 @@ struct DeviceGuard {
 #define ON_DEVICE(dev)                                                                        \
     DeviceGuard guard_(dev);                                                                  \
     HIP_TRY((hipError_t)guard_.err)
+
+// What a handle holds -- device memory, the pinned host words, streams, events -- is made and let go by the helpers between the two markers below, the
+// only raw allocation / creation calls of this file (tests/test_handle_owner_source.py); none of them launches anything.
+//   Scoped   one resource that dies with its scope unless a field of the handle adopts it: a call's temporaries, and the way a feature gets its
+//            buffers all or none -- the whole group as Scoped, adopted once every piece exists;
+//   Owner    the handle's record: the address of every field that holds a resource right now (the handle lives on the heap and never moves).
+// ---- owner helpers: begin
+enum ResKind : uint8_t { RES_MEM, RES_PINNED, RES_STREAM, RES_EVENT };
+static int res_done(const char* call, hipError_t r) {             // BBAI_OK -- or g_err and g_hip written, BBAI_ERR_HIP
+    if (r != hipSuccess) snprintf(g_err, sizeof(g_err), "%s: %s -> %s", __FILE__, call, hipGetErrorString(g_hip = r));
+    return r == hipSuccess ? BBAI_OK : BBAI_ERR_HIP;
+}
+static hipError_t res_release(ResKind k, void* h) { return k == RES_MEM ? hipFree(h) : k == RES_PINNED ? hipHostFree(h) : k == RES_STREAM ? hipStreamDestroy((hipStream_t)h) : hipEventDestroy((hipEvent_t)h); }
+struct Scoped {
+    ResKind kind = RES_MEM; void* h = nullptr;
+    Scoped() = default; Scoped(const Scoped&) = delete; Scoped& operator=(const Scoped&) = delete;
+    ~Scoped() { reset(); }
+    void reset() { if (h) (void)res_release(kind, h); h = nullptr; }
+    int mem(size_t bytes, bool zero = false) {                   // device memory, zeroed where asked
+        const hipError_t r = hipMalloc(&h, bytes);
+        return r == hipSuccess && zero ? res_done("hipMemset", hipMemset(h, 0, bytes)) : res_done("hipMalloc", r);
+    }
+    int pinned(size_t bytes) { kind = RES_PINNED; return res_done("hipHostMalloc", hipHostMalloc(&h, bytes, hipHostMallocMapped)); }      // mapped pinned host memory
+    int stream(unsigned flags, const int* prio = nullptr) {      // the flags form, or the priority form
+        kind = RES_STREAM;
+        return res_done("hipStreamCreate", prio ? hipStreamCreateWithPriority((hipStream_t*)&h, flags, *prio) : hipStreamCreateWithFlags((hipStream_t*)&h, flags));
+    }
+    int event(unsigned flags = hipEventDisableTiming) {          // (hipEventDefault: the timing pairs of bbai_profile)
+        kind = RES_EVENT;
+        return res_done("hipEventCreate", flags == hipEventDefault ? hipEventCreate((hipEvent_t*)&h) : hipEventCreateWithFlags((hipEvent_t*)&h, flags));
+    }
+};
+struct Owner {
+    struct Held { ResKind kind; void* field; }; struct Want { void* field; size_t bytes; bool zero; };
+    std::vector<Held> held;            // every field of the handle that holds a resource right now, in the order they got it
+    template <class T> void adopt(T* field, Scoped& t) { if (t.h) { *field = (T)t.h; held.push_back({t.kind, (void*)field}); t.h = nullptr; } }      // (into an empty field; an empty temporary is passed over)
+    int alloc(std::initializer_list<Want> wants) {               // device memory into empty fields, in the order given: all of them or none
+        std::vector<Scoped> t(wants.size());
+        size_t i = 0, k = 0;
+        for (const Want& w : wants) BBAI_TRY(t[i++].mem(w.bytes, w.zero));
+        for (const Want& w : wants) adopt((void**)w.field, t[k++]);
+        return BBAI_OK;
+    }
+    int stream(hipStream_t* field, unsigned flags, const int* prio = nullptr) { Scoped t; BBAI_TRY(t.stream(flags, prio)); adopt(field, t); return BBAI_OK; }
+    int event(hipEvent_t* field, unsigned flags = hipEventDisableTiming) { Scoped t; BBAI_TRY(t.event(flags)); adopt(field, t); return BBAI_OK; }
+    int drop(void* field) {                                      // release what the field holds (nothing: fine) and null it
+        for (size_t i = held.size(); i-- > 0;) if (held[i].field == field) {
+            const ResKind kind = held[i].kind;
+            void* h = nullptr;
+            memcpy(&h, field, sizeof(h)); memset(field, 0, sizeof(h));          // (fields are pointers of many types: read and nulled as bytes)
+            held.erase(held.begin() + (long)i);
+            return res_done("release", res_release(kind, h));
+        }
+        return BBAI_OK;
+    }
+    void drop_all() { while (!held.empty()) (void)drop(held.back().field); }       // bbai_destroy: the latest first
+};
+// ---- owner helpers: end
 
 constexpr int PROF_RING = 256;          // event pairs per profiled kernel (bbai_profile)
 constexpr int MAX_SIDES = 8;            // look-ahead streams a window's refill can be split over
@@ -246,6 +306,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* rs_first;    // [n] always zero: a reseeded ring is generated from slot 0
     uint32_t* rs_claim;   // [(n + 31) / 32] zero between calls
     hipEvent_t ev_rs_call, ev_rs_done, ev_rs_part[MAX_SIDES];
+    Owner own;            // every allocation, pinned word, stream and event above (option "owned" counts them; bbai_destroy releases them)
 };
 
 #include "bbai_stepk.hpp"
@@ -312,6 +373,116 @@ static int inplace_by_default(const LevelCfg& c, int64_t n_envs) {
     return c.num_rows * c.num_cols > 1 ? 0 : 1;
 }
 
+// bbai_create's steps, in the order it takes them (a failing one leaves the HIP error in g_hip).  Step 2: the layout (BBAI_INPLACE) and the per-env planes.
+static int create_planes(bbai_env* e) {
+    const LevelCfg& c = e->cfg; const size_t n = (size_t)e->n;
+    BBAI_TRY(e->own.alloc({{&e->rec, n * c.rec_bytes, true},
+                           {&e->hot, n * sizeof(Hot), true},       // (slot 0 before any seed: an in-place handle that is only imported into keeps its live records in slot depth - 1)
+                           {&e->stale, n * 8}, {&e->mt, n * MT_N * 4}, {&e->mti, n * 4}, {&e->vhead, n * 4, true}, {&e->vset, n * 8 * 8, true},
+                           {&e->pending, NWIN * n, true}, {&e->first_slot, NWIN * n, true}, {&e->win_meta, NWIN * META_U32 * 4, true},
+                           {&e->totals, SHARDS * SHARD_U64 * 8, true}, {&e->flow, FLOW_WORDS * 8, true},
+                           {&e->gen_list, (size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4}, {&e->gen_count, SHARDS * GEN_COUNT_U32 * 4}}));
+    e->gen_lists[0] = e->gen_list; e->gen_counts[0] = e->gen_count;         // (further look-ahead streams' lists: set_sides)
+    // BBAI_INPLACE: 1 / 0 force the in-place layout (live_slot, bbai_kernels.hpp) on / off; default: by level family and batch size
+    const char* iv = getenv("BBAI_INPLACE");
+    e->inplace = iv ? (atoi(iv) != 0) : inplace_by_default(c, e->n);
+    const char* vv = getenv("BBAI_VPLANE");              // 0: round 2's record-only step path (A/B runs)
+    if (!(vv && atoi(vv) == 0) && !e->inplace) BBAI_TRY(e->own.alloc({{&e->vplane, n * v_bytes(c), true}, {&e->fcache, n * 2, true}}));
+    const char* cv = getenv("BBAI_CPLANE");              // 0: the in-place step path of rounds 4-5 (window out of the record; A/B runs)
+    if (e->inplace && cpl_ok(c) && !(cv && atoi(cv) == 0)) BBAI_TRY(e->own.alloc({{&e->cplane, n * cpl_bytes(c), true}, {&e->fcache, n * 2, true}}));
+    return BBAI_OK;
+}
+// Step 3: the lane = level generator's state, where the kind and the layout are covered.
+static int create_lane_gen(bbai_env* e) {
+    const LevelCfg& c = e->cfg;
+    if (!(lane_gen_ok(c) && (!e->inplace || cpl_ok(c)))) return BBAI_OK;
+    // Default: the single rooms.  Measured (profiles/r06/NOTES.md): bulk fills 2.2 - 2.9 ns per level against 6 - 7 (PickupLoc 262 144: 0.057 -> 0.043 ms
+    // per step); the mazes' bulk rates are 17 (GoTo) and 31 (BossLevel) ns against 30 and 20, and a maze refill of a few thousand levels
+    // lasts milliseconds as ONE level per lane where the lane-group kernel needs a third of that -- the mazes keep k_pregen.
+    const char* lv = getenv("BBAI_PREGEN_LANE");
+    e->pregen_lane = lv ? (atoi(lv) != 0) : (c.num_rows * c.num_cols == 1);
+    e->lane_words = lane_layout(c).words;
+    std::vector<uint8_t> t((size_t)lane_template_bytes(c));
+    BBAI_TRY(e->own.alloc({{&e->mtt, (size_t)e->n * 2 * MT_N * 4, true}, {&e->mtpar, (size_t)e->n, true}, {&e->lane_tmpl, t.size()}}));
+    lane_build_template(c, t.data());
+    HIP_TRY(hipMemcpy(e->lane_tmpl, t.data(), t.size(), hipMemcpyHostToDevice));
+    return BBAI_OK;
+}
+// The look-ahead ring of one depth as temporaries: next_rec, next_hot and, in the in-place layout, next_obs -- all of them, or none and the sticky
+// out-of-memory error cleared.  ring_install hands them to the handle, letting the ring it had go only now (bbai_checkpoint_load).
+struct Ring { Scoped rec, hot, obs; };
+static int ring_alloc(const bbai_env* e, int depth, Ring& r) {
+    const size_t D = (size_t)depth, n = (size_t)e->n;
+    int rc = r.rec.mem(D * n * e->cfg.rec_bytes);
+    if (rc == BBAI_OK) rc = r.hot.mem(D * n * sizeof(Hot));
+    if (rc == BBAI_OK && e->inplace) rc = r.obs.mem(D * n * OBS_SLOT);
+    if (rc != BBAI_OK) { (void)hipGetLastError(); r.rec.reset(); r.hot.reset(); r.obs.reset(); }
+    return rc;
+}
+static void ring_install(bbai_env* e, Ring& r, int period) {
+    (void)e->own.drop(&e->next_rec); (void)e->own.drop(&e->next_hot); (void)e->own.drop(&e->next_obs);
+    e->own.adopt(&e->next_rec, r.rec); e->own.adopt(&e->next_hot, r.hot); e->own.adopt(&e->next_obs, r.obs);
+    e->period = period; e->depth = 2 * period + e->inplace;          // (in-place: the live slot + the 2B look-ahead levels)
+}
+// Step 4: the ring, at the longest period that fits.
+static int create_ring(bbai_env* e) {
+    const LevelCfg& c = e->cfg;
+    // Refill period B (ticks per look-ahead refill, BBAI_LOOKAHEAD); ring depth D = 2B.  One k_pregen launch per
+    // window lasts as long as its slowest level (hundreds of microseconds to milliseconds: rejection sampling has a
+    // heavy tail) and has to land within one window, so B ticks of the step path must outlast it or the step stream
+    // waits: default = the longest period of 96 (mazes), 64, 32, 16, 8, 4, 2 whose ring fits the cap.  (Up to 32 until round 6.  A refill launch lasts as
+    // long as its slowest WAVE -- 0.4 ms for 64 single-room levels per lane-generator wave, 0.6-0.9 ms for a lane group's maze -- almost whatever its
+    // size, and bbai_rollout's k_step takes 8 us per tick at 65 536 envs: 32 ticks no longer outlast a refill.  GoToLocal 65 536 envs 0.0146 -> 0.0103 ms
+    // per step at 64, GoTo 131 072 0.0344 -> 0.0244 at 64 -> 0.0214 at 96: profiles/r06/NOTES.md section 9.)  The cap is BBAI_RING_GIB
+    // (default 64 GiB -- the part has 288 GB; round 4: 1 048 576 GoTo envs waited for refills at period 4, the 16-GiB cap of
+    // rounds 1-3) but never more than a quarter of the memory that is FREE right now (several handles or ranks
+    // on one device, smaller parts), and an allocation that fails all the same is retried with half the period: a
+    // shorter period only costs speed, never correctness.  (131072 GoTo envs -> 32; 1M BossLevel envs -> 16.)
+    const char* ev = getenv("BBAI_LOOKAHEAD");
+    const char* gv = getenv("BBAI_RING_GIB");
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)64 << 30;
+    const size_t slot_bytes = (size_t)e->n * c.rec_bytes;
+    const size_t cap = std::min((size_t)(gv ? std::max(1, atoi(gv)) : 64) << 30, free_b / 4);
+    int b = 2;
+    if (ev) b = atoi(ev);
+    else for (int cand : {96, 64, 32, 16, 8, 4, 2}) if (cand <= (c.num_rows * c.num_cols > 1 ? 96 : 64))      // (single rooms: 96 measured equal to 64)
+         if (slot_bytes * (2 * (size_t)cand + (size_t)e->inplace) <= cap) { b = cand; break; }
+    b = b < 1 ? 1 : (b > MAX_PERIOD ? MAX_PERIOD : b);
+    for (;; b >>= 1) {
+        Ring r;
+        const int rc = ring_alloc(e, 2 * b + e->inplace, r);
+        if (rc == BBAI_OK) {                           // (the ring that fits starts zeroed; next_hot is written by bbai_seed)
+            ring_install(e, r, b);
+            HIP_TRY(hipMemset(e->next_rec, 0, (size_t)e->depth * slot_bytes));
+            if (e->next_obs) HIP_TRY(hipMemset(e->next_obs, 0, (size_t)e->depth * (size_t)e->n * OBS_SLOT));
+            return BBAI_OK;
+        }
+        if (b == 1 || ev) return rc;                   // an explicit BBAI_LOOKAHEAD is a request, not a hint
+    }
+}
+
+// Step 5: the small buffers.
+static int create_small(bbai_env* e) {
+    const size_t n = (size_t)e->n;
+    // babyai/levels/verifier.py:17 `use_done_actions = os.environ.get('BABYAI_DONE_ACTIONS', False)`: any non-empty value
+    const char* dv = getenv("BABYAI_DONE_ACTIONS");
+    if (dv && dv[0]) BBAI_TRY(e->own.alloc({{&e->lsm, n, true}}));
+    return e->own.alloc({{&e->reset_list, n * 4}, {&e->reset_slot, n}, {&e->counters, 128, true}, {&e->atlas, MAX_TILES * TILE_BYTES},
+                         {&e->render_tickets, 64 * 64 * 4, true}, {&e->lut, 512}});
+}
+// Step 6: the pinned flag words, zeroed, and the device's address of them.
+static int create_pinned(bbai_env* e) {
+    Scoped hf;
+    void* dv = nullptr;
+    BBAI_TRY(hf.pinned(64));
+    memset(hf.h, 0, 64);
+    e->own.adopt(&e->host_flags, hf);
+    HIP_TRY(hipHostGetDevicePointer(&dv, (void*)e->host_flags, 0));
+    e->host_flags_dev = (uint32_t*)dv;
+    return BBAI_OK;
+}
+
 int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env** out) {
     if (!cfg || !out || n_envs <= 0 || n_envs > (1ll << 30)) { snprintf(g_err, sizeof(g_err), "bad argument"); return BBAI_ERR_ARG; }
     LevelCfg c;
@@ -322,133 +493,16 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
         return BBAI_ERR_ARG;
     }
     ON_DEVICE(device);
-    bbai_env* e = new bbai_env();
-    memset(e, 0, sizeof(*e));
+    bbai_env* e = new bbai_env();          // (value-initialised: every field starts zero)
     e->cfg = c; e->n = n_envs; e->device = device;
-    hipError_t err = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (err == hipSuccess) err = hipMalloc(p, bytes); };
-    auto zalloc = [&](void** p, size_t bytes) { alloc(p, bytes); if (err == hipSuccess) err = hipMemset(*p, 0, bytes); };      // starts zeroed
-    zalloc((void**)&e->rec, (size_t)n_envs * c.rec_bytes);
-    zalloc((void**)&e->hot, (size_t)n_envs * sizeof(Hot));        // (slot 0 before any seed: an in-place handle that is only imported into keeps its live records in slot depth - 1)
-    alloc((void**)&e->stale, (size_t)n_envs * 8);
-    alloc((void**)&e->mt, (size_t)n_envs * MT_N * 4);
-    alloc((void**)&e->mti, (size_t)n_envs * 4);
-    zalloc((void**)&e->vhead, (size_t)n_envs * 4);
-    zalloc((void**)&e->vset, (size_t)n_envs * 8 * 8);
-    zalloc((void**)&e->pending, NWIN * (size_t)n_envs);
-    zalloc((void**)&e->first_slot, NWIN * (size_t)n_envs);
-    zalloc((void**)&e->win_meta, NWIN * META_U32 * 4);
-    zalloc((void**)&e->totals, SHARDS * SHARD_U64 * 8);
-    zalloc((void**)&e->flow, FLOW_WORDS * 8);
-    alloc((void**)&e->gen_list, (size_t)SHARDS * (size_t)gen_sublist_cap(n_envs) * 4);
-    alloc((void**)&e->gen_count, SHARDS * GEN_COUNT_U32 * 4);
-    e->gen_lists[0] = e->gen_list; e->gen_counts[0] = e->gen_count;         // (further look-ahead streams' lists: set_sides)
-    {
-        // BBAI_INPLACE: 1 / 0 force the in-place layout (live_slot, bbai_kernels.hpp) on / off; default: by level family and batch size
-        const char* iv = getenv("BBAI_INPLACE");
-        e->inplace = iv ? (atoi(iv) != 0) : inplace_by_default(c, n_envs);
-    }
-    {
-        const char* vv = getenv("BBAI_VPLANE");              // 0: round 2's record-only step path (A/B runs)
-        if (!(vv && atoi(vv) == 0) && !e->inplace) {
-            zalloc((void**)&e->vplane, (size_t)n_envs * v_bytes(c));
-            zalloc((void**)&e->fcache, (size_t)n_envs * 2);
-        }
-        const char* cv = getenv("BBAI_CPLANE");              // 0: the in-place step path of rounds 4-5 (window out of the record; A/B runs)
-        if (e->inplace && cpl_ok(c) && !(cv && atoi(cv) == 0)) {
-            zalloc((void**)&e->cplane, (size_t)n_envs * cpl_bytes(c));
-            zalloc((void**)&e->fcache, (size_t)n_envs * 2);
-        }
-    }
-    if (lane_gen_ok(c) && (!e->inplace || cpl_ok(c))) {
-        // Default: the single rooms.  Measured (profiles/r06/NOTES.md): bulk fills 2.2 - 2.9 ns per level against 6 - 7 (PickupLoc 262 144: 0.057 -> 0.043 ms
-        // per step); the mazes' bulk rates are 17 (GoTo) and 31 (BossLevel) ns against 30 and 20, and a maze refill of a few thousand levels
-        // lasts milliseconds as ONE level per lane where the lane-group kernel needs a third of that -- the mazes keep k_pregen.
-        const char* lv = getenv("BBAI_PREGEN_LANE");
-        e->pregen_lane = lv ? (atoi(lv) != 0) : (c.num_rows * c.num_cols == 1);
-        e->lane_words = lane_layout(c).words;
-        zalloc((void**)&e->mtt, (size_t)n_envs * 2 * MT_N * 4);
-        zalloc((void**)&e->mtpar, (size_t)n_envs);
-        alloc((void**)&e->lane_tmpl, (size_t)lane_template_bytes(c));
-        if (err == hipSuccess) {
-            std::vector<uint8_t> t((size_t)lane_template_bytes(c));
-            lane_build_template(c, t.data());
-            err = hipMemcpy(e->lane_tmpl, t.data(), t.size(), hipMemcpyHostToDevice);
-        }
-    }
-    {
-        // Refill period B (ticks per look-ahead refill, BBAI_LOOKAHEAD); ring depth D = 2B.  One k_pregen launch per
-        // window lasts as long as its slowest level (hundreds of microseconds to milliseconds: rejection sampling has a
-        // heavy tail) and has to land within one window, so B ticks of the step path must outlast it or the step stream
-        // waits: default = the longest period of 96 (mazes), 64, 32, 16, 8, 4, 2 whose ring fits the cap.  (Up to 32 until round 6.  A refill launch lasts as
-        // long as its slowest WAVE -- 0.4 ms for 64 single-room levels per lane-generator wave, 0.6-0.9 ms for a lane group's maze -- almost whatever its
-        // size, and bbai_rollout's k_step takes 8 us per tick at 65 536 envs: 32 ticks no longer outlast a refill.  GoToLocal 65 536 envs 0.0146 -> 0.0103 ms
-        // per step at 64, GoTo 131 072 0.0344 -> 0.0244 at 64 -> 0.0214 at 96: profiles/r06/NOTES.md section 9.)  The cap is BBAI_RING_GIB
-        // (default 64 GiB -- the part has 288 GB; round 4: 1 048 576 GoTo envs waited for refills at period 4, the 16-GiB cap of
-        // rounds 1-3) but never more than a quarter of the memory that is FREE right now (several handles or ranks
-        // on one device, smaller parts), and an allocation that fails all the same is retried with half the period: a
-        // shorter period only costs speed, never correctness.  (131072 GoTo envs -> 32; 1M BossLevel envs -> 16.)
-        const char* ev = getenv("BBAI_LOOKAHEAD");
-        const char* gv = getenv("BBAI_RING_GIB");
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)64 << 30;
-        const size_t slot_bytes = (size_t)n_envs * c.rec_bytes;
-        const size_t cap = std::min((size_t)(gv ? std::max(1, atoi(gv)) : 64) << 30, free_b / 4);
-        int b = 2;
-        if (ev) b = atoi(ev);
-        else for (int cand : {96, 64, 32, 16, 8, 4, 2}) if (cand <= (c.num_rows * c.num_cols > 1 ? 96 : 64))      // (single rooms: 96 measured equal to 64)
-             if (slot_bytes * (2 * (size_t)cand + (size_t)e->inplace) <= cap) { b = cand; break; }
-        b = b < 1 ? 1 : (b > MAX_PERIOD ? MAX_PERIOD : b);
-        for (; err == hipSuccess; b >>= 1) {
-            e->period = b;
-            e->depth = 2 * b + e->inplace;         // (in-place: the live slot + the 2B look-ahead levels)
-            const size_t D = (size_t)e->depth;
-            const size_t obs_bytes = e->inplace ? D * (size_t)n_envs * OBS_SLOT : 0;
-            hipError_t r1 = hipMalloc((void**)&e->next_rec, D * slot_bytes);
-            hipError_t r2 = r1 == hipSuccess ? hipMalloc((void**)&e->next_hot, D * (size_t)n_envs * sizeof(Hot)) : r1;
-            hipError_t r3 = r2;
-            if (r3 == hipSuccess && obs_bytes) r3 = hipMalloc((void**)&e->next_obs, obs_bytes);
-            if (r3 == hipSuccess) {                        // (the ring that fits starts zeroed; next_hot is written by bbai_seed)
-                err = hipMemset(e->next_rec, 0, D * slot_bytes);
-                if (err == hipSuccess && obs_bytes) err = hipMemset(e->next_obs, 0, obs_bytes);
-                break;
-            }
-            (void)hipGetLastError();                       // clear the sticky out-of-memory error before retrying
-            if (e->next_rec) { (void)hipFree(e->next_rec); e->next_rec = nullptr; }
-            if (e->next_hot) { (void)hipFree(e->next_hot); e->next_hot = nullptr; }
-            if (e->next_obs) { (void)hipFree(e->next_obs); e->next_obs = nullptr; }
-            if (b == 1 || ev) err = r3;                    // an explicit BBAI_LOOKAHEAD is a request, not a hint
-        }
-    }
-    {
-        // babyai/levels/verifier.py:17 `use_done_actions = os.environ.get('BABYAI_DONE_ACTIONS', False)`: any non-empty value
-        const char* dv = getenv("BABYAI_DONE_ACTIONS");
-        if (dv && dv[0]) zalloc((void**)&e->lsm, (size_t)n_envs);
-    }
-    alloc((void**)&e->reset_list, (size_t)n_envs * 4);
-    alloc((void**)&e->reset_slot, (size_t)n_envs);
-    zalloc((void**)&e->counters, 128);
-    alloc((void**)&e->atlas, MAX_TILES * TILE_BYTES);
-    zalloc((void**)&e->render_tickets, 64 * 64 * 4);
-    alloc((void**)&e->lut, 512);
-    if (err == hipSuccess) {
-        void* hf = nullptr;
-        err = hipHostMalloc(&hf, 64, hipHostMallocMapped);
-        if (err == hipSuccess) {
-            memset(hf, 0, 64);
-            e->host_flags = (volatile uint32_t*)hf;
-            void* dv = nullptr;
-            err = hipHostGetDevicePointer(&dv, hf, 0);
-            e->host_flags_dev = (uint32_t*)dv;
-        }
-    }
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "hipMalloc failed: %s", hipGetErrorString(err));
+    int rc = BBAI_OK;
+    for (auto step : {create_planes, create_lane_gen, create_ring, create_small, create_pinned}) if (rc == BBAI_OK) rc = step(e);
+    if (rc != BBAI_OK) {
+        snprintf(g_err, sizeof(g_err), "hipMalloc failed: %s", hipGetErrorString(g_hip));
         bbai_destroy(e);
         return BBAI_ERR_NOMEM;
     }
-    int rc = create_finish(e);
-    if (rc != BBAI_OK) { bbai_destroy(e); return rc; }      // g_err holds the failing call
+    if ((rc = create_finish(e)) != BBAI_OK) { bbai_destroy(e); return rc; }      // g_err holds the failing call
     *out = e;
     return BBAI_OK;
 }
@@ -510,58 +564,52 @@ static int knob_value(const Knob& k, int v) {
 // profiles/r06/NOTES.md section 9).
 static int set_sides(bbai_env* e, int want) {
     want = std::max(1, std::min(MAX_SIDES, want));
+    Owner& o = e->own;
+    Scoped side[MAX_SIDES], list[MAX_SIDES], count[MAX_SIDES], mark, part[MAX_SIDES];       // going up: whatever is missing (a lower setting leaves lists and events behind), all of it or none
     for (int k = 1; k < want; ++k) {
-        if (!e->sides[k]) HIP_TRY(hipStreamCreateWithPriority(&e->sides[k], hipStreamNonBlocking, e->side_prio));
-        if (!e->gen_lists[k]) HIP_TRY(hipMalloc((void**)&e->gen_lists[k], (size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4));
-        if (!e->gen_counts[k]) HIP_TRY(hipMalloc((void**)&e->gen_counts[k], SHARDS * GEN_COUNT_U32 * 4));
+        if (!e->sides[k]) BBAI_TRY(side[k].stream(hipStreamNonBlocking, &e->side_prio));
+        if (!e->gen_lists[k]) BBAI_TRY(list[k].mem((size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4));
+        if (!e->gen_counts[k]) BBAI_TRY(count[k].mem(SHARDS * GEN_COUNT_U32 * 4));
     }
-    if (want > 1) {
-        if (!e->mark_stream) HIP_TRY(hipStreamCreateWithPriority(&e->mark_stream, hipStreamNonBlocking, e->side_prio));
-        for (int k = 0; k < want; ++k) if (!e->ev_part[k]) HIP_TRY(hipEventCreateWithFlags(&e->ev_part[k], hipEventDisableTiming));
-    }
-    for (int k = want; k < MAX_SIDES; ++k) if (k >= 1 && e->sides[k]) { HIP_TRY(hipStreamDestroy(e->sides[k])); e->sides[k] = nullptr; }
-    if (want == 1 && e->mark_stream) { HIP_TRY(hipStreamDestroy(e->mark_stream)); e->mark_stream = nullptr; }
+    if (want > 1 && !e->mark_stream) BBAI_TRY(mark.stream(hipStreamNonBlocking, &e->side_prio));
+    for (int k = 0; k < want && want > 1; ++k) if (!e->ev_part[k]) BBAI_TRY(part[k].event());
+    for (int k = 0; k < want; ++k) { o.adopt(&e->sides[k], side[k]); o.adopt(&e->gen_lists[k], list[k]); o.adopt(&e->gen_counts[k], count[k]); o.adopt(&e->ev_part[k], part[k]); }
+    o.adopt(&e->mark_stream, mark);
+    for (int k = std::max(1, want); k < MAX_SIDES; ++k) BBAI_TRY(o.drop(&e->sides[k]));      // going down: the streams go, their lists and events stay
+    if (want == 1) BBAI_TRY(o.drop(&e->mark_stream));
     e->n_sides = want;
     e->n_probed = 0;
     return BBAI_OK;
 }
 static int create_finish(bbai_env* e) {
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess) cus = 0;
-        e->n_cus = cus;
+    if (hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess) e->n_cus = 0;
+    // The look-ahead stream.  (Confining it to a subset of the CUs with a CU mask was measured in round 3 --
+    // profiles/r03/pregen_cus_ab.jsonl: 32 / 64 / 96 / 128 CUs change no step time by more than 1 %, and a masked stream is a
+    // BLOCKING stream: with a caller on the NULL stream it serialises generation and stepping, 46 -> 72 us per step at
+    // 65 536 GoToLocal envs.  Not kept.  Round 6 tried again for callers on their own stream: on this pool's runtime
+    // hipExtStreamCreateWithCUMask changes NOTHING -- a bulk fill confined to 32 of 256 CUs runs at the unconfined rate
+    // (profiles/r06/NOTES.md section 6).)
+    int lo = 0, hi = 0;     // look-ahead generation should get wave slots as soon as any free up
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    const char* pv = getenv("BBAI_PREGEN_PRIORITY");     // 1 (default): highest priority, 0: default priority
+    e->side_prio = (pv && atoi(pv) == 0) ? lo : hi;
+    BBAI_TRY(e->own.stream(&e->side, hipStreamNonBlocking, &e->side_prio));
+    e->sides[0] = e->side;
+    const char* ls = getenv("BBAI_LOOKAHEAD_STREAMS");
+    BBAI_TRY(set_sides(e, ls ? atoi(ls) : LOOKAHEAD_STREAMS_DEFAULT));
+    BBAI_TRY(e->own.event(&e->ev_consumed));
+    BBAI_TRY(e->own.stream(&e->split, hipStreamNonBlocking));
+    BBAI_TRY(e->own.event(&e->ev_split0));
+    BBAI_TRY(e->own.event(&e->ev_splitB));
+    for (int k = 0; k < NWIN; ++k) BBAI_TRY(e->own.event(&e->ev_refill[k]));
+    BBAI_TRY(e->own.event(&e->ev_switch));
+    const char* cv = getenv("BBAI_CALL_EVENTS");
+    e->call_events = cv && atoi(cv) != 0;
+    for (const Knob& k : KNOBS) if (!k.read_only) {
+        const char* kv = k.var ? getenv(k.var) : nullptr;
+        e->*k.field = kv ? knob_value(k, atoi(kv)) : k.def;
     }
-    {
-        // The look-ahead stream.  (Confining it to a subset of the CUs with a CU mask was measured in round 3 --
-        // profiles/r03/pregen_cus_ab.jsonl: 32 / 64 / 96 / 128 CUs change no step time by more than 1 %, and a masked stream is a
-        // BLOCKING stream: with a caller on the NULL stream it serialises generation and stepping, 46 -> 72 us per step at
-        // 65 536 GoToLocal envs.  Not kept.  Round 6 tried again for callers on their own stream: on this pool's runtime
-        // hipExtStreamCreateWithCUMask changes NOTHING -- a bulk fill confined to 32 of 256 CUs runs at the unconfined rate
-        // (profiles/r06/NOTES.md section 6).)
-        int lo = 0, hi = 0;     // look-ahead generation should get wave slots as soon as any free up
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        const char* pv = getenv("BBAI_PREGEN_PRIORITY");     // 1 (default): highest priority, 0: default priority
-        e->side_prio = (pv && atoi(pv) == 0) ? lo : hi;
-        HIP_TRY(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, e->side_prio));
-        e->sides[0] = e->side;
-        const char* ls = getenv("BBAI_LOOKAHEAD_STREAMS");
-        BBAI_TRY(set_sides(e, ls ? atoi(ls) : LOOKAHEAD_STREAMS_DEFAULT));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_consumed, hipEventDisableTiming));
-        HIP_TRY(hipStreamCreateWithFlags(&e->split, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_split0, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_splitB, hipEventDisableTiming));
-        for (int k = 0; k < NWIN; ++k) HIP_TRY(hipEventCreateWithFlags(&e->ev_refill[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_switch, hipEventDisableTiming));
-    }
-    {
-        const char* cv = getenv("BBAI_CALL_EVENTS");
-        e->call_events = cv && atoi(cv) != 0;
-        for (const Knob& k : KNOBS) if (!k.read_only) {
-            const char* kv = k.var ? getenv(k.var) : nullptr;
-            e->*k.field = kv ? knob_value(k, atoi(kv)) : k.def;
-        }
-        if (!e->mtt) e->lane_blocks = 0;        // (no lane generator on this handle)
-    }
+    if (!e->mtt) e->lane_blocks = 0;        // (no lane generator on this handle)
     return BBAI_OK;
 }
 
@@ -571,30 +619,7 @@ void bbai_destroy(bbai_env* e) {
     if (!e) return;
     DeviceGuard guard_(e->device);
     (void)hipDeviceSynchronize();
-    if (e->side) (void)hipStreamDestroy(e->side);
-    for (int k = 1; k < MAX_SIDES; ++k) if (e->sides[k]) (void)hipStreamDestroy(e->sides[k]);
-    if (e->mark_stream) (void)hipStreamDestroy(e->mark_stream);
-    for (int k = 0; k < MAX_SIDES; ++k) if (e->ev_part[k]) (void)hipEventDestroy(e->ev_part[k]);
-    for (int k = 1; k < MAX_SIDES; ++k) { if (e->gen_lists[k]) (void)hipFree(e->gen_lists[k]); if (e->gen_counts[k]) (void)hipFree(e->gen_counts[k]); }
-    if (e->split) (void)hipStreamDestroy(e->split);
-    if (e->ev_split0) (void)hipEventDestroy(e->ev_split0);
-    if (e->ev_splitB) (void)hipEventDestroy(e->ev_splitB);
-    if (e->ev_consumed) (void)hipEventDestroy(e->ev_consumed);
-    if (e->ev_switch) (void)hipEventDestroy(e->ev_switch);
-    if (e->ev_rs_call) (void)hipEventDestroy(e->ev_rs_call);
-    if (e->ev_rs_done) (void)hipEventDestroy(e->ev_rs_done);
-    for (int k = 0; k < MAX_SIDES; ++k) if (e->ev_rs_part[k]) (void)hipEventDestroy(e->ev_rs_part[k]);
-    for (int k = 0; k < NWIN; ++k) if (e->ev_refill[k]) (void)hipEventDestroy(e->ev_refill[k]);
-    for (int k = 0; k < 3; ++k) for (int i = 0; i < PROF_RING; ++i) if (e->prof[k][i].a) { (void)hipEventDestroy(e->prof[k][i].a); (void)hipEventDestroy(e->prof[k][i].b); }
-    void* bot_ptrs[] = {e->bot_state, e->bot_work, e->bot_stats, e->bot_rows};
-    for (void* p : bot_ptrs) if (p) (void)hipFree(p);
-    void* ptrs[] = {e->rec, e->hot, e->stale, e->mt, e->mti, e->vhead, e->vset, e->next_rec, e->next_hot, e->pending, e->first_slot, e->win_meta, e->totals, e->flow, e->gen_list, e->gen_count, e->reset_list, e->counters,
-                    e->atlas, e->lut, e->vplane, e->fcache, e->lsm, e->render_tickets, e->reset_slot, e->next_obs, e->cplane, e->mtt, e->mtpar, e->lane_tmpl, e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids, e->rt_shadow, e->rt_dmask,
-                    e->rs_list, e->rs_count, e->rs_pending, e->rs_first, e->rs_claim};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int k = 0; k < 3; ++k) { if (e->grid_atlas[k]) (void)hipFree(e->grid_atlas[k]); if (e->grid_lut[k]) (void)hipFree(e->grid_lut[k]); }
-    for (int k = 0; k < 2; ++k) { if (e->view_atlas[k]) (void)hipFree(e->view_atlas[k]); if (e->view_lut[k]) (void)hipFree(e->view_lut[k]); }
-    if (e->host_flags) (void)hipHostFree((void*)e->host_flags);
+    e->own.drop_all();
     delete e;
 }
 
@@ -706,7 +731,7 @@ struct ProfScope {
         i = e->prof_pos[k];
         e->prof_pos[k] = (i + 1) % PROF_RING;
         prof_fold(e, k, i);
-        if (!e->prof[k][i].a) { (void)hipEventCreate(&e->prof[k][i].a); (void)hipEventCreate(&e->prof[k][i].b); }
+        if (!e->prof[k][i].a) { (void)e->own.event(&e->prof[k][i].a, hipEventDefault); (void)e->own.event(&e->prof[k][i].b, hipEventDefault); }
         (void)hipEventRecord(e->prof[k][i].a, s);
     }
     ~ProfScope() {
@@ -833,9 +858,9 @@ int bbai_seed(bbai_env* e, const uint64_t* seeds, int64_t n) {
     HIP_TRY(hipDeviceSynchronize());             // nothing of an earlier run may still be in flight on either stream
     // 8 bytes per env cross PCIe; sha512 + init_by_array run per lane (k_seed).  Staged in a buffer of its own (parked in the
     // verifier's obj_set area, a re-seed of a live handle followed by a hot-only import left every env's verifier sets zeroed).
-    uint64_t* seeds_dev = nullptr;
-    HIP_TRY(hipMalloc((void**)&seeds_dev, (size_t)n * 8));
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_seeds{seeds_dev};
+    Scoped staged;
+    BBAI_TRY(staged.mem((size_t)n * 8));
+    uint64_t* const seeds_dev = (uint64_t*)staged.h;
     HIP_TRY(hipMemcpy(seeds_dev, seeds, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_seed, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, e->side, n, seeds_dev, e->mt, e->mti);
     hipLaunchKernelGGL(k_init_hot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->side, n, e->hot, e->next_hot, e->stale, e->depth);
@@ -992,9 +1017,8 @@ int bbai_step_tap_set(bbai_env* e, const int64_t* ids, int64_t count) {
     if (!e || count < 0 || (count && !ids)) ARG_FAIL("null handle or id list");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
-    void* old[] = {e->tap_mask, e->tap_rank0, e->tap_perm, e->tap_ids};
-    for (void* q : old) if (q) (void)hipFree(q);
-    e->tap_mask = nullptr; e->tap_rank0 = nullptr; e->tap_perm = nullptr; e->tap_ids = nullptr; e->tap_count = 0;
+    Owner& o = e->own;      // (the list before goes first: a refused or failing call leaves the handle without one)
+    (void)o.drop(&e->tap_mask); (void)o.drop(&e->tap_rank0); (void)o.drop(&e->tap_perm); (void)o.drop(&e->tap_ids); e->tap_count = 0;
     if (count == 0) return BBAI_OK;
     const int64_t nb = (e->n + STEP_BLOCK - 1) / STEP_BLOCK;
     std::vector<unsigned long long> mask((size_t)nb, 0ull);
@@ -1011,10 +1035,7 @@ int bbai_step_tap_set(bbai_env* e, const int64_t* ids, int64_t count) {
     for (int64_t k = 0; k < count; ++k) perm[(size_t)k] = order[(size_t)k].second;      // k-th listed env in ascending order -> its log row
     uint32_t run = 0;
     for (int64_t b = 0; b < nb; ++b) { rank0[(size_t)b] = run; run += (uint32_t)__builtin_popcountll(mask[(size_t)b]); }
-    HIP_TRY(hipMalloc((void**)&e->tap_mask, (size_t)nb * 8));
-    HIP_TRY(hipMalloc((void**)&e->tap_rank0, (size_t)nb * 4));
-    HIP_TRY(hipMalloc((void**)&e->tap_perm, (size_t)count * 4));
-    HIP_TRY(hipMalloc((void**)&e->tap_ids, (size_t)count * 8));
+    BBAI_TRY(o.alloc({{&e->tap_mask, (size_t)nb * 8}, {&e->tap_rank0, (size_t)nb * 4}, {&e->tap_perm, (size_t)count * 4}, {&e->tap_ids, (size_t)count * 8}}));
     HIP_TRY(hipMemcpy(e->tap_mask, mask.data(), (size_t)nb * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->tap_rank0, rank0.data(), (size_t)nb * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->tap_perm, perm.data(), (size_t)count * 4, hipMemcpyHostToDevice));
@@ -1050,8 +1071,8 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
 int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
     if (!e) ARG_FAIL("null handle");
     ON_DEVICE(e->device);
-    if (pixels && !e->rt_shadow) HIP_TRY(hipMalloc((void**)&e->rt_shadow, (size_t)e->n * CELLS));
-    if (pixels && !e->rt_dmask) HIP_TRY(hipMalloc((void**)&e->rt_dmask, (size_t)e->n * sizeof(uint64_t)));
+    // the first registration: the shadow and the dirty masks, both or neither (un-registering keeps them)
+    if (pixels && !e->rt_shadow) BBAI_TRY(e->own.alloc({{&e->rt_shadow, (size_t)e->n * CELLS}, {&e->rt_dmask, (size_t)e->n * sizeof(uint64_t)}}));
     e->rt_pixels = pixels;
     e->rt_valid = false; e->rt_filled = 0;
     return BBAI_OK;
@@ -1245,24 +1266,30 @@ int bbai_render(bbai_env* e, const uint8_t* image, uint8_t* pixels, void* stream
 // ---- the full-grid picture (k_render_grid) ----
 static int grid_ts_index(int ts) { return ts == 8 ? 0 : ts == 16 ? 1 : ts == 32 ? 2 : -1; }
 
+// One installer for the full-grid atlases and the view's (`who`: they differ in constants alone), into slot k of the handle's atlas / lookup table / tile count arrays.
+// The first installation at a tile size allocates both buffers or neither; a later one reuses them.  (The callers have checked the handle, the pointers and the tile size.)
+static int atlas_install(bbai_env* e, const char* who, uint8_t** atlas, uint8_t** lut_dev, int* installed, int k, int tile_size, int max_tiles, int lut_bytes,
+                         const uint8_t* tiles, int n_tiles, const uint8_t* lut) {
+    if (n_tiles < 1 || n_tiles > max_tiles) { snprintf(g_err, sizeof(g_err), "%s: %s", who, "tile count out of range"); return BBAI_ERR_ARG; }
+    for (int i = 0; i < lut_bytes; ++i)
+        if (lut[i] >= n_tiles) { snprintf(g_err, sizeof(g_err), "%s: %s", who, "a lut entry names a tile the atlas does not hold"); return BBAI_ERR_ARG; }
+    ON_DEVICE(e->device);
+    const size_t tb = (size_t)tile_size * tile_size * 3;
+    HIP_TRY(hipDeviceSynchronize());                 // (a render still in flight may read the atlas being replaced)
+    if (!atlas[k]) BBAI_TRY(e->own.alloc({{&atlas[k], (size_t)(max_tiles + 1) * tb}, {&lut_dev[k], (size_t)lut_bytes}}));
+    HIP_TRY(hipMemcpy(atlas[k], tiles, n_tiles * tb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(atlas[k] + n_tiles * tb, 0, tb));        // the zero tile: frames of ids (grid) / row ids (view) outside the batch
+    HIP_TRY(hipMemcpy(lut_dev[k], lut, (size_t)lut_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    installed[k] = n_tiles;
+    return BBAI_OK;
+}
+
 int bbai_set_grid_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_tiles, const uint8_t* lut) {
     const int k = grid_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
-    if (n_tiles < 1 || n_tiles > GRID_MAX_TILES) ARG_FAIL("tile count out of range");
-    for (int i = 0; i < GRID_LUT_BYTES; ++i)
-        if (lut[i] >= n_tiles) ARG_FAIL("a lut entry names a tile the atlas does not hold");
-    ON_DEVICE(e->device);
-    const size_t tb = (size_t)tile_size * tile_size * 3;
-    HIP_TRY(hipDeviceSynchronize());                 // (a render still in flight may read the atlas being replaced)
-    if (!e->grid_atlas[k]) HIP_TRY(hipMalloc((void**)&e->grid_atlas[k], (GRID_MAX_TILES + 1) * tb));
-    if (!e->grid_lut[k]) HIP_TRY(hipMalloc((void**)&e->grid_lut[k], GRID_LUT_BYTES));
-    HIP_TRY(hipMemcpy(e->grid_atlas[k], tiles, n_tiles * tb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(e->grid_atlas[k] + n_tiles * tb, 0, tb));        // the zero tile: frames of ids outside [0, n)
-    HIP_TRY(hipMemcpy(e->grid_lut[k], lut, GRID_LUT_BYTES, hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    e->grid_tiles[k] = n_tiles;
-    return BBAI_OK;
+    return atlas_install(e, __func__, e->grid_atlas, e->grid_lut, e->grid_tiles, k, tile_size, GRID_MAX_TILES, GRID_LUT_BYTES, tiles, n_tiles, lut);
 }
 
 }  // extern "C"
@@ -1326,20 +1353,7 @@ int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = view_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_set_atlas)");
-    if (n_tiles < 1 || n_tiles > VIEWPX_MAX_TILES) ARG_FAIL("tile count out of range");
-    for (int i = 0; i < VIEWPX_LUT_BYTES; ++i)
-        if (lut[i] >= n_tiles) ARG_FAIL("a lut entry names a tile the atlas does not hold");
-    ON_DEVICE(e->device);
-    const size_t tb = (size_t)tile_size * tile_size * 3;
-    HIP_TRY(hipDeviceSynchronize());                 // (a render still in flight may read the atlas being replaced)
-    if (!e->view_atlas[k]) HIP_TRY(hipMalloc((void**)&e->view_atlas[k], (VIEWPX_MAX_TILES + 1) * tb));
-    if (!e->view_lut[k]) HIP_TRY(hipMalloc((void**)&e->view_lut[k], VIEWPX_LUT_BYTES));
-    HIP_TRY(hipMemcpy(e->view_atlas[k], tiles, n_tiles * tb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(e->view_atlas[k] + n_tiles * tb, 0, tb));        // the zero tile: frames of row ids outside [0, rows)
-    HIP_TRY(hipMemcpy(e->view_lut[k], lut, VIEWPX_LUT_BYTES, hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    e->view_tiles[k] = n_tiles;
-    return BBAI_OK;
+    return atlas_install(e, __func__, e->view_atlas, e->view_lut, e->view_tiles, k, tile_size, VIEWPX_MAX_TILES, VIEWPX_LUT_BYTES, tiles, n_tiles, lut);
 }
 
 }  // extern "C"
@@ -1583,13 +1597,12 @@ int bbai_import_state(bbai_env* e, int64_t first, int64_t count, const uint8_t* 
     if (hot && count > 0) {
         // (the imported hot state keeps this env's place in ITS ring in both layouts: the ring belongs to the handle -- in-place, hot.slot
         // says where the live record is; classic, an exporter's slot may not even exist here: it comes from another ring depth)
-        Hot* staged = nullptr;
-        HIP_TRY(hipMalloc((void**)&staged, (size_t)count * sizeof(Hot)));
-        hipError_t r = hipMemcpy(staged, hot, (size_t)count * sizeof(Hot), hipMemcpyHostToDevice);
-        if (r == hipSuccess) { hipLaunchKernelGGL(k_import_hot, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, first, count, staged, e->hot); r = hipGetLastError(); }
-        if (r == hipSuccess) r = hipDeviceSynchronize();
-        (void)hipFree(staged);
-        HIP_TRY(r);
+        Scoped staged;
+        BBAI_TRY(staged.mem((size_t)count * sizeof(Hot)));
+        HIP_TRY(hipMemcpy(staged.h, hot, (size_t)count * sizeof(Hot), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_import_hot, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, first, count, (Hot*)staged.h, e->hot);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
     }
     if (stale) HIP_TRY(hipMemcpy(e->stale + first, stale, (size_t)count * 8, hipMemcpyHostToDevice));
     if (rec && count > 0) BBAI_TRY(live_copy(e, first, count, 1));
@@ -1712,25 +1725,12 @@ int bbai_checkpoint_load(bbai_env* e, const void* host_buf, int64_t bytes) {
         // The handle chose its look-ahead period from the memory that was free when it was created (bbai_create); the blob's
         // ring has the saving handle's.  The ring is part of the state: take the blob's shape.  The new ring is allocated BEFORE the
         // old one is let go, so that a failure leaves the handle as it was.
-        const size_t D = (size_t)h.depth, slot_bytes = (size_t)e->n * e->cfg.rec_bytes;
-        uint8_t* nrec = nullptr; Hot* nhot = nullptr; uint8_t* nobs = nullptr;
-        hipError_t r1 = hipMalloc((void**)&nrec, D * slot_bytes);
-        hipError_t r2 = r1 == hipSuccess ? hipMalloc((void**)&nhot, D * (size_t)e->n * sizeof(Hot)) : r1;
-        hipError_t r3 = r2;
-        if (r3 == hipSuccess && e->inplace) r3 = hipMalloc((void**)&nobs, D * (size_t)e->n * OBS_SLOT);
-        if (r3 != hipSuccess) {
-            (void)hipGetLastError();
-            if (nrec) (void)hipFree(nrec);
-            if (nhot) (void)hipFree(nhot);
-            if (nobs) (void)hipFree(nobs);
+        Ring r;
+        if (ring_alloc(e, h.depth, r) != BBAI_OK) {
             snprintf(g_err, sizeof(g_err), "checkpoint_load: no memory for the checkpoint's look-ahead ring (period %d); the handle is unchanged", h.period);
             return BBAI_ERR_NOMEM;
         }
-        (void)hipFree(e->next_rec); (void)hipFree(e->next_hot);
-        if (e->next_obs) (void)hipFree(e->next_obs);
-        e->next_rec = nrec; e->next_hot = nhot; e->next_obs = nobs;
-        e->period = h.period;
-        e->depth = h.depth;
+        ring_install(e, r, h.period);
     }
     const bool had_bot = e->bot_state != nullptr;
     if (!h.bot_stack && had_bot) {               // checkpoint without expert state: every env gets a fresh Bot
@@ -1762,24 +1762,23 @@ int bbai_get_programs(bbai_env* e, int64_t first, int64_t count, uint8_t* prog) 
     return BBAI_OK;
 }
 
-static int bot_alloc(bbai_env* e, int cap) {             // the expert's state: all three buffers or none
+static int bot_alloc(bbai_env* e, int cap) {             // the expert's state: all four buffers or none
     const int64_t threads = std::min<int64_t>((e->n + 63) / 64 * 64, 256 * 8 * 64);
-    void *st = nullptr, *wk = nullptr, *ss = nullptr, *rw = nullptr;
+    Scoped st, wk, rw, ss;
     const size_t sbytes = bot_state_bytes(cap);
-    hipError_t err = hipMalloc(&st, (size_t)e->n * sbytes);
-    if (err == hipSuccess) err = hipMalloc(&wk, (size_t)threads * BOT_WORK_WORDS * sizeof(uint16_t));
-    if (err == hipSuccess) err = hipMalloc(&rw, (size_t)threads * (R_ALL - R_FAST) * MAX_W * sizeof(uint32_t));
-    if (err == hipSuccess) err = hipMalloc(&ss, 16);
-    if (err == hipSuccess) err = hipMemset(st, 0, (size_t)e->n * sbytes);
-    if (err == hipSuccess) err = hipMemset(ss, 0, 16);
-    if (err != hipSuccess) {
-        (void)hipFree(st); (void)hipFree(wk); (void)hipFree(ss); (void)hipFree(rw);
-        snprintf(g_err, sizeof(g_err), "allocating the expert's state failed: %s", hipGetErrorString(err));
+    int rc = st.mem((size_t)e->n * sbytes);
+    if (rc == BBAI_OK) rc = wk.mem((size_t)threads * BOT_WORK_WORDS * sizeof(uint16_t));
+    if (rc == BBAI_OK) rc = rw.mem((size_t)threads * (R_ALL - R_FAST) * MAX_W * sizeof(uint32_t));
+    if (rc == BBAI_OK) rc = ss.mem(16);
+    if (rc == BBAI_OK) rc = res_done("hipMemset", hipMemset(st.h, 0, (size_t)e->n * sbytes));
+    if (rc == BBAI_OK) rc = res_done("hipMemset", hipMemset(ss.h, 0, 16));
+    if (rc != BBAI_OK) {
+        snprintf(g_err, sizeof(g_err), "allocating the expert's state failed: %s", hipGetErrorString(g_hip));
         return BBAI_ERR_NOMEM;
     }
     e->bot_stack = cap;
-    e->bot_state = (uint8_t*)st; e->bot_work = (uint16_t*)wk; e->bot_stats = (uint64_t*)ss; e->bot_threads = threads;
-    e->bot_rows = (uint32_t*)rw;
+    e->own.adopt(&e->bot_state, st); e->own.adopt(&e->bot_work, wk); e->own.adopt(&e->bot_stats, ss); e->bot_threads = threads;
+    e->own.adopt(&e->bot_rows, rw);
     { const char* ev = getenv("BBAI_BOT_EAGER"); e->bot_eager = ev ? atoi(ev) != 0 : 1; }
     return BBAI_OK;
 }
@@ -2086,8 +2085,8 @@ int bbai_set_done_actions(bbai_env* e, int enable) {
     if (!e) ARG_FAIL("null handle");
     ON_DEVICE(e->device);
     HIP_TRY(hipDeviceSynchronize());
-    if (enable && !e->lsm) HIP_TRY(hipMalloc((void**)&e->lsm, (size_t)e->n));
-    if (!enable && e->lsm) { HIP_TRY(hipFree(e->lsm)); e->lsm = nullptr; }
+    if (enable && !e->lsm) BBAI_TRY(e->own.alloc({{&e->lsm, (size_t)e->n}}));
+    if (!enable) BBAI_TRY(e->own.drop(&e->lsm));
     if (e->lsm) HIP_TRY(hipMemset(e->lsm, 0, (size_t)e->n));
     return BBAI_OK;
 }
@@ -2140,6 +2139,7 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     else if (!strcmp(name, "gate_fault")) *out = e->host_flags ? (int64_t)e->host_flags[0] : 0;     // sticky; no synchronisation
     else if (!strcmp(name, "profile_step_ticks")) *out = e->prof_step_ticks;
     else if (!strcmp(name, "cplane")) *out = e->cplane ? 1 : 0;
+    else if (!strcmp(name, "owned")) *out = (int64_t)e->own.held.size();      // device allocations, the pinned words, streams and events held right now
     else if (!strcmp(name, "gate_timeouts")) {      // (synchronises) window gates that gave up waiting for a refill: must be 0 (k_gate)
         ON_DEVICE(e->device);
         unsigned long long v = 0;
@@ -2252,19 +2252,18 @@ int bbai_load_state(bbai_env* e, const int64_t* ids, const int64_t* rows, int64_
 // After step 1 every closed window's refill has landed -- all their `pending` bytes are zero -- so the current window's buffer is the only one that can
 // hold a listed env, and k_reseed_seed clears it there.  k_reseed_consume then books the env's reset into that buffer like any finished env's.
 static int reseed_scratch(bbai_env* e) {
-    if (e->rs_claim) return BBAI_OK;          // (allocated last)
+    if (e->rs_claim) return BBAI_OK;          // (the group is committed as a whole: any of its fields says so)
     const size_t n = (size_t)e->n;
-    if (!e->ev_rs_call) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_call, hipEventDisableTiming));
-    if (!e->ev_rs_done) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_done, hipEventDisableTiming));
-    for (int k = 1; k < MAX_SIDES; ++k) if (!e->ev_rs_part[k]) HIP_TRY(hipEventCreateWithFlags(&e->ev_rs_part[k], hipEventDisableTiming));
-    if (!e->rs_list) HIP_TRY(hipMalloc((void**)&e->rs_list, (size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4));
-    if (!e->rs_count) HIP_TRY(hipMalloc((void**)&e->rs_count, SHARDS * GEN_COUNT_U32 * 4));
-    if (!e->rs_pending) { HIP_TRY(hipMalloc((void**)&e->rs_pending, n)); HIP_TRY(hipMemset(e->rs_pending, 0, n)); }
-    if (!e->rs_first) { HIP_TRY(hipMalloc((void**)&e->rs_first, n)); HIP_TRY(hipMemset(e->rs_first, 0, n)); }
-    uint32_t* claim = nullptr;
-    HIP_TRY(hipMalloc((void**)&claim, (n + 31) / 32 * 4));
-    if (hipMemset(claim, 0, (n + 31) / 32 * 4) != hipSuccess) { (void)hipFree(claim); snprintf(g_err, sizeof(g_err), "reseed: hipMemset failed"); return BBAI_ERR_HIP; }
-    e->rs_claim = claim;
+    Scoped call, done, part[MAX_SIDES], list, count, pending, first, claim;
+    BBAI_TRY(call.event()); BBAI_TRY(done.event());
+    for (int k = 1; k < MAX_SIDES; ++k) BBAI_TRY(part[k].event());
+    BBAI_TRY(list.mem((size_t)SHARDS * (size_t)gen_sublist_cap(e->n) * 4)); BBAI_TRY(count.mem(SHARDS * GEN_COUNT_U32 * 4));
+    BBAI_TRY(pending.mem(n, true)); BBAI_TRY(first.mem(n, true));
+    BBAI_TRY(claim.mem((n + 31) / 32 * 4));
+    if (hipMemset(claim.h, 0, (n + 31) / 32 * 4) != hipSuccess) { snprintf(g_err, sizeof(g_err), "reseed: hipMemset failed"); return BBAI_ERR_HIP; }
+    Owner& o = e->own;
+    for (int k = 1; k < MAX_SIDES; ++k) o.adopt(&e->ev_rs_part[k], part[k]);
+    o.adopt(&e->ev_rs_call, call); o.adopt(&e->ev_rs_done, done); o.adopt(&e->rs_list, list); o.adopt(&e->rs_count, count); o.adopt(&e->rs_pending, pending); o.adopt(&e->rs_first, first); o.adopt(&e->rs_claim, claim);
     return BBAI_OK;
 }
 

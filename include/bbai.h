@@ -488,7 +488,9 @@ int bbai_set_option(bbai_env* env, const char* name, int64_t value);
  * look-ahead refill after ~10 s -- must be 0; anything else means a refill was lost and the batch's results are void), or
  * "gate_fault" (the same fact as a sticky flag in pinned host memory, read without synchronising: once it is set EVERY stepping /
  * resetting entry point of the handle returns BBAI_ERR_STATE before it enqueues anything, until bbai_seed regenerates the ring),
- * or "gate_forced_strict" (1: the caller's stream failed the concurrency probe and runs under the strict rule). */
+ * or "gate_forced_strict" (1: the caller's stream failed the concurrency probe and runs under the strict rule), or "owned" (how many
+ * resources the handle holds right now -- device allocations, its pinned host words, streams and events: what bbai_destroy releases;
+ * features that allocate on first use add to it once, not per call). */
 int bbai_get_option(bbai_env* env, const char* name, int64_t* out);
 
 /* Number of level generations (resets) performed so far, all envs. */
