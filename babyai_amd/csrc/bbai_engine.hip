@@ -1589,6 +1589,8 @@ static int sync_view(bbai_env* e, int64_t first, int64_t count) {
     return BBAI_OK;
 }
 
+static int import_tokens(bbai_env* e, int64_t first, int64_t count);      // (behind bbai_reseed: it launches k_state_tokens, whose code keeps its place)
+
 int bbai_import_state(bbai_env* e, int64_t first, int64_t count, const uint8_t* rec, const uint8_t* hot, const uint64_t* stale) {
     if (!e || first < 0 || count < 0 || first + count > e->n) ARG_FAIL("null handle or env range out of bounds");
     ON_DEVICE(e->device);
@@ -1616,6 +1618,16 @@ int bbai_import_state(bbai_env* e, int64_t first, int64_t count, const uint8_t* 
     // (a hot / stale-only import: the C plane rows are rebuilt from the staging records, which must then hold the LIVE ones)
     if (!rec && e->cplane && count > 0) BBAI_TRY(live_copy(e, first, count, 0));
     if (count > 0) BBAI_TRY(sync_view(e, first, count));
+    if (rec && count > 0) {
+        // the expert's plan is not part of an exported state: 0 is no step a plan can expect (k_bot starts a fresh Bot at step 0 anyway), so the
+        // env's next decision starts one (k_state_load's rule: BotState::next_step of the range, one strided memset)
+        if (e->bot_state) {
+            const size_t sbytes = bot_state_bytes(e->bot_stack);
+            HIP_TRY(hipMemset2D(e->bot_state + (size_t)first * sbytes + offsetof(BotState, next_step), sbytes, 0, sizeof(uint16_t), (size_t)count));
+            HIP_TRY(hipDeviceSynchronize());          // (the import is synchronous: the next bbai_bot_act may come on any stream)
+        }
+        if (e->tokens) BBAI_TRY(import_tokens(e, first, count));      // (behind the live records and hot states: the sentence k_state_tokens writes)
+    }
     e->live = true;
     return BBAI_OK;
 }
@@ -2308,6 +2320,22 @@ int bbai_reseed(bbai_env* e, const int64_t* ids, const uint64_t* seeds, int64_t 
     HIP_TRY(hipGetLastError());
     e->live = true;
     return call.leave();
+}
+
+// bbai_import_state's token rows: the registered rows of envs [first, first + count) from their live records, by k_state_tokens over a device id
+// list of the range.  Synchronous, like the import; it stands here and not next to its caller so that k_state_tokens' first launch stays
+// bbai_load_state's (bbai_statek.hpp: a template's code is emitted where it is first launched).
+static int import_tokens(bbai_env* e, int64_t first, int64_t count) {
+    std::vector<int64_t> ids((size_t)count);
+    for (int64_t k = 0; k < count; ++k) ids[(size_t)k] = first + k;
+    Scoped list;
+    BBAI_TRY(list.mem((size_t)count * sizeof(int64_t)));
+    HIP_TRY(hipMemcpy(list.h, ids.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_state_tokens<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 4096)), dim3(64), 0, 0, e->cfg, e->n, (const int64_t*)list.h,
+                       (const int64_t*)nullptr, count, count, e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, e->tokens);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return BBAI_OK;
 }
 
 }  // extern "C"

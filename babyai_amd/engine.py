@@ -697,6 +697,9 @@ class BatchedBabyAIEnv(object):
         return np.stack([e & 7, (e >> 3) & 7, e >> 6], axis=-1).astype(np.uint8), hot[:, :3].astype(np.int64)
 
     def import_state(self, rec, hot, stale, first=0):
+        """export_state()'s arrays into envs first .. first + len(rec) - 1 (include/bbai.h bbai_import_state; synchronous).  As after
+        load_state the imported envs' next bot_actions() starts a fresh Bot and their `instr` rows hold the imported missions; unlike it, no
+        observation is written: image / direction / pixels are stale until the next step."""
         rec = np.ascontiguousarray(rec, dtype=np.uint8)
         hot = np.ascontiguousarray(hot, dtype=np.uint8)
         stale = np.ascontiguousarray(stale, dtype=np.uint64)

@@ -189,7 +189,14 @@ int bbai_set_token_buffer(bbai_env* env, uint8_t* tokens_dev);
 
 /* State access (host buffers; synchronous): parity tests, checkpoints, mission strings.  hot_host[15] is the env's place in its
  * look-ahead ring: engine bookkeeping of the EXPORTING handle -- bbai_import_state ignores it and keeps the importing handle's own
- * (the ring belongs to the handle; in the in-place layout the slot says where the live record is). */
+ * (the ring belongs to the handle; in the in-place layout the slot says where the live record is).
+ * All three take the env range [first, first + count): BBAI_ERR_ARG for a negative first or count or first + count > n_envs; count == 0
+ * is a no-op.  bbai_import_state with records (rec_host != NULL) puts the range's envs into the given states like bbai_load_state: where
+ * the expert's state is allocated each env's next bbai_bot_act starts a fresh Bot, a registered token buffer gets the imported missions'
+ * tokens in the range's rows, and the lastStepMatch bytes are cleared (they are no part of the exported state); every env keeps its own
+ * look-ahead ring and RNG stream, so it goes on with its OWN next level when the imported episode ends.  Unlike bbai_load_state it writes
+ * NO observation: the caller's image / direction buffers (and a render target) are stale until the next step or an explicit observe.
+ * A hot- or stale-only import (rec_host == NULL: poses of the records the envs hold) changes neither the expert's plans nor token rows. */
 int bbai_export_state(bbai_env* env, int64_t first, int64_t count, uint8_t* rec_host,
                       uint8_t* hot_host /* 16 B each */, uint64_t* stale_host);
 int bbai_import_state(bbai_env* env, int64_t first, int64_t count, const uint8_t* rec_host,
@@ -265,7 +272,8 @@ int bbai_checkpoint_load(bbai_env* env, const void* host_buf, int64_t bytes);
  * have raised (assertion / DisappearedBoxError / endless replanning); it stays 255 until the episode ends.
  * Decision-for-decision parity with the reference bot: tests/test_hostsim_bot.py, tests/golden/bot/.
  * The expert's plan lives in the handle (allocated on first use, ~1.7 KB per env) and is not part of
- * bbai_export_state / bbai_import_state: import states at episode boundaries when the expert is in use. */
+ * bbai_export_state / bbai_import_state: an env that gets a record through bbai_import_state, bbai_load_state or bbai_reseed starts a
+ * fresh Bot at its next decision, wherever in its episode the state is. */
 int bbai_bot_act(bbai_env* env, const uint8_t* prev_actions_dev, uint8_t* actions_dev, void* stream);
 /* The inner loop of expert-driven demonstration generation (scripts/make_agent_demos.py:71-137 generate_demos with
  * BotAgent, babyai/utils/agent.py:139-155) for every env, T steps per call with NO host round trip between the steps:

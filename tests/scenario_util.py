@@ -8,11 +8,14 @@ A script is a list of events:
     ("reset",)                             reset() of the whole batch: every env's next level
     ("save", ids)                          snapshot of the listed envs; its index = the number of saves before it
     ("load", snap_index, ids, rows)        snapshot rows `rows` into envs `ids`
+    ("import", donor_rows, first)          bbai_import_state: donor_rows = {"rec" uint8[count, rec_bytes] or None, "hot" uint8[count, 16] or None,
+                                           "stale" uint64[count] or None} (export_state's arrays) into envs first .. first + count - 1
 
 What a run returns (model: numpy; device: numpy after one copy at the end), `n` envs wide, never only the listed ones:
     "steps"   image [T, n, 7, 7, 3], direction [T, n], reward64 [T, n], reward [T, n], done [T, n], tokens [T, n, 72] after every step
     "bot"     image / direction / tokens the expert decided on, action, gave_up, reward, done, per bbai_bot_rollout step
     "calls"   per reseed / load / reset: image [n, 7, 7, 3], direction [n], tokens [n, 72] as the call leaves them
+    "imports" per import: tokens [n, 72] as the call leaves them (an import writes no observation)
     "snaps"   per save: rec, hot, stale rows
     "starts"  episode starts: the reset, every reseeded env, every finished env of an auto-resetting step (bbai_reset_count)
 
@@ -41,11 +44,11 @@ DEAD_CAPACITY = 2          # babyai_amd/csrc/bbai_bot.hpp: a fixed-size structur
 class ScenarioModel(object):
     """n envs of the host build behind reset(), with the two calls modelled on HostBatch's arrays."""
 
-    def __init__(self, level, seeds, auto_reset=True):
+    def __init__(self, level, seeds, auto_reset=True, done_actions=False, enum_done=False):
         self.level, self.cfg = level, make_cfg(level)
         self.L = lib()
         self.auto_reset = bool(auto_reset)
-        self.hb = HostBatch(self.cfg, seeds, auto_reset=auto_reset)
+        self.hb = HostBatch(self.cfg, seeds, auto_reset=auto_reset, done_actions=done_actions, enum_done=enum_done)
         self.n = self.hb.n
         self.hb.reset()
         self.starts = self.n
@@ -53,7 +56,30 @@ class ScenarioModel(object):
         self._tok = {}
         self._bot_states = None
         self._bot_fresh = np.ones(self.n, bool)
+        self._own14 = {}            # env -> its level stream's own Hot.last_locked byte while its hot state shows a loaded row's (_take_hot)
         self.bot_stats = {"gave_up": 0, "capacity": 0}
+
+    # Hot byte 14 (last_locked: LevelGen.locked_room, which survives episodes and feeds the next level's rand_obj) is state of the env's LEVEL
+    # STREAM, like mt / mti: the engine generates from the ring's previous entry, never from the live hot state, so a loaded or imported env
+    # goes on with its own.  Its live hot state SHOWS the loaded row's byte until the env's next episode starts, and so does hb.hot here; the
+    # host build generates from hb.hot[i, 14] in place, so the env's own byte is kept apart and put back around everything that may generate.
+    def _take_hot(self, i, row):
+        self._own14.setdefault(i, self.hb.hot[i, 14])
+        self.hb.hot[i, :15] = row[:15]          # (byte 15: the env's place in its own ring; mt / mti stay: its own next level)
+
+    def _own_streams(self):
+        """Before a call that may generate: every env's own byte 14 back in place.  -> what the hot states showed, for _shown_again."""
+        shown = {i: self.hb.hot[i, 14] for i in self._own14}
+        for i, b in self._own14.items():
+            self.hb.hot[i, 14] = b
+        return shown
+
+    def _shown_again(self, shown, started):
+        for i, b in shown.items():
+            if started[i]:
+                del self._own14[i]              # (the new episode's hot state came from the env's own stream)
+            else:
+                self.hb.hot[i, 14] = b
 
     # -- the calls
     def reseed(self, ids, seeds):
@@ -67,10 +93,12 @@ class ScenarioModel(object):
             for k in ("mt", "mti", "rec", "hot", "stale", "image", "direction"):
                 getattr(hb, k)[i] = getattr(one, k)[0]
             hb.hot[i, 13] = 0           # (frozen)
+            self._own14.pop(i, None)
             self._bot_fresh[i] = True
             self.starts += 1
 
     def reset(self):
+        self._shown_again(self._own_streams(), np.ones(self.n, bool))
         self.hb.reset()
         self._bot_fresh[:] = True
         self.starts += self.n
@@ -91,18 +119,41 @@ class ScenarioModel(object):
             if not (0 <= i < self.n and 0 <= r < len(snap["stale"])):
                 continue
             hb.rec[i], hb.stale[i] = snap["rec"][r], snap["stale"][r]
-            hb.hot[i, :15] = snap["hot"][r, :15]          # (byte 15: the env's place in its own ring; mt / mti stay: its own next level)
+            self._take_hot(i, snap["hot"][r])
             self.L.hs_observe(ctypes.byref(self.cfg), hb.rec[i].ctypes.data, hb.hot[i].ctypes.data, hb.image[i].ctypes.data)
             hb.direction[i] = hb.hot[i, 2]
             self._bot_fresh[i] = True
+
+    def import_state(self, rows, first):
+        """bbai_import_state(first, count, rec, hot, stale): load() on ids first .. first + count - 1 without the observation -- image and
+        direction keep what the last step wrote.  With records the env's next expert decision starts a fresh Bot and its token row follows
+        (tokens() reads the records); a hot- / stale-only import (rec None) moves neither.  Every import clears the done-action byte
+        (lastStepMatch is no part of the exported state); the env keeps mt / mti: its own level stream."""
+        hb = self.hb
+        rec, hot, stale = rows.get("rec"), rows.get("hot"), rows.get("stale")
+        count = len(next(x for x in (rec, hot, stale) if x is not None))
+        assert first >= 0 and first + count <= self.n and all(x is None or len(x) == count for x in (rec, hot, stale))
+        for k in range(count):
+            i = first + k
+            if rec is not None:
+                hb.rec[i] = rec[k]
+                self._bot_fresh[i] = True
+            if hot is not None:
+                self._take_hot(i, hot[k])
+            if stale is not None:
+                hb.stale[i] = stale[k]
+            if hb.lsm is not None:
+                hb.lsm[i] = 0
 
     # -- the steps
     def step(self, actions):
         hb = self.hb
         live = hb.hot[:, 13] == 0
+        shown = self._own_streams()
         hb.step(actions)
-        if self.auto_reset:
-            self.starts += int((live & (hb.done != 0)).sum())
+        started = live & (hb.done != 0) & self.auto_reset
+        self._shown_again(shown, started)
+        self.starts += int(started.sum())
 
     def tokens(self):
         """The mission token rows uint8[n, 72] of the current records (missions.tokenize of prog_surface)."""
@@ -152,7 +203,7 @@ class ScenarioModel(object):
         hb = self.hb
         steps = {k: [] for k in OUT_KEYS + ("tokens",)}
         bot = {k: [] for k in BOT_KEYS}
-        calls, log = [], []
+        calls, imports, log = [], [], []
         reset = {"image": hb.image.copy(), "direction": hb.direction.copy(), "tokens": self.tokens()}
 
         def emit():
@@ -189,6 +240,11 @@ class ScenarioModel(object):
                 log.append({"kind": "load", "at": at, "ids": [i for i, _ in ok], "rows": [r for _, r in ok], "step_count": hot[:, 4] | hot[:, 5] << 8,
                             "max_steps": hot[:, 6] | hot[:, 7] << 8, "frozen": hot[:, 13]})
                 self.load(snap, ev[2], ev[3])
+            elif ev[0] == "import":
+                self.import_state(ev[1], ev[2])
+                count = len(next(x for x in ev[1].values() if x is not None))
+                log.append({"kind": "import", "at": at, "ids": list(range(ev[2], ev[2] + count)), "rec": ev[1].get("rec") is not None})
+                imports.append({"tokens": self.tokens()})
             else:
                 raise ValueError(ev[0])
             if ev[0] in ("reseed", "load", "reset"):
@@ -196,7 +252,7 @@ class ScenarioModel(object):
         T = len(steps["done"])
         shapes = {"image": (0, self.n, 7, 7, 3), "tokens": (0, self.n, TOK_MAX)}
         stack = lambda d: {k: np.stack(v) if v else np.zeros(shapes.get(k, (0, self.n)), np.uint8) for k, v in d.items()}
-        return {"steps": stack(steps), "bot": stack(bot), "calls": calls, "snaps": self.snaps, "starts": self.starts, "log": log, "reset": reset, "T": T,
+        return {"steps": stack(steps), "bot": stack(bot), "calls": calls, "imports": imports, "snaps": self.snaps, "starts": self.starts, "log": log, "reset": reset, "T": T,
                 "bot_stats": dict(self.bot_stats)}
 
 
@@ -365,6 +421,19 @@ def _abi_load(env, snap, ids, rows):
                                              snap.lsm.data_ptr(), env.image.data_ptr(), env.direction.data_ptr(), env._stream()), "bbai_load_state")
 
 
+def abi_import(env, rows, first):
+    """bbai_import_state through the library handle: env.import_state() takes all three arrays, the entry point takes NULL for any of them
+    (rec NULL = a hot- / stale-only import).  The host arrays are read before the call returns."""
+    from babyai_amd.engine import _check
+    rec, hot, stale = rows.get("rec"), rows.get("hot"), rows.get("stale")
+    count = len(next(x for x in (rec, hot, stale) if x is not None))
+    rec = None if rec is None else np.ascontiguousarray(rec, dtype=np.uint8).reshape(count, env.cfg.rec_bytes)
+    hot = None if hot is None else np.ascontiguousarray(hot, dtype=np.uint8).reshape(count, 16)
+    stale = None if stale is None else np.ascontiguousarray(stale, dtype=np.uint64).reshape(count)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(env.lib, env.lib.bbai_import_state(env.handle, int(first), count, ptr(rec), ptr(hot), ptr(stale)), "bbai_import_state")
+
+
 def run_device(env, events, entry, tap_ids=None, after=None):
     """The script on `env` (reset() behind it already) under step entry `entry`; the model's arrays back, as numpy.  `after(kind, index)` is called
     behind every step ("step", step index) and call ("call", call index) of the per-step entries, for checks of buffers the result does not carry
@@ -378,7 +447,7 @@ def run_device(env, events, entry, tap_ids=None, after=None):
     steps = {k: [] for k in keys + (("tokens",) if tokens_on else ())}
     bot = {k: [] for k in BOT_KEYS}
     tapped = {k: [] for k in ("image", "direction", "reward64", "done")}
-    calls, snaps, finals = [], [], {}
+    calls, imports, snaps, finals = [], [], [], {}
     count = 0
 
     def emit():
@@ -440,6 +509,11 @@ def run_device(env, events, entry, tap_ids=None, after=None):
             count += ev[1]
         elif ev[0] == "save":
             snaps.append(env.save_state(ev[1]))
+        elif ev[0] == "import":
+            abi_import(env, ev[1], ev[2])
+            imports.append({"tokens": env.instr.clone() if tokens_on else None})
+            if after:
+                after("import", len(imports) - 1)
         else:
             if ev[0] == "reseed":
                 ids = None if ev[1] is None else np.asarray(ev[1], np.int64)
@@ -461,6 +535,7 @@ def run_device(env, events, entry, tap_ids=None, after=None):
     torch.cuda.current_stream(dev).synchronize()
     cpu = lambda t: None if t is None else t.cpu().numpy()
     out = {"steps": {k: [cpu(x) for x in v] for k, v in steps.items()}, "calls": [{k: cpu(v) for k, v in c.items()} for c in calls],
+           "imports": [{k: cpu(v) for k, v in c.items()} for c in imports],
            "bot": {k: np.concatenate([cpu(x) for x in v]) if v else None for k, v in bot.items()},
            "snaps": [{"rec": cpu(s.rec), "hot": cpu(s.hot), "stale": cpu(s.stale).view(np.uint64)} for s in snaps],
            "finals": {t: {k: cpu(v) for k, v in f.items()} for t, f in finals.items()}, "tapped": {k: [cpu(x) for x in v] for k, v in tapped.items()}, "T": count}
@@ -498,6 +573,10 @@ def assert_equals_model(got, want, tap_ids=None):
         for k in ("image", "direction", "tokens"):
             if c[k] is not None:
                 _same("call %d %s" % (j, k), c[k], w[k])
+    assert len(got.get("imports", ())) == len(want.get("imports", ()))
+    for j, (c, w) in enumerate(zip(got.get("imports", ()), want.get("imports", ()))):
+        if c["tokens"] is not None:
+            _same("import %d tokens" % j, c["tokens"], w["tokens"])
     assert len(got["snaps"]) == len(want["snaps"])
     for j, (s, w) in enumerate(zip(got["snaps"], want["snaps"])):
         _same("snapshot %d rec" % j, s["rec"], w["rec"])

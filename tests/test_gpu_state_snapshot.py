@@ -288,6 +288,8 @@ def test_every_observation_kind_follows_a_load(gpu, level, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("level,inplace", [("GoToLocal", "0"), ("GoToLocal", "1"), ("BossLevel", "0")])
 def test_token_rows_and_a_fresh_expert(gpu, monkeypatch, level, inplace):
+    """The expected decisions come from a host import into a handle that never consulted the expert; what an import does to a handle that did
+    is tests/test_gpu_state_ranges.py::test_an_import_starts_a_fresh_expert's."""
     import torch
     monkeypatch.setenv("BBAI_INPLACE", inplace)
     src = _make(level, N, gpu, 100)

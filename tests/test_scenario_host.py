@@ -178,6 +178,175 @@ def test_the_expert_model_is_host_bot_on_host_env():
     assert episodes >= 3 * n
 
 
+def _host_envs(level, seeds, pre):
+    """One HostEnv per seed behind reset() and the steps pre[T, n] (auto-resetting, actions 0 .. 6): per-env objects that share no batch code
+    with ScenarioModel."""
+    cfg = make_cfg(level)
+    envs = [HostEnv(cfg, int(s)) for s in seeds]
+    for e in envs:
+        e.reset()
+    for t in range(len(pre)):
+        for i, e in enumerate(envs):
+            if e.step(int(pre[t, i]))[2]:
+                e.reset()
+    return envs
+
+
+@pytest.mark.parametrize("with_rec", [True, False], ids=["records", "hot-only"])
+@pytest.mark.parametrize("level", LEVELS)
+def test_an_imported_range_continues_as_the_donor_rows_and_keeps_its_own_next_levels(level, with_rec):
+    """The ("import", rows, first) event against per-env HostEnv objects: env first + k of the recipient gets donor row k's record, hot bytes
+    0 .. 14 and stale set written into ITS object -- which keeps its own MT19937 stream --, is stepped on, and restarts through its own reset().
+    With records: a donor row twice; the model's image / direction are what the last step wrote until the next step; the expert starts a fresh
+    Bot on the imported rows, and only there.  Hot-only: the range's own poses with the direction turned -- valid for the records they stay
+    with, since every direction is valid wherever the agent stands --, the expert's plans and the token rows untouched."""
+    from hostsim_util import HostBot
+    n, first, count = 24, 5, 9
+    base_r, base_d = 7800, 8800
+    pre_r, pre_d = _acts(12, n, 31, 0.0), _acts(12, n, 32, 0.0)
+    a, c = (su.ScenarioModel(level, np.arange(n) + base_r) for _ in range(2))
+    d = su.ScenarioModel(level, np.arange(n) + base_d)
+    for t in range(12):
+        a.step(pre_r[t]); c.step(pre_r[t]); d.step(pre_d[t])
+    envs = _host_envs(level, np.arange(n) + base_r, pre_r)
+    for i, e in enumerate(envs):
+        assert np.array_equal(e.rec, a.hb.rec[i]) and np.array_equal(e.hot[:15], a.hb.hot[i, :15]) and e.stale.value == a.hb.stale[i]
+    a.bot_decide(); c.bot_decide()                      # every env has a plan now (no env is fresh any more)
+    assert not a._bot_fresh.any()
+    if with_rec:
+        src = np.array([3, 3, 0, 23, 11, 12, 13, 20, 7], dtype=np.int64)          # donor row 3 twice
+        rows = {"rec": d.hb.rec[src].copy(), "hot": d.hb.hot[src].copy(), "stale": d.hb.stale[src].copy()}
+        rows["hot"][:, 15] = 0xEE                        # (the exporter's ring slot: ignored)
+    else:
+        hot = a.hb.hot[first:first + count].copy()
+        hot[:, 2] = (hot[:, 2] + 1 + np.arange(count) % 3) % 4
+        rows = {"rec": None, "hot": hot, "stale": None}
+    before = {k: getattr(a.hb, k).copy() for k in ("image", "direction", "mt", "mti", "rec", "hot", "stale")}
+    tok0, starts0 = a.tokens(), a.starts
+    a.import_state(rows, first)
+    rng_ = np.arange(first, first + count)
+    out = np.setdiff1d(np.arange(n), rng_)
+    for k in ("image", "direction", "mt", "mti"):           # no observation is written; the level streams stay
+        assert np.array_equal(getattr(a.hb, k), before[k]), k
+    for k in ("rec", "hot", "stale"):
+        assert np.array_equal(getattr(a.hb, k)[out], before[k][out]), k
+    assert np.array_equal(a.hb.hot[:, 15], before["hot"][:, 15]) and a.starts == starts0
+    assert np.array_equal(a._bot_fresh, np.isin(np.arange(n), rng_) & with_rec)
+    if with_rec:
+        assert np.array_equal(a.tokens()[rng_], d.tokens()[src]) and np.array_equal(a.tokens()[out], tok0[out])
+        assert (a.tokens()[rng_] != tok0[rng_]).any()
+    else:
+        assert np.array_equal(a.tokens(), tok0) and np.array_equal(a.hb.rec, before["rec"])
+    for k, i in enumerate(rng_):                          # the same bytes into the per-env objects
+        if with_rec:
+            envs[i].rec[:] = rows["rec"][k]
+            envs[i].stale.value = int(rows["stale"][k])
+        envs[i].hot[:14] = rows["hot"][k, :14]          # (byte 14, LevelGen.locked_room, belongs to the env's own level stream)
+    # the expert: a fresh Bot on the imported rows (HostBot on the per-env object), the old plan's next decision elsewhere
+    act, gave = a.bot_decide()
+    act_c, _ = c.bot_decide()
+    assert np.array_equal(act[out], act_c[out])
+    if with_rec:
+        for i in rng_:
+            want = HostBot(envs[i]).decide(True)
+            assert (RESET_ENV if want is None else want) == act[i] and bool(gave[i]) == (want is None), i
+    acts = _acts(150, n, 33, 0.0)
+    ends = np.zeros(n, int)
+    for t in range(150):
+        a.step(acts[t]); c.step(acts[t])
+        for i, e in enumerate(envs):
+            img, rew, done = e.step(int(acts[t, i]))
+            assert bool(a.hb.done[i]) == done and a.hb.reward64[i:i + 1].view(np.uint64)[0] == np.float64(e.last_reward64).reshape(1).view(np.uint64)[0], (level, t, i)
+            if done:
+                img = e.reset()                          # ... its OWN next level
+                ends[i] += 1
+            assert np.array_equal(a.hb.image[i], img) and a.hb.direction[i] == e.agent[2], (level, t, i)
+        for k in su.OUT_KEYS:
+            assert np.array_equal(su._bits(getattr(a.hb, k)[out]), su._bits(getattr(c.hb, k)[out])), (level, t, k)
+    if level == "GoToLocal":
+        assert ends[rng_].min() >= 2, ends          # (64 steps at most per episode: two own levels behind the imported one)
+    assert a.starts - starts0 == int(ends.sum())
+
+
+def test_an_import_clears_the_done_action_byte():
+    """Done-action mode: the model's lastStepMatch word of every imported env is cleared, also by a hot-only import, and nowhere else."""
+    n = 16
+    a = su.ScenarioModel("GoToLocal", np.arange(n) + 7950, done_actions=True)
+    a.hb.lsm[:] = 1
+    a.import_state({"rec": a.hb.rec[2:5].copy(), "hot": a.hb.hot[2:5].copy(), "stale": a.hb.stale[2:5].copy()}, 2)
+    a.import_state({"rec": None, "hot": a.hb.hot[9:10].copy(), "stale": None}, 9)
+    assert a.hb.lsm.tolist() == [int(i not in (2, 3, 4, 9)) for i in range(n)]
+
+
+# ---- what the scripts of tests/test_gpu_state_ranges.py reach (tests/state_ranges_util.py, the model alone) ---------------------------------
+def test_range_import_scripts_reach_the_recipients_own_next_levels():
+    """Every case of test_range_import_steps_as_the_host_model: the import stands in front of the window position the case names, all four
+    positions occur in every layout, and at least a quarter of the imported envs start a new episode -- of their OWN stream -- in the 30
+    steps behind it.  A random walk does not finish a GoToLocal episode that soon (the donor rows are 20 steps into 64), so the reset command
+    comes at scenario_util's rate on every level here."""
+    import state_ranges_util as sr
+    import test_gpu_state_ranges as tr
+    assert len(tr.CASES2) == len(tr.IDS2) == len(set(tr.IDS2)) == 10 * len(sr.RANGES) + 4
+    positions = {}
+    for level, ev, ev_src, done_actions, first, count, pos, repeat in tr.CASES2:
+        run = sr.import_run(level, first, count, pos, done_actions, False, repeat)
+        log = [e for e in run["model"]["log"] if e["kind"] == "import"]
+        assert len(log) == 1 and (log[0]["at"] + 1) % su.B == pos and log[0]["ids"] == list(range(first, first + count))
+        assert run["model"]["T"] - log[0]["at"] == sr.AFTER
+        assert int(run["restarted"].sum()) * 4 >= count, (level, first, count, int(run["restarted"].sum()))
+        assert len(set(run["src"].tolist())) == count - (6 if repeat else 0)
+        positions.setdefault((level, tuple(sorted(ev.items())), done_actions), set()).add(pos)
+    assert all(p == set(range(su.B)) for p in positions.values())
+    assert {(tuple(ev.items()), tuple(es.items())) for _, ev, es, _, _, _, _, _ in tr.CASES2 if ev != es} == \
+        {((("BBAI_INPLACE", "1"),), (("BBAI_INPLACE", "0"),)), ((("BBAI_INPLACE", "0"),), (("BBAI_INPLACE", "1"),))}
+
+
+def test_expert_import_case_has_colliding_pairs():
+    """test_an_import_starts_a_fresh_expert: 33 of the 37 (row, env) pairs collide -- the row's Hot.step is the 10 the env's own plan expects
+    and the env's own episode has not ended --, so a plan that survived the import would be continued; at least 8 are required.  The fresh
+    decisions differ from the continued plans' somewhere, and the model's fresh decisions are HostBot's on the rows."""
+    import state_ranges_util as sr
+    from hostsim_util import HostBot
+    case = sr.expert_case()
+    assert int(case["colliding"].sum()) == 33 and int(case["colliding"].sum()) >= 8
+    cfg = make_cfg(sr.BOT_LEVEL)
+    for k in range(sr.BOT_COUNT):
+        e = HostEnv(cfg, 0)
+        e.rec[:], e.hot[:] = case["rows"]["rec"][k], case["rows"]["hot"][k]
+        e.stale.value = int(case["rows"]["stale"][k])
+        d = HostBot(e).decide(True)
+        assert (255 if d is None else d) == case["want"][sr.BOT_FIRST + k], k
+    out = np.setdiff1d(np.arange(sr.N), np.arange(sr.BOT_FIRST, sr.BOT_FIRST + sr.BOT_COUNT))
+    assert np.array_equal(case["want"][out], case["want_twin"][out])
+    assert (case["want"] != case["want_twin"]).any()
+
+
+def test_done_action_import_case_meets_envs_in_front_of_their_target():
+    import state_ranges_util as sr
+    case = sr.done_case()
+    m, pre = case["model"]["steps"], case["pre"]
+    matched = sr.DONE_FIRST + np.nonzero(case["is_matched"])[0]
+    assert len(matched) >= 1 and len(case["donor_acts"]) >= 20 and (case["donor_paid"] > 0).all()
+    assert not m["reward64"][pre][matched].any() and m["done"][pre][sr.DONE_FIRST:sr.DONE_FIRST + sr.DONE_COUNT].all()
+    assert (m["reward64"][pre + 1:] > 0).any()          # (later `done` actions do succeed: the mode is on)
+
+
+@pytest.mark.parametrize("level", ["GoToLocal", "BossLevel"])
+def test_pose_import_script_turns_agents_that_then_move(level):
+    """The three imports without records stand in front of window positions 1, 3 and 0, and the turned agents' next steps differ from those of a
+    run without the imports (the poses matter)."""
+    import state_ranges_util as sr
+    run = sr.pose_run(level)
+    log = [e for e in run["model"]["log"] if e["kind"] == "import"]
+    assert [(e["at"] + 1) % su.B for e in log] == [1, 3, 0] and not any(e["rec"] for e in log)
+    assert [len(e["ids"]) for e in log] == [sr.POSE_COUNT, sr.N, 64]
+    plain = su.ScenarioModel(level, sr.seeds(sr.RECIPIENT_SEED + 2000)).run(sr.twin_script(run["events"]))
+    at = log[0]["at"]
+    differ = (run["model"]["steps"]["image"][at] != plain["steps"]["image"][at]).reshape(sr.N, -1).any(1)
+    assert differ[sr.POSE_FIRST:sr.POSE_FIRST + sr.POSE_COUNT].sum() >= sr.POSE_COUNT // 2 and not differ[:sr.POSE_FIRST].any()
+    assert np.array_equal(run["model"]["steps"]["image"][:at], plain["steps"]["image"][:at])
+
+
 # ---- what the committed scenarios reach (the model alone) -----------------------------------------------------------------------------------
 def _edges(n):
     return {0, n - 1} | {b + d for b in range(64, n, 64) for d in (-1, 0)}
