@@ -277,6 +277,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int render_delta_from_step;   // 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
     int done_action_enum; // done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
+    int reseed_levels;    // "reseed_levels": levels of the new stream a bbai_reseed generates per listed env (0 = the whole ring); the env parks behind them
     int consume_fused;    // -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
     int inplace;          // BBAI_INPLACE: the in-place layout (live_slot, bbai_kernels.hpp): an env's live record IS the look-ahead slot its episode was generated into
     uint8_t* atlas;       // [n_tiles][192]
@@ -511,7 +512,8 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
 
 // The performance knobs (include/bbai.h: bbai_set_option), one row each: the option's name, the BBAI_* variable bbai_create reads (or none), the
 // field, the default, and how a raw value -- from the variable or from bbai_set_option alike -- becomes the stored one.  The read-only rows
-// at the end are looked up by bbai_get_option alone (their fields are set elsewhere).  Never semantics: every setting produces the same bytes.
+// at the end are looked up by bbai_get_option alone (their fields are set elsewhere).  Never semantics: every setting produces the same bytes --
+// but for the two semantic switches that ride in this table because the C surface is closed: "done_action_enum" and "reseed_levels".
 enum KnobNorm { AS_IS, FLAG /* v != 0 */, AT_LEAST /* max(lo, v) */, TRI /* v < 0: -1, else v != 0 */ };
 struct Knob { const char* name; const char* var; int bbai_env::*field; int def; KnobNorm norm; int lo; bool read_only; };
 static const Knob KNOBS[] = {
@@ -544,7 +546,8 @@ static const Knob KNOBS[] = {
     {"bot_group", "BBAI_BOT_GROUP", &bbai_env::bot_group, 0},
     {"step_render_split", "BBAI_STEP_RENDER_SPLIT", &bbai_env::step_render_split, -1},
     {"rollout_multi", "BBAI_ROLLOUT_MULTI", &bbai_env::rollout_multi, 1},
-    {"done_action_enum", nullptr, &bbai_env::done_action_enum, 0, FLAG},                      // (the one SEMANTIC switch in this list: include/bbai.h bbai_set_done_actions)
+    {"done_action_enum", nullptr, &bbai_env::done_action_enum, 0, FLAG},                      // (a SEMANTIC switch, the first of two in this list: include/bbai.h bbai_set_done_actions)
+    {"reseed_levels", nullptr, &bbai_env::reseed_levels, 0, AT_LEAST, 0},                     // (the second SEMANTIC switch: the depth of the next bbai_reseed calls; a host value read when a call is enqueued)
     {"pregen_lane", nullptr, &bbai_env::pregen_lane, 0, AS_IS, 0, true},                              // (set: bbai_set_option converts the generator state)
     {"lookahead_streams", nullptr, &bbai_env::n_sides, 0, AS_IS, 0, true},                            // (set: set_sides)
     {"gate_forced_strict", nullptr, &bbai_env::gate_forced, 0, AS_IS, 0, true},                       // 1: the caller's stream failed the concurrency probe
@@ -2105,13 +2108,14 @@ int bbai_set_done_actions(bbai_env* e, int enable) {
 int bbai_get_done_actions(bbai_env* e) { return e && e->lsm ? 1 : 0; }
 
 // Performance knobs by name (KNOBS, plus the three that do work): what the BBAI_* environment variables set at bbai_create, switchable on a
-// live handle so that measurements can alternate settings inside ONE process on ONE box (tools/ab.py).  Synchronises the device first.
+// live handle so that measurements can alternate settings inside ONE process on ONE box (tools/ab.py).  Synchronises the device first
+// ("reseed_levels" aside: a caller sets it around single bbai_reseed calls of a running loop).
 int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     if (!e || !name) ARG_FAIL("null handle or name");
     ON_DEVICE(e->device);
-    HIP_TRY(hipDeviceSynchronize());
-    const int v = (int)value;
     const Knob* k = find_knob(name);
+    if (!(k && k->field == &bbai_env::reseed_levels)) HIP_TRY(hipDeviceSynchronize());      // (a bbai_reseed reads its depth on the host, when it is enqueued: nothing in flight sees it)
+    const int v = (int)value;
     if (!strcmp(name, "pregen_lane")) {
         if (!e->mtt) { if (v) ARG_FAIL("pregen_lane: this level kind / layout is not covered by the lane generator"); }
         else if ((v != 0) != (e->pregen_lane != 0)) {
@@ -2263,6 +2267,12 @@ int bbai_load_state(bbai_env* e, const int64_t* ids, const int64_t* rows, int64_
 //   2. the caller's stream waits for the end of that generation, and only then consumes slot 0 of the new rings (k_reseed_consume).
 // After step 1 every closed window's refill has landed -- all their `pending` bytes are zero -- so the current window's buffer is the only one that can
 // hold a listed env, and k_reseed_seed clears it there.  k_reseed_consume then books the env's reset into that buffer like any finished env's.
+// Option "reseed_levels" = k (0 < k < D - inplace): only levels 0 .. k - 1 of the new stream are generated, into slots 0 .. k - 1.  Slot k keeps the
+// empty FROZEN hot state that k_reseed_seed wrote into every slot, so the env's ordinary move into it -- at the end of its k-th level under
+// auto-reset, or by the bbai_reset behind it -- PARKS the env: frozen, like an env that finished without auto-reset, until it is reseeded or
+// the batch is seeded.  Nothing else changes: same kernels, same order, same bookkeeping (the move is counted and booked for the window's
+// refill like any other; what the refill puts into the slots behind a parked env is never played).  bbai_reseedk.hpp says why every slot an env
+// can park in holds a record that is safe to move into.
 static int reseed_scratch(bbai_env* e) {
     if (e->rs_claim) return BBAI_OK;          // (the group is committed as a whole: any of its fields says so)
     const size_t n = (size_t)e->n;
@@ -2298,6 +2308,8 @@ int bbai_reseed(bbai_env* e, const int64_t* ids, const uint64_t* seeds, int64_t 
     uint8_t* const cur_pending = e->pending + (size_t)tp.wb * e->n;
     uint8_t* const cur_first = e->first_slot + (size_t)tp.wb * e->n;
     hipStream_t g = e->side;
+    const int full = e->depth - e->inplace;           // levels of a whole ring; a depth of 0, or of that many and more, is the whole ring
+    const int gen = e->reseed_levels > 0 && e->reseed_levels < full ? e->reseed_levels : full;
     HIP_TRY(hipEventRecord(e->ev_rs_call, s));
     HIP_TRY(hipStreamWaitEvent(g, e->ev_rs_call, 0));
     for (int k = 1; k < e->n_sides; ++k) {
@@ -2306,7 +2318,7 @@ int bbai_reseed(bbai_env* e, const int64_t* ids, const uint64_t* seeds, int64_t 
     }
     HIP_TRY(hipMemsetAsync(e->rs_count, 0, SHARDS * GEN_COUNT_U32 * 4, g));
     hipLaunchKernelGGL(k_reseed_seed<0>, dim3((unsigned)std::min<int64_t>((count + 63) / 64, 65536)), dim3(64), 0, g, e->n, ids, seeds, count, e->mt, e->mti, e->mtpar,
-                       e->hot, e->next_hot, e->depth, e->inplace, cur_pending, e->rs_pending, e->rs_first, e->rs_claim, e->rs_list, e->rs_count);
+                       e->hot, e->next_hot, e->depth, e->depth - gen, cur_pending, e->rs_pending, e->rs_first, e->rs_claim, e->rs_list, e->rs_count);
     launch_pregen(e, pregen_grid(e, count), true, e->rs_pending, e->rs_first, count, 0, e->rs_list, e->rs_count);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_rs_done, g));

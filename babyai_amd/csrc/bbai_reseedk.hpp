@@ -7,6 +7,18 @@
 //   k_reseed_consume  wave = list entry: consume_env (bbai_stepk.hpp) on slot 0 under the current window's bookkeeping -- the copy (or, in place,
 //                     the move) into the live state, the verifier view, planes, first observation -- plus the reset total and an expert plan that
 //                     no longer matches any step.
+// A SHORT reseed (option "reseed_levels" = k, 0 < k < D - inplace) books k levels instead of the ring (bbai_reseed hands k_reseed_seed the
+// slots that get NO level: D - k instead of `inplace` -- the kernel and its signature are the whole-ring reseed's): the generator fills slots 0 .. k - 1 and
+// slot k keeps the empty frozen Hot written here, so the env's ordinary move into slot k (consume_env, advance_load / advance_finish) PARKS it;
+// no step kernel knows.  That move reads slot k's RECORD too (Prog, start_carry -> pos[], window plane, C plane row, first observation), and
+// nothing wrote one for this seed.  It is safe because every slot an env can move into holds a record some generator run completed:
+//   * bbai_seed fills slots 0 .. D - 1 - inplace of every env, and k <= D - 1 - inplace, so slot k is one of them (the in-place layout's empty
+//     slot D - 1, zeros since bbai_create, is never a parking slot; bbai_reset calls can walk a parked env there, 2B consume-ticks behind the
+//     reseed at the earliest, and k_gate has by then waited for the refill that the reseed's own consume booked for slot D - 1);
+//   * later writers of a slot are the generators alone (whole records, each behind the last on the look-ahead streams) and, in place, the
+//     steps of the episode that lived there -- which change cells and id bytes but never Prog, and leave pos[] of a carried object where it
+//     was (apply_start_carry, bbai_step.hpp): start_carry and the position it indexes stay what a generator wrote, inside the env's rows.
+// What the parked env shows is that old level's first observation under the empty pose: unspecified by contract, never stepped (frozen).
 // An env listed twice (a caller error) is seeded and consumed ONCE: k_reseed_seed claims an env by its bit of `claim` and skips an entry
 // whose env is taken, k_reseed_consume gives the bit back and skips an entry whose env's bit is gone.  So the work list holds every env at
 // most once (its sub-lists cannot overflow: k_compact's bound), and `claim` is all zero between calls.
@@ -28,7 +40,7 @@ using namespace bbai;
 template <int TAIL = 0>
 __global__ __launch_bounds__(64) void k_reseed_seed(int64_t n, const int64_t* __restrict__ ids /* or NULL: env k */, const uint64_t* __restrict__ seeds, int64_t count,
                                                     uint32_t* __restrict__ mts, int32_t* __restrict__ mtis, uint8_t* __restrict__ mtpar /* or NULL */,
-                                                    Hot* __restrict__ hots, Hot* __restrict__ next_hots, int depth, int inplace,
+                                                    Hot* __restrict__ hots, Hot* __restrict__ next_hots, int depth, int spare /* slots of the ring that get no level: `inplace` (the whole ring), D - k (a short reseed) */,
                                                     uint8_t* __restrict__ cur_pending /* the current window's buffer */,
                                                     uint8_t* __restrict__ rs_pending, uint8_t* __restrict__ rs_first, uint32_t* __restrict__ claim,
                                                     int32_t* __restrict__ rs_list, uint32_t* __restrict__ rs_count) {
@@ -48,7 +60,7 @@ __global__ __launch_bounds__(64) void k_reseed_seed(int64_t n, const int64_t* __
         hots[env] = h;
         for (int d = 0; d < depth; ++d) next_hots[ring_at(d, env, depth)] = h;
         cur_pending[env] = 0;
-        rs_pending[env] = (uint8_t)(depth - inplace);
+        rs_pending[env] = (uint8_t)(depth - spare);                   // slots 0 .. depth - spare - 1 get the new stream's first levels; the next slot of a short reseed parks the env
         rs_first[env] = 0;
         const int j = (int)((env >> 6) % SHARDS);                     // k_compact's sub-list of the env's 64-env block: at most `cap` different envs
         const uint32_t at = atomicAdd(&rs_count[j * GEN_COUNT_U32], 1u);

@@ -146,6 +146,20 @@ def seeds_u64(seeds, what):
     return np.array(vals, dtype=np.uint64)
 
 
+def reseed_levels_arg(levels, what):
+    """A `levels=` / `reseed_levels=` argument as None or an int >= 0 -- ValueError (after `what`) for anything that is not an integer (bool
+    and float included) and for a negative one."""
+    if levels is None:
+        return None
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)):
+        raise ValueError("%s: levels must be None or an integer, got %r" % (what, levels))
+    if int(levels) < 0:
+        raise ValueError("%s: levels must not be negative, got %d" % (what, int(levels)))
+    if int(levels) > 0x7fffffff:
+        return 0            # (beyond any ring: the whole ring)
+    return int(levels)
+
+
 def load_atlas(path, tool):
     """(tiles, lut) of a tile atlas file as contiguous uint8; `tool`: what writes the file, for the EngineError if it is not there."""
     if not os.path.isfile(path):
@@ -783,20 +797,33 @@ class BatchedBabyAIEnv(object):
             raise ValueError("reseed: %d envs listed for %d seeds" % (k, int(seeds_t.shape[0])))
         return k, seeds_t
 
-    def reseed(self, ids, seeds):
+    def reseed(self, ids, seeds, levels=None):
         """`env[ids[k]].seed(seeds[k]); env[ids[k]].reset()` for the listed envs of a live batch (ids None = every env; an int sequence,
         an ndarray or an int64 device tensor; seeds: ints, a uint64 ndarray or an int64 / uint64 device tensor), on the current stream
         without a host synchronisation: each listed env's level stream restarts from its seed, the env starts level 0 of it -- a frozen
         env (auto_reset=False) is live again -- and every other env goes on as if nothing had happened.  Returns the observation dict as
         reset() does, the listed rows holding the new episodes' first observations.  An id outside [0, num_envs) is skipped (pad with
-        -1); ValueError: see _reseed_args; the same env twice in a DEVICE id list is undefined as to which seed it gets."""
+        -1); ValueError: see _reseed_args; the same env twice in a DEVICE id list is undefined as to which seed it gets.
+        `levels`: how many levels of its new stream a listed env will play (include/bbai.h bbai_reseed, option "reseed_levels"): only those
+        are generated, and the env PARKS -- frozen, done = 1, its other outputs unspecified -- when the last of them ends, until it is
+        reseeded again.  None: the handle's option as it stands (0 unless set: the whole look-ahead ring, the env never parks); an int: that
+        depth for this call, the option's previous value put back behind it; 0 or anything beyond the ring's depth is the whole ring.
+        ValueError for a negative or non-integer value."""
+        levels = reseed_levels_arg(levels, "reseed")
         k, seeds_t = self._reseed_args(ids, seeds)
         if k == 0:
             return self._obs()
         _, ids_ptr, ids_t = self._ids(ids)
         self._hold["reseed"] = (ids_t, seeds_t)
-        _check(self.lib, self.lib.bbai_reseed(self.handle, ids_ptr, seeds_t.data_ptr(), k, self.image.data_ptr(), self.direction.data_ptr(),
-                                               self._stream()), "bbai_reseed")
+        before = None if levels is None else self.get_option("reseed_levels")
+        if before is not None and before != levels:
+            self.set_option("reseed_levels", levels)
+        try:
+            _check(self.lib, self.lib.bbai_reseed(self.handle, ids_ptr, seeds_t.data_ptr(), k, self.image.data_ptr(), self.direction.data_ptr(),
+                                                   self._stream()), "bbai_reseed")
+        finally:
+            if before is not None and before != levels:
+                self.set_option("reseed_levels", before)
         return self._obs()
 
     def save_checkpoint(self):
@@ -936,7 +963,8 @@ class BatchedBabyAIEnv(object):
 
     def set_option(self, name, value):
         """A performance knob of the live handle by name (include/bbai.h bbai_set_option: launch shapes, render input,
-        priorities -- never semantics).  What measurements alternate inside one process (tools/ab.py)."""
+        priorities -- never semantics, but for "done_action_enum" and "reseed_levels": see reseed()).  What measurements alternate inside
+        one process (tools/ab.py)."""
         _check(self.lib, self.lib.bbai_set_option(self.handle, name.encode(), int(value)), "bbai_set_option(%s)" % name)
     
     def get_option(self, name):

@@ -44,14 +44,18 @@ class AgentPolicy(object):
                                      tuple(bool(d) for d in done.cpu().numpy()))
 
 
-def _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every):
+def _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every, reseed_levels=None, make_env=BatchedBabyAIEnv):
     """evaluate_policy(pool=k): min(k, episodes) envs play all the seeds.  At every poll the envs that have finished are read out and
     reseeded (BatchedBabyAIEnv.reseed: env.seed(s); env.reset() of the listed envs) with the next unplayed seeds, until none are left;
     an env without a seed left stays frozen.  An env waits frozen between its episode's end and the next poll, so `t`, the global frame
-    count, is not a frame count of any episode: an episode's frames are counted from the frame it started at."""
+    count, is not a frame count of any episode: an episode's frames are counted from the frame it started at.  `reseed_levels` goes to every
+    reseed as `levels=`: an env here plays ONE level per seed, so 1 generates that level instead of the look-ahead ring (same logs).
+    `make_env`: what builds the batch (the tests run this loop on CPU tensors over the host build)."""
     import torch
+    from .engine import reseed_levels_arg
+    reseed_levels = reseed_levels_arg(reseed_levels, "evaluate_policy")
     n = min(int(pool), episodes)
-    env = BatchedBabyAIEnv(env_name, n, device=device, pixel=pixel, auto_reset=False)
+    env = make_env(env_name, n, device=device, pixel=pixel, auto_reset=False)
     try:
         env.seed(np.arange(n, dtype=np.uint64) + np.uint64(seed))
         instr = env.enable_instr_tokens()
@@ -88,7 +92,7 @@ def _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_e
             if k:
                 again = fin[:k].contiguous()
                 new_eps = np.arange(next_ep, next_ep + k, dtype=np.int64)
-                obs = env.reseed(again, new_eps.astype(np.uint64) + np.uint64(seed))
+                obs = env.reseed(again, new_eps.astype(np.uint64) + np.uint64(seed), **({} if reseed_levels is None else {"levels": reseed_levels}))
                 episode[again] = torch.as_tensor(new_eps, device=dev)
                 started[again] = t
                 start[again] = 1
@@ -100,21 +104,23 @@ def _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_e
 
 
 def evaluate_policy(policy, env_name, seed, episodes, pixel=False, device="cuda:0", chunk=262144, poll_every=16,
-                    agent=None, pool=None):
+                    agent=None, pool=None, reseed_levels=None):
     """Run `episodes` episodes (seeds seed .. seed+episodes-1) to completion; returns the reference's `logs` dict
     (num_frames_per_episode, return_per_episode, seed_per_episode).  `agent`: wrap a reference-style agent instead of a
     tensor policy.  `poll_every`: frames between two host checks of "is everybody done" (frozen envs cost nothing).
     `pool=k`: instead of one env per episode, min(k, episodes) envs play all the seeds, a finished env being reseeded with the next
     unplayed seed at the next poll (_evaluate_pool); `obs` then has one more key, `episode_start` (uint8 [N]: the env's row is the
     first observation of an episode), `t` stays the global frame count, and the logs -- in seed order -- equal the default path's for
-    any policy that is a pure function of the observation.  Not for a stateful `agent` (ValueError)."""
+    any policy that is a pure function of the observation.  Not for a stateful `agent` (ValueError).  `reseed_levels` (pool mode only; None =
+    the engine's option as it stands, the whole ring unless set): the `levels=` of every reseed -- 1 generates the one level an env plays
+    per seed instead of its whole look-ahead ring; the logs are the same."""
     import torch
     if pool is not None:
         if agent is not None:
             raise ValueError("evaluate_policy: pool= serves tensor policies only, not agent=")
         if int(pool) < 1:
             raise ValueError("evaluate_policy: pool must be at least 1")
-        return _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every)
+        return _evaluate_pool(policy, env_name, seed, episodes, pixel, device, pool, poll_every, reseed_levels)
     logs = {"num_frames_per_episode": [], "return_per_episode": [], "seed_per_episode": []}
     for first in range(0, episodes, chunk):
         n = min(chunk, episodes - first)

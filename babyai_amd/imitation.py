@@ -279,12 +279,15 @@ class DemoStore(object):
         return cls(*[torch.cat([p[i] for p in parts]) for i in range(4)], np.concatenate([[0], np.cumsum(lens)]))
 
     @classmethod
-    def collect_seeds(cls, env_name, seeds, device="cuda:0", pool=32768, chunk=None, env=None):
+    def collect_seeds(cls, env_name, seeds, device="cuda:0", pool=32768, chunk=None, env=None, reseed_levels=None):
         """One demonstration per LISTED seed (`generate_demos(env_name, seeds)` of scripts/train_intelligent_expert.py:106-147): for every
         seeds[j], in order, the episode that `env.seed(seeds[j]); env.reset()` starts, played by the expert, kept iff it ends with
         reward > 0 and the expert did not give up.  -> (store of the kept demonstrations in the order of `seeds`, kept = their positions in
-        `seeds`, int64 on the host).  min(pool, len(seeds)) envs play the list (see _collect_seeds)."""
-        return _collect_seeds(cls, env_name, seeds, device, pool, chunk, env)
+        `seeds`, int64 on the host).  min(pool, len(seeds)) envs play the list (see _collect_seeds).  `reseed_levels` (None = the engine's
+        option as it stands: whole look-ahead rings): the `levels=` of the pool's reseeds; with 1 a pool env plays its seed's one episode and
+        parks until the round's reseed instead of playing on through rows nobody reads -- the same (store, kept), less generator and
+        expert work."""
+        return _collect_seeds(cls, env_name, seeds, device, pool, chunk, env, reseed_levels)
 
     # ---- ways out ----
     def to_reference(self, pack=None):
@@ -521,7 +524,7 @@ class _Timed(object):
             ROUND_EVENTS.append((self.part, self.ev[0], self.ev[1]))
 
 
-def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
+def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env, reseed_levels=None):
     """A pool of P = min(pool, J) auto-resetting envs plays the J listed seeds, rounds of `chunk` expert steps each: bot_rollout into the next
     slot of a ring of history slots, one k_demo_jobs launch (which episodes ended, which are kept, who plays what next), one read of its four
     counters -- the round's only synchronisation --, a reseed of the envs that finished with the device lists the kernel wrote, and, if
@@ -530,9 +533,16 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
     max_steps_bound steps, so a ring of ceil(max_steps_bound / chunk) + 1 slots never overwrites a row that a live episode needs.  The
     staging order depends on which wave claimed what; the result -- the staging store's demos sorted by job -- does not.  `env`: any
     object with num_envs, device, max_steps_bound, bot_rollout(steps, tokens, out), reseed(ids, seeds) and close(), already created on the
-    first num_envs seeds with auto-reset, token rows on and reset() behind it (the host build in the tests); pool = its size."""
+    first num_envs seeds with auto-reset, token rows on and reset() behind it (the host build in the tests); pool = its size.
+    `reseed_levels` = k (not None) is passed to every reseed as `levels=k` (an `env=` then needs reseed(ids, seeds, levels=)): a pool env plays
+    k levels of its seed's stream and parks -- frozen: its steps write no `done` / `reward` rows, the expert answers `done` for it -- until the
+    round's reseed.  Only an env's FIRST done row of a round is ever read, and the rows in front of it were written by the live env; an env
+    without a job (idle: its column may be parked, unwritten memory from its first row on) is skipped by demo_jobs whatever its column holds.
+    So every k >= 1 gives the default's (store, kept).  The first round's envs come from seed() + reset(), with full rings: a pool created
+    here is put into its first levels by a reseed of every env at depth k instead of by reset(), so that they park as well."""
     import torch
-    from .engine import seeds_u64
+    from .engine import reseed_levels_arg, seeds_u64
+    reseed_levels = reseed_levels_arg(reseed_levels, "collect_seeds")
     seeds_h = seeds_u64(seeds, "collect_seeds")
     J = len(seeds_h)
     if J == 0:
@@ -549,7 +559,10 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
             raise ValueError("collect_seeds: %d envs for %d seeds" % (P, J))
         if own:
             env.enable_instr_tokens()
-            env.reset()
+            if reseed_levels:
+                env.reseed(None, seeds_h[:P], levels=reseed_levels)
+            else:
+                env.reset()
         bound = int(env.max_steps_bound)
         chunk = collect_chunk(bound) if chunk is None else int(chunk)
         if chunk < 1:
@@ -588,7 +601,10 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
             claimed, ended, nrec, frames = int(c[0]) - cursor, int(c[1]) - finished, int(c[2]), int(c[3])
             if claimed and cursor < J:
                 with _Timed(dev, "reseed"):
-                    env.reseed(ids_out, seeds_out)
+                    if reseed_levels is None:
+                        env.reseed(ids_out, seeds_out)
+                    else:
+                        env.reseed(ids_out, seeds_out, levels=reseed_levels)
             if nrec:
                 rec = records[:nrec].clone()
                 kept_records.append(rec)
@@ -612,24 +628,28 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env):
             env.close()
 
 
-def grow_training_set(store, policy, env_name, eval_seed, grow_factor, num_eval_demos, device="cuda:0", pixel=False, pool=None, max_rounds=64):
+def grow_training_set(store, policy, env_name, eval_seed, grow_factor, num_eval_demos, device="cuda:0", pixel=False, pool=None, max_rounds=64,
+                      reseed_levels=None):
     """`grow_training_set` of scripts/train_intelligent_expert.py:150-176, step for step: until `store` holds int(len(store) * grow_factor)
     demonstrations, evaluate `policy` (a tensor policy of `evaluate.evaluate_policy`) on num_eval_demos fresh seeds from eval_seed on (:158-160),
     move eval_seed past them (:166), take the seeds of the episodes with return <= 0 in episode order, cut to the number still missing
     (:162-165, :168), have the expert make one demonstration for each (`DemoStore.collect_seeds`, :169) and extend the store (:171).  Returns
     the new eval_seed (:176).  `pool`: the env pool of both the evaluation and the collection (None: one env per evaluation episode, the
     default pool of collect_seeds).  The reference loops for ever under a learner that never fails -- or whose failures the expert cannot
-    solve either; here `max_rounds` evaluations in a row that add nothing raise RuntimeError."""
+    solve either; here `max_rounds` evaluations in a row that add nothing raise RuntimeError.  `reseed_levels`: the depth of the reseeds of
+    both (evaluate_policy with a pool, collect_seeds); both play one episode per seed, so 1 changes no result."""
     from .evaluate import evaluate_policy
     target = int(len(store) * grow_factor)
     idle = 0
     while len(store) < target:
-        logs = evaluate_policy(policy, env_name, eval_seed, num_eval_demos, pixel=pixel, device=device, pool=pool)
+        logs = evaluate_policy(policy, env_name, eval_seed, num_eval_demos, pixel=pixel, device=device, pool=pool,
+                               **({} if pool is None or reseed_levels is None else {"reseed_levels": reseed_levels}))
         eval_seed += num_eval_demos
         fail = [s for s, r in zip(logs["seed_per_episode"], logs["return_per_episode"]) if r <= 0][:target - len(store)]
         before = len(store)
         if fail:
-            new, _ = DemoStore.collect_seeds(env_name, fail, device=device, **({} if pool is None else {"pool": pool}))
+            new, _ = DemoStore.collect_seeds(env_name, fail, device=device, **({} if pool is None else {"pool": pool}),
+                                             **({} if reseed_levels is None else {"reseed_levels": reseed_levels}))
             store.extend(new)
         idle = 0 if len(store) > before else idle + 1
         if idle >= max_rounds:

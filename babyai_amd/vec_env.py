@@ -161,10 +161,11 @@ class _VecBase(object):
         """Snapshot rows into the listed envs (BatchedBabyAIEnv.load_state); returns the obs list of the whole batch, as reset() does."""
         return self._obs_list(self.engine.load_state(snap, ids, rows))
 
-    def reseed(self, ids, seeds):
+    def reseed(self, ids, seeds, levels=None):
         """env.seed(s); env.reset() for the listed envs (BatchedBabyAIEnv.reseed: evaluate.py:64-71, make_agent_demos.py:93 seed per
-        episode); returns the obs list of the whole batch, as reset() does."""
-        return self._obs_list(self.engine.reseed(ids, seeds))
+        episode); returns the obs list of the whole batch, as reset() does.  `levels`: the levels of its seed's stream a listed env will
+        play before it parks (None: the engine's "reseed_levels" option as it stands)."""
+        return self._obs_list(self.engine.reseed(ids, seeds) if levels is None else self.engine.reseed(ids, seeds, levels=levels))
 
     def render(self):
         raise NotImplementedError
@@ -200,8 +201,8 @@ class BatchedManyEnvs(_VecBase):
         self.done = list(done)
         return iter((obs, reward, done, info))
 
-    def reseed(self, ids, seeds):
-        obs = super().reseed(ids, seeds)
+    def reseed(self, ids, seeds, levels=None):
+        obs = super().reseed(ids, seeds, levels=levels)
         listed = range(self.num_envs) if ids is None else np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids, dtype=np.int64).reshape(-1)
         for i in listed:
             if 0 <= int(i) < self.num_envs:

@@ -243,6 +243,18 @@ int bbai_load_state(bbai_env* env, const int64_t* ids_dev /* NULL = envs 0..coun
  * token buffer gets the new mission's row, and bbai_reset_count grows by one.  Every other env goes on exactly as if nothing had happened.
  * It is no consume-tick; the registered render target is NOT touched (render afterwards, as after bbai_reset).  The call's latency is that of
  * ONE env's ring generated in sequence (ring depth x one level), however few envs are listed.
+ * A SHORT reseed -- bbai_set_option(env, "reseed_levels", k) with 0 < k < the ring's depth (2 x "lookahead_period") in front of the call --
+ * says "this env will play k levels of the seed's stream": only levels 0 .. k - 1 are generated (k levels of latency instead of the ring's),
+ * and when the env's k-th level ends under auto_reset the env PARKS: it is frozen like an env that finished without auto-reset -- done stays
+ * 1, the reward stays the last episode's, bbai_bot_act / bbai_bot_rollout answer `done` (6) with gave_up = 0 -- under every step entry until it
+ * is reseeded (at any depth) or the batch is seeded by bbai_seed.  Without auto_reset the env freezes at the end of each level as ever and
+ * the bbai_reset that moves it past its k levels parks it.  bbai_reset_count counts the parking move like any reset.  A parked env's image,
+ * direction, mission and token row are unspecified, and so is what its stream would have produced beyond level k - 1: a parked env is
+ * reseeded, not reset.  "done stays 1" is said of the buffers the steps write: a step leaves a frozen env's reward and done alone, so in
+ * bbai_bot_rollout's HISTORY, where every step has rows of its own, a parked env's reward / done rows are not written at all -- read an env's
+ * FIRST done row of a call, as bbai_demo_jobs does.  The window refills regenerate the slots a parked env has left like any others: levels
+ * nobody plays, at most k + 1 per parked env.  k = 0 (the default) or k >= the ring's depth is the whole ring, byte for byte as without
+ * the option.
  * An id outside [0, n_envs) skips the entry (pad a fixed-length list with -1); the same env listed twice is a caller error (it gets one of
  * its seeds).  BBAI_ERR_ARG, before any device work, for a null handle, null seeds, null outputs, a negative count or count > n_envs without
  * ids; BBAI_ERR_STATE for a handle that was never seeded, and for one that was seeded but not yet reset unless every env is listed (ids_dev =
@@ -488,7 +500,10 @@ int bbai_get_done_actions(bbai_env* env);
  *   "bot_group"         the expert's kernel (bbai_bot_act / bbai_bot_rollout): 0 (default) = one lane per env (k_bot), 16 = one 16-lane
  *                       group per env with the first search in LDS (k_botg: same decisions, measured ~2 x slower -- an experiment
  *                       kept for reference); also BBAI_BOT_GROUP at bbai_create
- *   "done_action_enum"  the one semantic switch, meaningful in done-action mode only: see bbai_set_done_actions
+ *   "done_action_enum"  a semantic switch (one of two in this list), meaningful in done-action mode only: see bbai_set_done_actions
+ *   "reseed_levels"     the other semantic switch: how many levels of the new stream the following bbai_reseed calls generate per listed env (see
+ *                       bbai_reseed).  0 (default), or anything >= the ring's depth: the whole ring.  Negative values are stored as 0.  Read on the
+ *                       host when a bbai_reseed is enqueued, so setting it does not synchronise the device and costs no allocation
  * BBAI_ERR_ARG for an unknown name. */
 int bbai_set_option(bbai_env* env, const char* name, int64_t value);
 /* Read a knob back (the names of bbai_set_option), or "lookahead_period" (the refill period the handle chose at bbai_create), or

@@ -5,9 +5,10 @@ in the same process and alternated with them, the only way to give envs new seed
 clock: bbai_seed synchronises).  A reseed generates the listed envs' WHOLE rings (ring depth D levels each, one env's in sequence), so its latency
 is bounded below by D levels of one lane group / lane however few envs are listed: the 64-env figure is that latency.  Every figure is the mean
 over at least --min-seconds of back-to-back calls on warm shapes; `runs_ms` holds the repeated figures, `ms` their median.  One JSON line per
-figure.
+figure.  --levels K[,K ...]: SHORT reseeds instead (reseed(ids, seeds, levels=K): K levels per listed env and a parking slot behind them) -- the
+64- and 4 096-env lists at depth 0 (the whole ring) and at every K, alternated on the same handle; the whole-batch figures are left out.
 
-    python tools/reseed_bench.py [--only local,boss,goto] [--out profiles/reseed/reseed_bench.jsonl]
+    python tools/reseed_bench.py [--only local,boss,goto] [--levels 1] [--out profiles/reseed/reseed_bench.jsonl]
 """
 import argparse
 import json
@@ -62,8 +63,10 @@ def main():
     ap.add_argument("--only", default=",".join(WORKLOADS))
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--pairs", type=int, default=2, help="alternations of the reseed calls with seed() + reset()")
+    ap.add_argument("--levels", default=None, help="comma-separated reseed depths to alternate with depth 0 (the whole ring)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    depths = [int(v) for v in args.levels.split(",")] if args.levels else None
     import numpy as np
     import torch
     from babyai_amd.engine import BatchedBabyAIEnv
@@ -99,14 +102,24 @@ def main():
                 env.seed(all_seeds)
                 env.reset()
 
-            for pair in range(args.pairs):
+            full = shape["ring_depth"] - shape["inplace"]
+            for pair in range(args.pairs if depths else 0):
+                for k in LISTS:
+                    ids = torch.as_tensor(np.sort(np.random.RandomState(k).choice(n, k, replace=False)), device=dev)
+                    seeds = torch.as_tensor((np.arange(k, dtype=np.int64) * 3 + 5 * 10 ** 6 + pair), device=dev)
+                    for depth in [0] + depths:
+                        med, runs, reps = event_ms(torch, lambda: env.reseed(ids, seeds, levels=depth), args.min_seconds)
+                        gen = depth if 0 < depth < full else full
+                        emit(dict(shape, figure="reseed_%d_scattered" % k, reseed_levels=depth, pair=pair, listed=k, ms=med, runs_ms=runs, calls_per_run=reps,
+                                  levels_generated=k * gen, us_per_level_of_one_env=med * 1e3 / gen))
+            for pair in range(0 if depths else args.pairs):
                 for k in LISTS + ((n,) if lookahead is None else ()):
                     ids = None if k == n else torch.as_tensor(np.sort(np.random.RandomState(k).choice(n, k, replace=False)), device=dev)
                     seeds = torch.as_tensor((np.arange(k, dtype=np.int64) * 3 + 5 * 10 ** 6 + pair), device=dev)
                     med, runs, reps = event_ms(torch, lambda: env.reseed(ids, seeds), args.min_seconds)
                     emit(dict(shape, figure="reseed_all" if k == n else "reseed_%d_scattered" % k, pair=pair, listed=k, ms=med, runs_ms=runs, calls_per_run=reps,
                               levels_generated=k * (shape["ring_depth"] - shape["inplace"]), us_per_level_of_one_env=med * 1e3 / (shape["ring_depth"] - shape["inplace"])))
-                if lookahead is None:
+                if lookahead is None and not depths:
                     w_ms, calls = wall_ms(torch, whole_batch, args.min_seconds)
                     emit(dict(shape, figure="seed_plus_reset_whole_batch", pair=pair, listed=n, ms_wall=w_ms, calls=calls))
             assert env.get_option("gate_timeouts") == 0

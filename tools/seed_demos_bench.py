@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The numbers of `DemoStore.collect_seeds` (GPU box; DESIGN.md section 5i quotes them).
 
-    python tools/seed_demos_bench.py [--out profiles/seed_demos/seed_demos_bench.jsonl] [--boss 131072] [--local 65536] [--reps 2]
+    python tools/seed_demos_bench.py [--out profiles/seed_demos/seed_demos_bench.jsonl] [--boss 131072] [--local 65536] [--reps 2] [--reseed-levels 1]
 
 One JSON line per measurement, the file rewritten on every run.  Per workload (BossLevel / GoToLocal, seeds 1000 ...) and look-ahead period
 (the default, and BBAI_LOOKAHEAD=4), alternated `--reps` times in one process:
@@ -9,7 +9,9 @@ One JSON line per measurement, the file rewritten on every run.  Per workload (B
   `DemoStore.collect` of the same seed range -- the outside reference: the same demonstrations where every first episode is solved.
 The first repetition of every collect_seeds run also brackets the parts of its rounds by HIP events (imitation.ROUND_EVENTS): the share of
 the summed round time spent in bot_rollout, reseed, k_demo_jobs, the pack and the extend.  A configuration whose history ring does not fit
-half of the free device memory is reported with the error it raises."""
+half of the free device memory is reported with the error it raises.
+--reseed-levels K: the POOL rows only (no one-env-per-seed run, no `collect`), each pool alternated without and with
+collect_seeds(reseed_levels=K) -- short reseeds, the envs parking behind their K levels -- and the two results compared."""
 import argparse
 import json
 import os
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--local", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--pools", default="8192,32768")
+    ap.add_argument("--reseed-levels", type=int, default=None)
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
@@ -54,10 +57,11 @@ def main():
             else:
                 os.environ["BBAI_LOOKAHEAD"] = lookahead
             DemoStore.collect_seeds(level, range(1000, 1256), pool=64)          # warm-up: allocator, library, kernels
+            variants = [(p, None) for p in pools + ["collect"]] if a.reseed_levels is None else [(p, k) for p in pools[:-1] for k in (None, a.reseed_levels)]
             for rep in range(a.reps):
-                for path in pools + ["collect"]:
+                for path, depth in variants:
                     rec = dict(what="demos", level=level, seeds=n, lookahead=lookahead, rep=rep, path="collect" if path == "collect" else "collect_seeds",
-                               pool=None if path == "collect" else path, one_env_per_seed=path == n)
+                               pool=None if path == "collect" else path, one_env_per_seed=path == n, reseed_levels=depth)
                     imitation.ROUND_EVENTS = [] if (rep == 0 and path != "collect") else None
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
@@ -66,8 +70,11 @@ def main():
                             store = DemoStore.collect(level, n, 1000, batch=n)
                             kept = len(store)
                         else:
-                            store, k = DemoStore.collect_seeds(level, range(1000, 1000 + n), pool=path)
+                            store, k = DemoStore.collect_seeds(level, range(1000, 1000 + n), pool=path, reseed_levels=depth)
                             kept = len(k)
+                            if a.reseed_levels is not None:          # the two variants return the same demonstrations
+                                digest = (kept, store.num_frames, int(store.action.to(torch.int64).sum()), int(store.image[::97].to(torch.int64).sum()))
+                                rec.update(digest=list(digest))
                         torch.cuda.synchronize()
                         dt = time.perf_counter() - t0
                         rec.update(seconds=dt, demos_per_s=kept / dt, seeds_per_s=n / dt, kept=kept, frames=store.num_frames)
