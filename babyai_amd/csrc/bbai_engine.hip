@@ -19,7 +19,8 @@
 //                     k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
 //                     the buffer holds are stored.  (render_launch)
 //   bbai_gridk.hpp    k_render_grid<TS>: the full-grid picture; k_full_obs: the fully observable encoding.  (render_grid_launch, full_launch)
-//   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32.  (render_view_launch)
+//   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32 (render_view_launch); k_view_delta<TS> / k_view_ids: a whole
+//                     batch into the target registered at that size, only the 64-byte pieces whose cells changed.  (view_delta_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
 //   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch / k_demo_jobs / k_demo_pack_list: demonstrations that stay on the device.
@@ -264,8 +265,10 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int render_pace;      // (experiment) 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
                           // one counter serves them
     // delta rendering (bbai_set_render_target): the registered buffer, and the atlas tile ids of the frame it holds
-    uint8_t* rt_pixels;   // the registered caller-owned uint8[n][9408] buffer (NULL: none); only this handle's renders write there
-    uint8_t* rt_shadow;   // [n][49] tile id of every cell of the frame in rt_pixels (allocated at the first registration)
+    uint8_t* rt_pixels;   // the registered caller-owned uint8[n][7 rt_ts][7 rt_ts][3] buffer (NULL: none); only this handle's renders write there
+    int rt_ts;            // the tile size of that registration: 8 (bbai_render's delta render), 16 / 32 (bbai_render_view's: k_view_delta)
+    int rt_next_ts;       // "render_target_tile_size": the tile size the NEXT bbai_set_render_target registers (8, default)
+    uint8_t* rt_shadow;   // [n][49] tile id of every cell of the frame in rt_pixels, in the atlas of rt_ts (allocated at the first registration)
     bool rt_valid;        // rt_shadow describes rt_pixels; false after registration / bbai_set_atlas / bbai_render_invalidate / a full render into it
     int64_t rt_filled;    // while not valid: envs [0, rt_filled) rewritten by full renders with shadow ids since (a split render's halves)
     int render_delta;     // 1 (default) = renders into the registered buffer store only changed lines
@@ -529,6 +532,7 @@ static const Knob KNOBS[] = {
     {"render_delta_bpc", nullptr, &bbai_env::render_delta_bpc, 0, AT_LEAST, 0},
     {"render_delta_from_step", nullptr, &bbai_env::render_delta_from_step, -1, TRI},
     {"render_piece_bytes", nullptr, &bbai_env::render_piece_bytes, RENDER_PIECE_DEFAULT},   // (64 or 128: bbai_set_option refuses the rest)
+    {"render_target_tile_size", nullptr, &bbai_env::rt_next_ts, TILE},                        // (8, 16 or 32: bbai_set_option refuses the rest)
     {"grid_render_bpc", nullptr, &bbai_env::grid_bpc, 0, AT_LEAST, 0},
     {"step_prio", "BBAI_STEP_PRIO", &bbai_env::step_prio, 1},                          // (never slower, GoTo 131 072 envs -2 %: profiles/r03/step_prio_ab.jsonl)
     {"pregen_group", "BBAI_PREGEN_GROUP", &bbai_env::pregen_group, 32},
@@ -613,6 +617,7 @@ static int create_finish(bbai_env* e) {
         e->*k.field = kv ? knob_value(k, atoi(kv)) : k.def;
     }
     if (!e->mtt) e->lane_blocks = 0;        // (no lane generator on this handle)
+    e->rt_ts = TILE;
     return BBAI_OK;
 }
 
@@ -1067,7 +1072,7 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
     HIP_TRY(hipMemcpy(e->atlas, tiles, (size_t)n_tiles * TILE_BYTES, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->lut, lut, 512, hipMemcpyHostToDevice));
     e->n_tiles = n_tiles;
-    e->rt_valid = false; e->rt_filled = 0;           // the registered frame was drawn with the old atlas
+    if (e->rt_ts == TILE) { e->rt_valid = false; e->rt_filled = 0; }      // the registered frame was drawn with the old atlas (a 16 / 32 target: bbai_set_view_atlas)
     return BBAI_OK;
 }
 
@@ -1077,6 +1082,7 @@ int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
     // the first registration: the shadow and the dirty masks, both or neither (un-registering keeps them)
     if (pixels && !e->rt_shadow) BBAI_TRY(e->own.alloc({{&e->rt_shadow, (size_t)e->n * CELLS}, {&e->rt_dmask, (size_t)e->n * sizeof(uint64_t)}}));
     e->rt_pixels = pixels;
+    e->rt_ts = e->rt_next_ts;                        // option "render_target_tile_size": the frames are uint8[n][7 ts][7 ts][3], the shadow holds ids of that size's atlas
     e->rt_valid = false; e->rt_filled = 0;
     return BBAI_OK;
 }
@@ -1108,9 +1114,16 @@ int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
 // moved from 10.8 to 11.4 ns between boxes and between two processes on one box, an idle chip puts it elsewhere than the loop does
 // (a first-render tuner), and a perturb-and-observe controller on the launches' own durations paid more for its event pairs and its
 // hovering than it gained.  The one counter's 1.50 ms is the same on all of them: it ships; the gate stays as a knob.
-// Is a render of envs [env_off, env_off + nr) into `pixels` a delta render of the registered target (given a valid shadow)?
-static bool delta_target(const bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
+// Do the `bytes` bytes at `out` overlap the registered buffer (at whatever tile size it was registered: its true length)?
+static bool target_overlaps(const bbai_env* e, const uint8_t* out, int64_t bytes) {
     const uint8_t* const rt = e->rt_pixels;
+    return rt && out < rt + e->n * (int64_t)(OBS_BYTES * e->rt_ts * e->rt_ts) && out + bytes > rt;
+}
+// Is a render of envs [env_off, env_off + nr) into `pixels` a delta render of the registered target (given a valid shadow)?
+// (A target registered at tile size 16 / 32 is bbai_render_view's: to everything that computes with PIX_BYTES -- this test, and through it
+// plan_render's paths, step_dirty and the split halves of bbai_step_render, bbai_rollout with pixels -- there is no target then.)
+static bool delta_target(const bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
+    const uint8_t* const rt = e->rt_ts == TILE ? e->rt_pixels : nullptr;
     const bool on_target = rt && pixels == rt + env_off * (int64_t)PIX_BYTES && env_off >= 0 && env_off + nr <= e->n;
     return on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
 }
@@ -1125,10 +1138,8 @@ struct RenderPlan {
 };
 static RenderPlan plan_render(bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
     RenderPlan p = {RenderPlan::ONESHOT, nullptr, 0, 0};
-    uint8_t* const rt = e->rt_pixels;
-    const int64_t pb = PIX_BYTES;
     const bool delta = delta_target(e, pixels, env_off, nr);
-    if (rt && !delta && pixels < rt + e->n * pb && pixels + nr * pb > rt) { e->rt_valid = false; e->rt_filled = 0; }
+    if (!delta && target_overlaps(e, pixels, nr * (int64_t)PIX_BYTES)) { e->rt_valid = false; e->rt_filled = 0; }
     // the shadow is not valid: the full render writes every byte of the range and, given `shadow`, every tile id of it
     p.shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
     if (p.shadow && env_off == e->rt_filled) e->rt_filled = env_off + nr;        // (recorded before the launch: a failed launch fails the call)
@@ -1356,6 +1367,7 @@ int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = view_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_set_atlas)");
+    if (e->rt_ts == tile_size) { e->rt_valid = false; e->rt_filled = 0; }      // the registered frame was drawn with the old atlas
     return atlas_install(e, __func__, e->view_atlas, e->view_lut, e->view_tiles, k, tile_size, VIEWPX_MAX_TILES, VIEWPX_LUT_BYTES, tiles, n_tiles, lut);
 }
 
@@ -1378,6 +1390,27 @@ static void render_view_launch(bbai_env* e, const uint8_t* image, int64_t rows, 
     hipLaunchKernelGGL((k_view_pixels<TS>), dim3(blocks), dim3(VIEWPX_BLOCK), 0, s, a);
 }
 
+// A whole batch into the registered target of tile size TS (bbai_render_view has checked that this is such a call).  With a valid shadow:
+// k_view_delta, persistent blocks, two per CU, over static groups of 16 / 8 envs.  Without: the frames whole (k_view_pixels, unchanged) and
+// every tile id behind them (k_view_ids).
+template <int TS>
+static void view_delta_launch(bbai_env* e, const uint8_t* image, uint8_t* out, hipStream_t s) {
+    const int k = view_ts_index(TS);
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    if (!e->rt_valid) {
+        render_view_launch<TS>(e, image, e->n, nullptr, e->n, out, s);
+        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((e->n * CELLS + 255) / 256, (int64_t)cus * 8));
+        hipLaunchKernelGGL(k_view_ids, dim3(blocks), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt_shadow);
+        return;
+    }
+    ViewDeltaArgs a;
+    a.image = image; a.n = e->n; a.out = out; a.shadow = e->rt_shadow;
+    a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
+    const int64_t groups = (e->n + ViewDelta<TS>::G - 1) / ViewDelta<TS>::G;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)cus * 2));
+    hipLaunchKernelGGL((k_view_delta<TS>), dim3(blocks), dim3(VIEWDELTA_BLOCK), 0, s, a);
+}
+
 extern "C" {
 
 int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
@@ -1391,12 +1424,27 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
     if (count == 0) return BBAI_OK;
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
+    // The whole batch into the registered target of this tile size: a delta render (or, while the shadow is not valid, the whole frames
+    // with every tile id behind them).  Any other render that writes into the registered buffer leaves a frame the shadow does not
+    // describe -- ids given, a partial count, another tile size, a misaligned target, "render_delta" 0 -- as plan_render has it at 8.
+    const bool target = e->rt_pixels && e->rt_ts == tile_size && out == e->rt_pixels && !ids && count == rows && rows == e->n &&
+                        ((uintptr_t)out % VIEW_PIECE) == 0 && e->render_delta && e->rt_shadow;
+    if (!target && target_overlaps(e, out, count * (int64_t)(OBS_BYTES * tile_size * tile_size))) { e->rt_valid = false; e->rt_filled = 0; }
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s);
-    else render_view_launch<32>(e, image, rows, ids, count, out, s);
+    if (!target) {
+        if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s);
+        else render_view_launch<32>(e, image, rows, ids, count, out, s);
+        HIP_TRY(hipGetLastError());
+        return call.leave();
+    }
+    if (k == 0) view_delta_launch<16>(e, image, out, s);
+    else view_delta_launch<32>(e, image, out, s);
+    e->rt_valid = false; e->rt_filled = 0;               // (a failed launch leaves no shadow to trust)
     HIP_TRY(hipGetLastError());
-    return call.leave();
+    BBAI_TRY(call.leave());
+    e->rt_valid = true;
+    return BBAI_OK;
 }
 
 }  // extern "C"
@@ -2130,6 +2178,7 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     else if (!strcmp(name, "gate_fault_inject")) e->host_flags[0] = v != 0;       // tests: what a timed-out gate leaves behind
     else if (k && !k->read_only) {
         if (k->field == &bbai_env::render_piece_bytes && v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
+        if (k->field == &bbai_env::rt_next_ts && v != 8 && v != 16 && v != 32) ARG_FAIL("render_target_tile_size: 8, 16 or 32");
         e->*k->field = knob_value(*k, v);
         if (k->field == &bbai_env::render_delta) { e->rt_valid = false; e->rt_filled = 0; }
         if (k->field == &bbai_env::gate_probe) { e->n_probed = 0; e->gate_forced = 0; }      // (forget the verdicts: the next window probes again)

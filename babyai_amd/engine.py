@@ -297,9 +297,11 @@ class BatchedBabyAIEnv(object):
                  `image`, `direction`, rewards and dones are computed and kept as without it
     tile_size : the pixel wrappers' tile size, 8, 16 or 32 (anything else with pixel=True: ValueError) -- RGBImgObsWrapper's with
                  full_obs=True, RGBImgPartialObsWrapper's without.  The partial view at 8 is the 56x56 path with its delta render
-                 (9.4 KB per env per frame); at 16 / 32 `pixels` is uint8[N,112,112,3] / [N,224,224,3], every frame is drawn whole
-                 (include/bbai.h bbai_render_view: no delta render at these sizes) and a batch costs 37.6 KB / 150.5 KB per env per
-                 frame -- 65 536 envs at 32 are 9.9 GB
+                 (9.4 KB per env per frame); at 16 / 32 `pixels` is uint8[N,112,112,3] / [N,224,224,3], 37.6 KB / 150.5 KB per env --
+                 65 536 envs at 32 are 9.9 GB -- and is registered as the handle's render target of that size: reset(), step(),
+                 load_state() and reseed() store only the 64-byte pieces of a frame that changed (include/bbai.h bbai_render_view,
+                 option "render_target_tile_size"; set_option("render_delta", 0) draws every frame whole again; after writing into
+                 `pixels` yourself call render_invalidate())
     validate_actions : check every step()'s actions on the device first and raise AssertionError("unknown action") like
                  the reference (gym_minigrid MiniGridEnv.step) instead of treating bytes 8..255 as `done` (include/bbai.h);
                  costs one reduction and a host synchronisation per step, so it is off by default
@@ -352,10 +354,15 @@ class BatchedBabyAIEnv(object):
                 shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
                 self.full = torch.zeros(shape, dtype=torch.uint8, device=self.device)
             elif self.pixel and self.tile_size != 8:
-                # RGBImgPartialObsWrapper(env, 16 | 32): whole frames by bbai_render_view -- no bbai_set_atlas, no registered target
+                # RGBImgPartialObsWrapper(env, 16 | 32): frames by bbai_render_view, no bbai_set_atlas.  self.pixels is registered as the
+                # handle's target of that tile size: _obs()'s whole-batch render into it stores only the 64-byte pieces that changed
+                # (include/bbai.h bbai_set_render_target, option "render_target_tile_size"; a library without the option draws whole frames)
                 ts = self.tile_size
                 self.pixels = torch.zeros((n, 7 * ts, 7 * ts, 3), dtype=torch.uint8, device=self.device)
                 self._install_atlas("view", ts)
+                if self._has_option("render_target_tile_size"):
+                    self.set_option("render_target_tile_size", ts)
+                    _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
             elif self.pixel:
                 self.pixels = torch.zeros((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
                 self._install_atlas("view", 8)
@@ -590,7 +597,7 @@ class BatchedBabyAIEnv(object):
     def render_shadow(self):
         """The tile ids of the frame the registered buffer holds, uint8[N][49] (include/bbai.h bbai_render_shadow)."""
         import torch
-        out = torch.empty((self.num_envs, 49), dtype=torch.uint8, device=self.pixels.device)
+        out = torch.empty((self.num_envs, 49), dtype=torch.uint8, device=self.device)      # (a target a caller registered itself: there may be no self.pixels)
         _check(self.lib, self.lib.bbai_render_shadow(self.handle, out.data_ptr(), self._stream()), "bbai_render_shadow")
         return out
 
@@ -972,6 +979,11 @@ class BatchedBabyAIEnv(object):
         v = ctypes.c_int64(0)
         _check(self.lib, self.lib.bbai_get_option(self.handle, name.encode(), ctypes.byref(v)), "bbai_get_option(%s)" % name)
         return int(v.value)
+
+    def _has_option(self, name):
+        """Does the loaded library know option `name` (an older experiment build, BBAI_ENGINE_LIB, may not)."""
+        v = ctypes.c_int64(0)
+        return self.lib.bbai_get_option(self.handle, name.encode(), ctypes.byref(v)) == 0
 
     def profile(self, enable=True):
         """Bracket every k_step / k_consume / k_render launch with HIP events on its launch stream (bench.py)."""

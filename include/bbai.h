@@ -122,7 +122,13 @@ int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_d
  * option "render_delta" was set writes every byte.  Renders into any other buffer are full renders and leave the history alone;
  * a full render into the registered buffer by another path (render_delta 0, a buffer not 128-byte aligned) invalidates it.
  * A caller that writes into the registered buffer itself calls bbai_render_invalidate before the next render.  Register the
- * buffer again when it is reallocated: a freed buffer's address may be handed out again with other contents. */
+ * buffer again when it is reallocated: a freed buffer's address may be handed out again with other contents.
+ * Option "render_target_tile_size" (8 by default; 16 or 32) states the frame size of the NEXT registration: uint8[N][7 ts][7 ts][3].  A
+ * handle has one target at a time; registering replaces it and invalidates the history.  A target of 16 / 32 is bbai_render_view's (below):
+ * the tile ids are those of that size's view atlas, bbai_set_view_atlas of that size invalidates (bbai_set_atlas does not), and
+ * bbai_render, bbai_step_render and bbai_rollout treat the handle as one without a target -- but for this: whatever they, or any other
+ * render of the handle, write into the registered buffer's bytes invalidates its history.  bbai_render_shadow, bbai_render_invalidate and
+ * the options "render_delta" / "render_delta_valid" work alike at every size. */
 int bbai_set_render_target(bbai_env* env, uint8_t* pixels_dev);
 int bbai_render_invalidate(bbai_env* env);
 /* A copy of the registered buffer's tile ids, uint8[N][49] (cell = 7 x + y of the encoded view), into a device buffer, on `stream`:
@@ -149,7 +155,7 @@ int bbai_render_grid(bbai_env* env, int tile_size, int highlight, const int64_t*
 
 /* The agent's 7x7 view as pixels at tile sizes 16 and 32: RGBImgPartialObsWrapper(env, tile_size).observation (gym_minigrid
  * wrappers.py; scripts/manual_control.py --agent_view, and 7 x 32 = 224 / 7 x 16 = 112 pixel inputs of image models).  Tile size 8 is
- * bbai_set_atlas / bbai_render (and the delta render); there is no delta render at these sizes.
+ * bbai_set_atlas / bbai_render (and its delta render); the delta render at these sizes is the last paragraph.
  * bbai_set_view_atlas installs the tile atlas of one tile size (babyai_amd/data/tile_atlas_ts<size>.npz, made by tools/gen_atlas.py
  * --tile-size): tiles uint8[n_tiles][ts][ts][3], n_tiles <= 64, and lut[agent cell][key] as bbai_set_atlas takes it (row 0 = ordinary
  * view cell, row 1 = the agent's cell (3, 6); key = type | colour << 3 | state << 6, taken & 255); synchronous.  A handle keeps the atlas
@@ -160,7 +166,15 @@ int bbai_render_grid(bbai_env* env, int tile_size, int highlight, const int64_t*
  * view x][rgb] -- 37 632 bytes a frame at 16, 150 528 at 32.  It writes nothing but out_dev; asynchronous on `stream`, ordered like
  * every other call of the handle.  An id outside [0, rows) yields an all-zero frame, never an out-of-bounds read.  BBAI_ERR_STATE
  * without an atlas of that tile size; BBAI_ERR_ARG for a tile size other than 16 / 32, count < 0, count > rows without ids, or a
- * missing / misaligned out_dev. */
+ * missing / misaligned out_dev.
+ * Delta render: a call that draws the WHOLE batch into the target registered at this tile size (bbai_set_render_target under option
+ * "render_target_tile_size": out_dev = the registered pointer, 64-byte aligned, ids_dev = NULL, count = rows = n_envs, option
+ * "render_delta" not 0) stores only the 64-byte pieces of each frame that show a cell whose atlas tile changed since the frame the buffer
+ * holds, and brings the tile ids up to date -- the same bytes in the buffer as a whole render's, a fraction of the stores.  The first such
+ * call after a registration, bbai_set_view_atlas of this size, bbai_render_invalidate, a set of "render_delta" or a failed launch draws the
+ * frames whole and writes every tile id.  Every other bbai_render_view whose output range overlaps the registered buffer (ids given, a
+ * partial count, another tile size, a misaligned target, "render_delta" 0) draws whole frames and invalidates the history; one that
+ * writes elsewhere leaves it alone. */
 int bbai_set_view_atlas(bbai_env* env, int tile_size, const uint8_t* tiles_host, int n_tiles, const uint8_t* lut_host /* [2][256] */);
 int bbai_render_view(bbai_env* env, int tile_size, const uint8_t* image_dev /* [rows][147] */, int64_t rows,
                      const int64_t* ids_dev /* NULL = rows 0..count-1 */, int64_t count, uint8_t* out_dev /* [count][7*ts][7*ts][3] */,
@@ -469,6 +483,8 @@ int bbai_get_done_actions(bbai_env* env);
  *   "render_group", "render_tpb"   envs / threads per one-shot render block (0 = by batch size)
  *   "render_delta"      1 (default; BBAI_RENDER_DELTA) = renders into the registered target store only changed lines
  *                       (bbai_set_render_target), 0 = full renders everywhere; setting it invalidates the target's history
+ *   "render_target_tile_size"   8 (default), 16 or 32 (anything else: BBAI_ERR_ARG): the frame size of the NEXT bbai_set_render_target
+ *                       registration, uint8[N][7 ts][7 ts][3] -- at 16 / 32 the target is bbai_render_view's
  *   "render_delta_sched", "render_delta_tpb", "render_delta_bpc"   the delta render's work split (0 = interleaved groups per
  *                       block, 1 = contiguous ranges), threads per block (512 default / 1024) and blocks per CU (0 = 3 of 512
  *                       threads, 1 of 1024)
