@@ -40,6 +40,7 @@ __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase
 #endif
 #include "../../include/bbai.h"
 #include "bbai_types.hpp"
+#include "bbai_target.hpp"
 #include "bbai_kernels.hpp"
 #include "bbai_gen.hpp"
 #include "bbai_genl.hpp"
@@ -265,17 +266,12 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int render_pace;      // (experiment) 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
                           // one counter serves them
     // delta rendering (bbai_set_render_target): the registered buffer, and the atlas tile ids of the frame it holds
-    uint8_t* rt_pixels;   // the registered caller-owned uint8[n][7 rt_ts][7 rt_ts][3] buffer (NULL: none); only this handle's renders write there
-    int rt_ts;            // the tile size of that registration: 8 (bbai_render's delta render), 16 / 32 (bbai_render_view's: k_view_delta)
+    RenderTarget rt;      // (bbai_target.hpp: the record, and the planner every render asks)
     int rt_next_ts;       // "render_target_tile_size": the tile size the NEXT bbai_set_render_target registers (8, default)
-    uint8_t* rt_shadow;   // [n][49] tile id of every cell of the frame in rt_pixels, in the atlas of rt_ts (allocated at the first registration)
-    bool rt_valid;        // rt_shadow describes rt_pixels; false after registration / bbai_set_atlas / bbai_render_invalidate / a full render into it
-    int64_t rt_filled;    // while not valid: envs [0, rt_filled) rewritten by full renders with shadow ids since (a split render's halves)
     int render_delta;     // 1 (default) = renders into the registered buffer store only changed lines
     int render_delta_sched;    // 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
     int render_delta_tpb;      // 512 (default, also for 0) or 1024 threads per delta render block
     int render_delta_bpc;      // delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
-    uint64_t* rt_dmask;   // [n] the dirty-cell mask of every env, left by k_step for the store-only render (k_render_dstore); allocated with rt_shadow
     int render_piece_bytes;    // the delta render's store unit, 64-byte pieces (default) or 128 (whole lines)
     int render_delta_from_step;   // 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
@@ -617,7 +613,6 @@ static int create_finish(bbai_env* e) {
         e->*k.field = kv ? knob_value(k, atoi(kv)) : k.def;
     }
     if (!e->mtt) e->lane_blocks = 0;        // (no lane generator on this handle)
-    e->rt_ts = TILE;
     return BBAI_OK;
 }
 
@@ -962,7 +957,7 @@ static int step_kernel(bbai_env* e, const StepPlan& p, const StepIO& io, hipStre
     a.rewards = io.rewards; a.rewards64 = io.rewards64; a.dones = io.dones; a.auto_reset = io.auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
     a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = io.enum_done; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
     a.tap = p.tap; a.ticks = ticks;
-    a.dshadow = p.dirty && ticks == 1 ? e->rt_shadow : nullptr; a.dmask = e->rt_dmask; a.lut = e->lut;
+    a.dshadow = p.dirty && ticks == 1 ? e->rt.shadow : nullptr; a.dmask = e->rt.dmask; a.lut = e->lut;
 #define STEP_LAUNCH(VV, FF, CC) do { if (ticks > 1) hipLaunchKernelGGL((k_step_ticks<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); \
                                      else hipLaunchKernelGGL((k_step<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); } while (0)
     if (e->inplace && e->cplane) STEP_LAUNCH(false, 3, true);
@@ -1072,7 +1067,7 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
     HIP_TRY(hipMemcpy(e->atlas, tiles, (size_t)n_tiles * TILE_BYTES, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->lut, lut, 512, hipMemcpyHostToDevice));
     e->n_tiles = n_tiles;
-    if (e->rt_ts == TILE) { e->rt_valid = false; e->rt_filled = 0; }      // the registered frame was drawn with the old atlas (a 16 / 32 target: bbai_set_view_atlas)
+    target_atlas_replaced(e->rt, TILE);      // (a 16 / 32 target: bbai_set_view_atlas)
     return BBAI_OK;
 }
 
@@ -1080,27 +1075,26 @@ int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
     if (!e) ARG_FAIL("null handle");
     ON_DEVICE(e->device);
     // the first registration: the shadow and the dirty masks, both or neither (un-registering keeps them)
-    if (pixels && !e->rt_shadow) BBAI_TRY(e->own.alloc({{&e->rt_shadow, (size_t)e->n * CELLS}, {&e->rt_dmask, (size_t)e->n * sizeof(uint64_t)}}));
-    e->rt_pixels = pixels;
-    e->rt_ts = e->rt_next_ts;                        // option "render_target_tile_size": the frames are uint8[n][7 ts][7 ts][3], the shadow holds ids of that size's atlas
-    e->rt_valid = false; e->rt_filled = 0;
+    if (pixels && !e->rt.shadow) BBAI_TRY(e->own.alloc({{&e->rt.shadow, (size_t)e->n * CELLS}, {&e->rt.dmask, (size_t)e->n * sizeof(uint64_t)}}));
+    // option "render_target_tile_size": the frames are uint8[n][7 ts][7 ts][3], the shadow holds ids of that size's atlas
+    register_target(e->rt, (uintptr_t)pixels, e->rt_next_ts, e->n);
     return BBAI_OK;
 }
 
 int bbai_render_invalidate(bbai_env* e) {
     if (!e) ARG_FAIL("null handle");
-    e->rt_valid = false; e->rt_filled = 0;
+    invalidate_target(e->rt);
     return BBAI_OK;
 }
 
 int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
     if (!e || !out) ARG_FAIL("null handle or buffer");
-    if (!e->rt_shadow) { snprintf(g_err, sizeof(g_err), "render_shadow before bbai_set_render_target"); return BBAI_ERR_STATE; }
+    if (!e->rt.shadow) { snprintf(g_err, sizeof(g_err), "render_shadow before bbai_set_render_target"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    HIP_TRY(hipMemcpyAsync(out, e->rt_shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out, e->rt.shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
     return call.leave();
 }
 
@@ -1114,46 +1108,20 @@ int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
 // moved from 10.8 to 11.4 ns between boxes and between two processes on one box, an idle chip puts it elsewhere than the loop does
 // (a first-render tuner), and a perturb-and-observe controller on the launches' own durations paid more for its event pairs and its
 // hovering than it gained.  The one counter's 1.50 ms is the same on all of them: it ships; the gate stays as a knob.
-// Do the `bytes` bytes at `out` overlap the registered buffer (at whatever tile size it was registered: its true length)?
-static bool target_overlaps(const bbai_env* e, const uint8_t* out, int64_t bytes) {
-    const uint8_t* const rt = e->rt_pixels;
-    return rt && out < rt + e->n * (int64_t)(OBS_BYTES * e->rt_ts * e->rt_ts) && out + bytes > rt;
-}
-// Is a render of envs [env_off, env_off + nr) into `pixels` a delta render of the registered target (given a valid shadow)?
-// (A target registered at tile size 16 / 32 is bbai_render_view's: to everything that computes with PIX_BYTES -- this test, and through it
-// plan_render's paths, step_dirty and the split halves of bbai_step_render, bbai_rollout with pixels -- there is no target then.)
-static bool delta_target(const bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
-    const uint8_t* const rt = e->rt_ts == TILE ? e->rt_pixels : nullptr;
-    const bool on_target = rt && pixels == rt + env_off * (int64_t)PIX_BYTES && env_off >= 0 && env_off + nr <= e->n;
-    return on_target && e->render_delta && e->rt_shadow && ((uintptr_t)rt % LINE_BYTES) == 0 && env_off % DELTA_UNIT == 0;
-}
-// What a render of envs [env_off, env_off + nr) into `pixels` means for the registered target (bbai_set_render_target), and the path it takes.
-// Envs of the target are rendered by the delta render, which stores only what changed -- or, while the shadow is not valid, by the full
-// render, which then also writes every tile id (`shadow`).  Any other render that writes into the registered buffer leaves a frame the
-// shadow does not describe: it is invalidated.  A render elsewhere leaves it alone.
+static_assert(TARGET_ALIGN_8 == LINE_BYTES && TARGET_UNIT_8 == DELTA_UNIT && TARGET_ALIGN_VIEW == VIEW_PIECE, "bbai_target.hpp restates the delta kernels' store units");
+// The full render (what the target's planner, bbai_target.hpp, does not send to the delta render): the queue (queue > 0) or one-shot blocks.
 struct RenderPlan {
-    enum Path { DELTA, QUEUE, ONESHOT } path;
-    uint8_t* shadow;      // full render (QUEUE / ONESHOT) of target envs whose shadow is not valid: their rows of it, else NULL
-    int queue, pace;      // QUEUE: the queue shape (launch_render_queue) and the option "render_pace"
+    uint8_t* shadow;      // a FILL of target envs: their rows of the shadow, where the render also writes every tile id; else NULL
+    int queue, pace;      // the queue shape (launch_render_queue; 0: one-shot blocks) and the option "render_pace"
 };
-static RenderPlan plan_render(bbai_env* e, const uint8_t* pixels, int64_t env_off, int64_t nr) {
-    RenderPlan p = {RenderPlan::ONESHOT, nullptr, 0, 0};
-    const bool delta = delta_target(e, pixels, env_off, nr);
-    if (!delta && target_overlaps(e, pixels, nr * (int64_t)PIX_BYTES)) { e->rt_valid = false; e->rt_filled = 0; }
-    // the shadow is not valid: the full render writes every byte of the range and, given `shadow`, every tile id of it
-    p.shadow = delta && !e->rt_valid ? e->rt_shadow + env_off * CELLS : nullptr;
-    if (p.shadow && env_off == e->rt_filled) e->rt_filled = env_off + nr;        // (recorded before the launch: a failed launch fails the call)
-    if (p.shadow && e->rt_filled >= e->n) e->rt_valid = true;
-    if (delta && !p.shadow) { p.path = RenderPlan::DELTA; return p; }
+static RenderPlan plan_render(const bbai_env* e, uint8_t* shadow) {
     // BBAI_RENDER_QUEUE / option "render_queue": -1 = by batch size (default), 0 = never, m > 0 = queue shape m (launch_render_queue).
-    p.queue = e->render_queue;
-    p.pace = e->render_pace;
+    RenderPlan p = {shadow, e->render_queue, e->render_pace};
     if (p.queue < 0) {
         p.queue = e->n >= RENDER_QUEUE_MIN_ENVS ? RENDER_QUEUE_DEFAULT : 0;
         if (p.queue == RENDER_QUEUE_DEFAULT && p.pace > 0) p.queue = RENDER_QUEUE_PACED;        // (a pace needs tickets served faster than it admits them: two counters)
     }
     if (p.pace < 0) p.pace = 0;
-    if (p.queue > 0) p.path = RenderPlan::QUEUE;
     return p;
 }
 
@@ -1176,7 +1144,7 @@ static void launch_delta_t(const bbai_env* e, const RenderRange& r, unsigned blo
 }
 template <int P>
 static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
-    hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->rt_dmask + r.env_off, e->atlas, e->n_tiles);
+    hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles);
 }
 static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool from_step) {
     const int cus = e->n_cus > 0 ? e->n_cus : 256;
@@ -1185,7 +1153,7 @@ static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool fr
     const int64_t groups = (r.nr + G - 1) / G;
     const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
-    uint8_t* sh = e->rt_shadow + r.env_off * CELLS;
+    uint8_t* sh = e->rt.shadow + r.env_off * CELLS;
     if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
     else if (T == 512) launch_delta_t<512>(e, r, blocks, sh);
     else launch_delta_t<1024>(e, r, blocks, sh);
@@ -1254,18 +1222,19 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
     CallScope call(e, (hipStream_t)stream);
     BBAI_TRY(call.rc);
     const RenderRange r = {input, pixels, n_render < 0 ? e->n : n_render, env_off, (hipStream_t)stream};
+    // plan, launch, commit (bbai_target.hpp): envs of the target go to the delta render or, while the shadow is not valid, to the full
+    // render, which then also writes every tile id
+    const TargetPlan tp = plan_target(e->rt, RenderRequest{TILE, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES, env_off, r.nr, false, e->render_delta != 0});
     {
     ProfScope prof_(e, 2, r.stream);
-    const RenderPlan p = plan_render(e, pixels, env_off, r.nr);
-    if (p.path != RenderPlan::ONESHOT) {
-        if (p.path == RenderPlan::DELTA) launch_render_delta(e, r, from_step); else launch_render_queue(e, r, p);
-        HIP_TRY(hipGetLastError());
-        return call.leave();
+    const RenderPlan p = plan_render(e, tp.kind == TargetPlan::FILL ? e->rt.shadow + tp.shadow_off : nullptr);
+    if (tp.kind == TargetPlan::DELTA) launch_render_delta(e, r, from_step);
+    else if (p.queue > 0) launch_render_queue(e, r, p);
+    else launch_render_oneshot(e, r, p.shadow);
     }
-    launch_render_oneshot(e, r, p.shadow);
-    }
-    HIP_TRY(hipGetLastError());
-    return call.leave();
+    const int rc = [&]() -> int { HIP_TRY(hipGetLastError()); return call.leave(); }();
+    commit_target(e->rt, tp, rc == BBAI_OK);
+    return rc;
 }
 
 extern "C" {
@@ -1367,7 +1336,7 @@ int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = view_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_set_atlas)");
-    if (e->rt_ts == tile_size) { e->rt_valid = false; e->rt_filled = 0; }      // the registered frame was drawn with the old atlas
+    target_atlas_replaced(e->rt, tile_size);
     return atlas_install(e, __func__, e->view_atlas, e->view_lut, e->view_tiles, k, tile_size, VIEWPX_MAX_TILES, VIEWPX_LUT_BYTES, tiles, n_tiles, lut);
 }
 
@@ -1390,21 +1359,21 @@ static void render_view_launch(bbai_env* e, const uint8_t* image, int64_t rows, 
     hipLaunchKernelGGL((k_view_pixels<TS>), dim3(blocks), dim3(VIEWPX_BLOCK), 0, s, a);
 }
 
-// A whole batch into the registered target of tile size TS (bbai_render_view has checked that this is such a call).  With a valid shadow:
-// k_view_delta, persistent blocks, two per CU, over static groups of 16 / 8 envs.  Without: the frames whole (k_view_pixels, unchanged) and
-// every tile id behind them (k_view_ids).
+// A whole batch into the registered target of tile size TS (the planner has said that this is such a call).  DELTA: k_view_delta, persistent
+// blocks, two per CU, over static groups of 16 / 8 envs.  FILL: the frames whole (k_view_pixels, unchanged) and every tile id behind them
+// (k_view_ids).
 template <int TS>
-static void view_delta_launch(bbai_env* e, const uint8_t* image, uint8_t* out, hipStream_t s) {
+static void view_delta_launch(bbai_env* e, bool fill, const uint8_t* image, uint8_t* out, hipStream_t s) {
     const int k = view_ts_index(TS);
     const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    if (!e->rt_valid) {
+    if (fill) {
         render_view_launch<TS>(e, image, e->n, nullptr, e->n, out, s);
         const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((e->n * CELLS + 255) / 256, (int64_t)cus * 8));
-        hipLaunchKernelGGL(k_view_ids, dim3(blocks), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt_shadow);
+        hipLaunchKernelGGL(k_view_ids, dim3(blocks), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt.shadow);
         return;
     }
     ViewDeltaArgs a;
-    a.image = image; a.n = e->n; a.out = out; a.shadow = e->rt_shadow;
+    a.image = image; a.n = e->n; a.out = out; a.shadow = e->rt.shadow;
     a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
     const int64_t groups = (e->n + ViewDelta<TS>::G - 1) / ViewDelta<TS>::G;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)cus * 2));
@@ -1424,27 +1393,22 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
     if (count == 0) return BBAI_OK;
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
-    // The whole batch into the registered target of this tile size: a delta render (or, while the shadow is not valid, the whole frames
-    // with every tile id behind them).  Any other render that writes into the registered buffer leaves a frame the shadow does not
-    // describe -- ids given, a partial count, another tile size, a misaligned target, "render_delta" 0 -- as plan_render has it at 8.
-    const bool target = e->rt_pixels && e->rt_ts == tile_size && out == e->rt_pixels && !ids && count == rows && rows == e->n &&
-                        ((uintptr_t)out % VIEW_PIECE) == 0 && e->render_delta && e->rt_shadow;
-    if (!target && target_overlaps(e, out, count * (int64_t)(OBS_BYTES * tile_size * tile_size))) { e->rt_valid = false; e->rt_filled = 0; }
+    // plan, launch, commit (bbai_target.hpp): the whole batch into the target registered at this tile size is a delta render (or, while
+    // the shadow is not valid, the whole frames with every tile id behind them); anything else -- ids given, a partial count, another
+    // tile size, a misaligned target, "render_delta" 0 -- draws whole frames, and invalidates where it writes into the registered buffer
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    if (!target) {
-        if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s);
-        else render_view_launch<32>(e, image, rows, ids, count, out, s);
+    const TargetPlan tp = plan_target(e->rt, RenderRequest{tile_size, (uintptr_t)out, count * (int64_t)(OBS_BYTES * tile_size * tile_size), 0, count,
+                                                           ids || count != rows || rows != e->n, e->render_delta != 0});
+    const int rc = [&]() -> int {
+        if (tp.kind == TargetPlan::ELSEWHERE) { if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s); else render_view_launch<32>(e, image, rows, ids, count, out, s); }
+        else if (k == 0) view_delta_launch<16>(e, tp.kind == TargetPlan::FILL, image, out, s);
+        else view_delta_launch<32>(e, tp.kind == TargetPlan::FILL, image, out, s);
         HIP_TRY(hipGetLastError());
         return call.leave();
-    }
-    if (k == 0) view_delta_launch<16>(e, image, out, s);
-    else view_delta_launch<32>(e, image, out, s);
-    e->rt_valid = false; e->rt_filled = 0;               // (a failed launch leaves no shadow to trust)
-    HIP_TRY(hipGetLastError());
-    BBAI_TRY(call.leave());
-    e->rt_valid = true;
-    return BBAI_OK;
+    }();
+    commit_target(e->rt, tp, rc == BBAI_OK);
+    return rc;
 }
 
 }  // extern "C"
@@ -1540,7 +1504,7 @@ static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, h
         // cells and updates the shadow (step_dirty), the render only stores (k_render_dstore).  From the step kernel on, the shadow is ahead
         // of the frame until the render has been launched: a failure in between invalidates it (step_render_launch).
         const bool from_step = e->render_delta_from_step < 0 ? e->n >= RENDER_FROM_STEP_MIN_ENVS : e->render_delta_from_step != 0;
-        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !io.auto_reset) && delta_target(e, pixels, 0, e->n) && e->rt_valid;
+        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !io.auto_reset) && whole_batch_delta(e->rt, (uintptr_t)pixels, e->render_delta != 0);
         const int want = e->step_render_split < 0 ? (STEP_RENDER_SPLIT_DEFAULT && e->n >= STEP_RENDER_SPLIT_MIN) : e->step_render_split;      // (an explicit 1: any size)
         const int64_t nb = step_blocks(e), hb = nb / 2;
         const bool split = want && pixels && (p.fused || !io.auto_reset) && hb > 0;
@@ -1572,7 +1536,7 @@ static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, h
 static int step_render_launch(bbai_env* e, const StepIO& io, uint8_t* pixels, hipStream_t s) {
     bool dirty = false;
     const int rc = step_render_launch_(e, io, pixels, s, dirty);
-    if (rc != BBAI_OK && dirty) { e->rt_valid = false; e->rt_filled = 0; }
+    if (rc != BBAI_OK && dirty) invalidate_target(e->rt);       // (a failure before the render's own plan: its commit was never reached)
     return rc;
 }
 
@@ -2180,7 +2144,7 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
         if (k->field == &bbai_env::render_piece_bytes && v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
         if (k->field == &bbai_env::rt_next_ts && v != 8 && v != 16 && v != 32) ARG_FAIL("render_target_tile_size: 8, 16 or 32");
         e->*k->field = knob_value(*k, v);
-        if (k->field == &bbai_env::render_delta) { e->rt_valid = false; e->rt_filled = 0; }
+        if (k->field == &bbai_env::render_delta) invalidate_target(e->rt);
         if (k->field == &bbai_env::gate_probe) { e->n_probed = 0; e->gate_forced = 0; }      // (forget the verdicts: the next window probes again)
     }
     else {
@@ -2200,7 +2164,7 @@ static int read_flow(bbai_env* e, int word, unsigned long long* out) {
 int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     if (!e || !name || !out) ARG_FAIL("null handle, name or output");
     if (const Knob* k = find_knob(name)) *out = e->*k->field;
-    else if (!strcmp(name, "render_delta_valid")) *out = e->rt_valid ? 1 : 0;
+    else if (!strcmp(name, "render_delta_valid")) *out = e->rt.valid ? 1 : 0;
     else if (!strcmp(name, "gate_fault")) *out = e->host_flags ? (int64_t)e->host_flags[0] : 0;     // sticky; no synchronisation
     else if (!strcmp(name, "profile_step_ticks")) *out = e->prof_step_ticks;
     else if (!strcmp(name, "cplane")) *out = e->cplane ? 1 : 0;

@@ -353,21 +353,17 @@ class BatchedBabyAIEnv(object):
                 c, ts = self.cfg, self.tile_size
                 shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
                 self.full = torch.zeros(shape, dtype=torch.uint8, device=self.device)
-            elif self.pixel and self.tile_size != 8:
-                # RGBImgPartialObsWrapper(env, 16 | 32): frames by bbai_render_view, no bbai_set_atlas.  self.pixels is registered as the
-                # handle's target of that tile size: _obs()'s whole-batch render into it stores only the 64-byte pieces that changed
-                # (include/bbai.h bbai_set_render_target, option "render_target_tile_size"; a library without the option draws whole frames)
+            elif self.pixel:
+                # RGBImgPartialObsWrapper(env, ts): frames by bbai_render at 8, by bbai_render_view at 16 / 32.  self.pixels is registered as
+                # the handle's target of that tile size: whole-batch renders into it store only the pieces that changed (include/bbai.h
+                # bbai_set_render_target, option "render_target_tile_size"; a library without the entry -- at 16 / 32: without the option --
+                # draws whole frames)
                 ts = self.tile_size
                 self.pixels = torch.zeros((n, 7 * ts, 7 * ts, 3), dtype=torch.uint8, device=self.device)
                 self._install_atlas("view", ts)
-                if self._has_option("render_target_tile_size"):
-                    self.set_option("render_target_tile_size", ts)
-                    _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
-            elif self.pixel:
-                self.pixels = torch.zeros((n, PIX, PIX, 3), dtype=torch.uint8, device=self.device)
-                self._install_atlas("view", 8)
-                # renders into self.pixels store only the lines that changed (include/bbai.h bbai_set_render_target)
-                if hasattr(self.lib, "bbai_set_render_target"):
+                if hasattr(self.lib, "bbai_set_render_target") and (ts == 8 or self._has_option("render_target_tile_size")):
+                    if ts != 8:
+                        self.set_option("render_target_tile_size", ts)
                     _check(self.lib, self.lib.bbai_set_render_target(self.handle, self.pixels.data_ptr()), "bbai_set_render_target")
         # (the five output tensors are never replaced: their pointers are taken once, see _step_out)
         self._out_ptrs = tuple(t.data_ptr() for t in (self.image, self.direction, self.reward, self.reward64, self.done))
@@ -417,17 +413,10 @@ class BatchedBabyAIEnv(object):
             img = self.full
         elif self.pixel and rendered:
             img = self.pixels
-        elif self.pixel and self.tile_size != 8:
-            ev = self._ev_begin()
-            self._render_view_into(self.image, None, self.num_envs, self.tile_size, self.pixels)
-            self._ev_end("render", ev)
-            img = self.pixels
         elif self.pixel:
             ev = self._ev_begin()
-            _check(self.lib, self.lib.bbai_render(self.handle, self.image.data_ptr(), self.pixels.data_ptr(),
-                                                   self._stream()), "bbai_render")
+            img = self._render_batch_into(self.image, self.tile_size, self.pixels)
             self._ev_end("render", ev)
-            img = self.pixels
         return self._obs_dict(img)
 
     def _moved_on(self):
@@ -460,9 +449,7 @@ class BatchedBabyAIEnv(object):
                 out = self.pixels
             out = self._frames_out(out, (k, 7 * ts, 7 * ts, 3))
             return self._render_view_into(image, None, k, ts, out)
-        out = self.pixels if out is None else out
-        _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
-        return out
+        return self._render_batch_into(image, 8, self.pixels if out is None else out)
 
     def _install_atlas(self, picture, ts):
         """The tile atlas of `picture` at tile size ts on the handle, on first use: "view" = the agent's 7x7 view (8: bbai_render's 56x56 atlas;
@@ -487,6 +474,13 @@ class BatchedBabyAIEnv(object):
         self._install_atlas("view", ts)
         _check(self.lib, self.lib.bbai_render_view(self.handle, ts, image.data_ptr(), image.numel() // OBS_BYTES, ids_ptr, k,
                                                     out.data_ptr() if k else None, self._stream()), "bbai_render_view")
+        return out
+
+    def _render_batch_into(self, image, ts, out):
+        """num_envs encoded rows -> num_envs frames of tile size ts: bbai_render at 8, bbai_render_view at 16 / 32."""
+        if ts != 8:
+            return self._render_view_into(image, None, self.num_envs, ts, out)
+        _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
         return out
 
     def render_view(self, ids=None, tile_size=None, out=None):
@@ -682,7 +676,7 @@ class BatchedBabyAIEnv(object):
                                                 self.pixels.data_ptr() if self.pixels is not None and not big else None, ctypes.byref(log) if log is not None else None,
                                                 self._stream()), "bbai_rollout")
         if big:
-            self._render_view_into(self.image, None, self.num_envs, self.tile_size, self.pixels)
+            self._render_batch_into(self.image, self.tile_size, self.pixels)
         if self.full_obs:
             self.observe_full()          # the last step's full observation (the tap log keeps its 7x7 rows)
         return self._obs_dict(self.full if self.full_obs else self.pixels if self.pixel else self.image)

@@ -118,8 +118,8 @@ int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_d
  * (49 bytes per env, allocated at the first registration), and a render into the buffer -- bbai_render, bbai_step_render (split
  * or not), bbai_rollout with pixels -- stores only the 128-byte lines whose cells changed since the frame before: same bytes, a
  * fraction of the stores (how large a fraction depends on the actions: turns redraw most of the view, blocked moves and object
- * actions almost nothing).  The first render after registration, after bbai_set_atlas, after bbai_render_invalidate and after
- * option "render_delta" was set writes every byte.  Renders into any other buffer are full renders and leave the history alone;
+ * actions almost nothing).  The first render after registration, after bbai_set_atlas, after bbai_render_invalidate, after
+ * option "render_delta" was set and after a failed launch writes every byte.  Renders into any other buffer are full renders and leave the history alone;
  * a full render into the registered buffer by another path (render_delta 0, a buffer not 128-byte aligned) invalidates it.
  * A caller that writes into the registered buffer itself calls bbai_render_invalidate before the next render.  Register the
  * buffer again when it is reallocated: a freed buffer's address may be handed out again with other contents.

@@ -374,3 +374,27 @@ def test_the_tile_size_8_planner_leaves_a_16_target_alone(gpu):
     env.render_encoding(out=target, tile_size=ts)
     assert valid(env) == 1
     assert np.array_equal(target.cpu().numpy(), view_frames(env.image.cpu().numpy(), *load_atlas(ts), ts))
+
+
+@pytest.mark.gpu
+def test_a_tile_size_16_render_into_an_8_target_drops_its_shadow(gpu):
+    """The mirror: a frame at 16 written into the head of the buffer registered at 8 (16 x 9408 B: room for four such frames)."""
+    import torch
+    n = 16
+    env = make_env(gpu, ROOM, n, seeds=5, pixel=True)
+    env.reset()
+    rng = np.random.RandomState(4)
+    env.step(torch.as_tensor(rng.randint(0, 7, size=n).astype(np.uint8), device=gpu))
+    assert valid(env) == 1
+    F = frame_bytes(16)
+    assert F == 37632 and F <= n * ru.PIX_BYTES
+    head = env.pixels.view(-1)[:F].view(1, 112, 112, 3)
+    enc = env.image[:1].contiguous()
+    env.render_encoding(enc, out=head, tile_size=16)
+    torch.cuda.synchronize()
+    assert np.array_equal(head.cpu().numpy(), view_frames(enc.cpu().numpy(), *load_atlas(16), 16))
+    assert valid(env) == 0
+    env.step(torch.as_tensor(rng.randint(0, 7, size=n).astype(np.uint8), device=gpu))
+    torch.cuda.synchronize()
+    assert np.array_equal(env.pixels.cpu().numpy(), ru.frames(ru.tile_ids(env.image.cpu().numpy())))
+    assert valid(env) == 1
