@@ -277,6 +277,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int n_cus;            // compute units of the device
     int done_action_enum; // done-action mode only -- bbai_step's `done` actions count as the enum member (verifier.py:543-545)
     int reseed_levels;    // "reseed_levels": levels of the new stream a bbai_reseed generates per listed env (0 = the whole ring); the env parks behind them
+    int step_hold;        // "step_hold": action byte BBAI_ACTION_HOLD means "this env sits the step out" under bbai_step / _render / _full / _tapped / bbai_rollout (0: it is `done`, as 8..255 are)
     int consume_fused;    // -1 = by batch size, 0 = k_consume launch, 1 = inside k_step
     int inplace;          // BBAI_INPLACE: the in-place layout (live_slot, bbai_kernels.hpp): an env's live record IS the look-ahead slot its episode was generated into
     uint8_t* atlas;       // [n_tiles][192]
@@ -512,7 +513,7 @@ int bbai_create(const bbai_level_cfg* cfg, int64_t n_envs, int device, bbai_env*
 // The performance knobs (include/bbai.h: bbai_set_option), one row each: the option's name, the BBAI_* variable bbai_create reads (or none), the
 // field, the default, and how a raw value -- from the variable or from bbai_set_option alike -- becomes the stored one.  The read-only rows
 // at the end are looked up by bbai_get_option alone (their fields are set elsewhere).  Never semantics: every setting produces the same bytes --
-// but for the two semantic switches that ride in this table because the C surface is closed: "done_action_enum" and "reseed_levels".
+// but for the three semantic switches that ride in this table because the C surface is closed: "done_action_enum", "reseed_levels" and "step_hold".
 enum KnobNorm { AS_IS, FLAG /* v != 0 */, AT_LEAST /* max(lo, v) */, TRI /* v < 0: -1, else v != 0 */ };
 struct Knob { const char* name; const char* var; int bbai_env::*field; int def; KnobNorm norm; int lo; bool read_only; };
 static const Knob KNOBS[] = {
@@ -546,8 +547,9 @@ static const Knob KNOBS[] = {
     {"bot_group", "BBAI_BOT_GROUP", &bbai_env::bot_group, 0},
     {"step_render_split", "BBAI_STEP_RENDER_SPLIT", &bbai_env::step_render_split, -1},
     {"rollout_multi", "BBAI_ROLLOUT_MULTI", &bbai_env::rollout_multi, 1},
-    {"done_action_enum", nullptr, &bbai_env::done_action_enum, 0, FLAG},                      // (a SEMANTIC switch, the first of two in this list: include/bbai.h bbai_set_done_actions)
+    {"done_action_enum", nullptr, &bbai_env::done_action_enum, 0, FLAG},                      // (a SEMANTIC switch, the first of three in this list: include/bbai.h bbai_set_done_actions)
     {"reseed_levels", nullptr, &bbai_env::reseed_levels, 0, AT_LEAST, 0},                     // (the second SEMANTIC switch: the depth of the next bbai_reseed calls; a host value read when a call is enqueued)
+    {"step_hold", nullptr, &bbai_env::step_hold, 0, FLAG},                                    // (the third SEMANTIC switch: BBAI_ACTION_HOLD; like "reseed_levels" a host value read when a stepping call is enqueued)
     {"pregen_lane", nullptr, &bbai_env::pregen_lane, 0, AS_IS, 0, true},                              // (set: bbai_set_option converts the generator state)
     {"lookahead_streams", nullptr, &bbai_env::n_sides, 0, AS_IS, 0, true},                            // (set: set_sides)
     {"gate_forced_strict", nullptr, &bbai_env::gate_forced, 0, AS_IS, 0, true},                       // 1: the caller's stream failed the concurrency probe
@@ -922,7 +924,11 @@ static bool use_fused_consume(const bbai_env* e) {
 //   step_kernel   k_step over the 64-env blocks [block0, block0 + nblocks) on stream `ks`
 //   step_finish   k_consume (unfused) / mission tokens / the window's close + refill -- on the caller's stream, behind EVERY k_step of the step
 // what the caller of one step hands over (device pointers); bbai_rollout moves `actions` on from tick to tick
-struct StepIO { const uint8_t* actions; uint8_t* image; uint8_t* dirs; float* rewards; double* rewards64; uint8_t* dones; int auto_reset, enum_done; };
+struct StepIO { const uint8_t* actions; uint8_t* image; uint8_t* dirs; float* rewards; double* rewards64; uint8_t* dones; int auto_reset, enum_done;
+                int hold;      // the action byte of an env that sits the step out, or -1: none does (step_hold; bbai_bot_rollout: always -1)
+};
+// The hold byte of a call that is being enqueued (option "step_hold": read here, on the host).
+static int step_hold(const bbai_env* e) { return e->step_hold ? BBAI_ACTION_HOLD : -1; }
 struct StepPlan { FuseArgs fa; bool fused; uint32_t* counter; TapArgs tap = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
                   bool dirty = false;      // k_step finds the dirty cells of the registered target for its render (step_render_launch, step_dirty)
 };
@@ -955,7 +961,7 @@ static int step_kernel(bbai_env* e, const StepPlan& p, const StepIO& io, hipStre
     StepArgs a;
     a.c = e->cfg; a.n = e->n; a.recs = e->rec; a.hots = e->hot; a.stales = e->stale; a.vheads = e->vhead; a.vsets = e->vset; a.actions = io.actions; a.image = io.image; a.dirs = io.dirs;
     a.rewards = io.rewards; a.rewards64 = io.rewards64; a.dones = io.dones; a.auto_reset = io.auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
-    a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = io.enum_done; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
+    a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = io.enum_done; a.hold = io.hold; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
     a.tap = p.tap; a.ticks = ticks;
     a.dshadow = p.dirty && ticks == 1 ? e->rt.shadow : nullptr; a.dmask = e->rt.dmask; a.lut = e->lut;
 #define STEP_LAUNCH(VV, FF, CC) do { if (ticks > 1) hipLaunchKernelGGL((k_step_ticks<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); \
@@ -1012,7 +1018,7 @@ int bbai_step(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s));
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
     return call.leave();
 }
 
@@ -1057,7 +1063,7 @@ int bbai_step_tapped(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_
     CallScope call(e, s);
     BBAI_TRY(call.rc);
     const TapRows rows = {image_out, dir_out, reward64_out, done_out};
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s, &rows));
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s, &rows));
     return call.leave();
 }
 
@@ -1464,7 +1470,7 @@ int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, s));
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
     BBAI_TRY(full_launch(e, nullptr, e->n, full, s));
     return call.leave();
 }
@@ -1548,7 +1554,7 @@ int bbai_step_render(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_
     BBAI_TRY(step_ready(e, auto_reset, "step"));
     if (e->n_tiles <= 0) { snprintf(g_err, sizeof(g_err), "render before set_atlas"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
-    return step_render_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum}, pixels, (hipStream_t)stream);
+    return step_render_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, pixels, (hipStream_t)stream);
 }
 
 // Register (or clear with NULL) a caller-owned uint8[n][72] device buffer that the engine keeps filled with the
@@ -1883,7 +1889,7 @@ int bbai_bot_rollout(bbai_env* e, int T, uint8_t* image, uint8_t* dirs, uint8_t*
         if (tokens_out) HIP_TRY(hipMemcpyAsync(tokens_out + (size_t)t * n * TOK_MAX, e->tokens, n * TOK_MAX, hipMemcpyDeviceToDevice, s));
         BBAI_TRY(bot_launch(e, nullptr, actions_out + (size_t)t * n, A_RESET_ENV, gave_up_out + (size_t)t * n, s));
         BBAI_TRY(step_launch(e, StepIO{actions_out + (size_t)t * n, image, dirs, rewards_out + (size_t)t * n, nullptr, dones_out + (size_t)t * n, 1,
-                                       1 /* the expert's `done` is the enum member (bot.py:593) */}, s));
+                                       1 /* the expert's `done` is the enum member (bot.py:593) */, -1 /* ... and it never holds */}, s));
     }
     return call.leave();
 }
@@ -1951,7 +1957,7 @@ int bbai_rollout(bbai_env* e, int T, const uint8_t* actions, uint8_t* image, uin
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)e->n;
     const bool own_tap = tap && !tap->ids_dev;          // the envs of bbai_step_tap_set, logged by the stepping lanes
-    StepIO io = {actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum};
+    StepIO io = {actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)};
     auto tap_rows = [&](int t) {                        // the tap log's rows of tick t
         const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
         return TapRows{tap->image_out + orow * c * OBS_BYTES, tap->dir_out + orow * c, tap->reward64_out + row * c, tap->done_out + row * c};
@@ -2121,12 +2127,13 @@ int bbai_get_done_actions(bbai_env* e) { return e && e->lsm ? 1 : 0; }
 
 // Performance knobs by name (KNOBS, plus the three that do work): what the BBAI_* environment variables set at bbai_create, switchable on a
 // live handle so that measurements can alternate settings inside ONE process on ONE box (tools/ab.py).  Synchronises the device first
-// ("reseed_levels" aside: a caller sets it around single bbai_reseed calls of a running loop).
+// ("reseed_levels" and "step_hold" aside: a caller sets them around single bbai_reseed / stepping calls of a running loop).
 int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
     if (!e || !name) ARG_FAIL("null handle or name");
     ON_DEVICE(e->device);
     const Knob* k = find_knob(name);
-    if (!(k && k->field == &bbai_env::reseed_levels)) HIP_TRY(hipDeviceSynchronize());      // (a bbai_reseed reads its depth on the host, when it is enqueued: nothing in flight sees it)
+    // (a bbai_reseed reads its depth, a stepping call its hold byte, on the host when it is enqueued: nothing in flight sees either)
+    if (!(k && (k->field == &bbai_env::reseed_levels || k->field == &bbai_env::step_hold))) HIP_TRY(hipDeviceSynchronize());
     const int v = (int)value;
     if (!strcmp(name, "pregen_lane")) {
         if (!e->mtt) { if (v) ARG_FAIL("pregen_lane: this level kind / layout is not covered by the lane generator"); }

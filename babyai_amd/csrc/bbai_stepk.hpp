@@ -415,9 +415,18 @@ struct FuseArgs {
     uint8_t* pending; uint8_t* first_slot; uint32_t* win_meta; unsigned long long* totals;
 };
 // step_body: ONE tick of a 64-env block (the whole of k_step; k_step_ticks calls it once per tick).  `s_obs`: the block's LDS rows.
+// The hold action (option "step_hold", include/bbai.h BBAI_ACTION_HOLD): `hold` = the action byte that means "this env sits this step out", or -1
+// (the option is off, or the actions are the expert's) -- then no byte compares equal and nothing below differs from a build without it.
+//   a held lane in a wave that steps   takes the frozen arm: its row goes through LDS unchanged (CP: the deferred copy behind the wave barrier), it stores
+//                                      nothing else -- no state, no reward / done / direction, no lastStepMatch byte -- and never asks for a reset, not even
+//                                      as an env the generator gave up on (frozen == 2: that skip waits for the env's next real step);
+//   a wave in which nobody steps       leaves behind its one coalesced action load -- false is returned: no SoA state, no plane or record line, no LDS row,
+//                                      no store loop over the block's span, no counter.  One wave is one block: the branch is uniform, and the barriers
+//                                      further down are reached by all of a block or by none.  A wave with a listed env of the step's own tap stays: a held,
+//                                      listed env logs its unchanged outputs (one row per listed env per step).
 template <bool VP, int FUSE /* 0: finished envs listed for k_consume; 1: consumed by the stepping wave (consume_env); 3: in-place layout (advance_load / advance_finish) */,
           bool CP = false /* in-place small single rooms: pose-independent C plane row instead of the record's planes (bbai_types.hpp) */>
-__device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t* __restrict__ recs,
+__device__ __forceinline__ bool step_body(const LevelCfg& c, int64_t n, uint8_t* __restrict__ recs,
                                                      Hot* __restrict__ hots, uint64_t* __restrict__ stales,
                                                      uint32_t* vheads, uint64_t* vsets /* read by every lane, WRITTEN for the envs the wave moves on (FUSE): no restrict */,
                                                      const uint8_t* __restrict__ actions, uint8_t* image /* read (frozen envs re-emit) AND written: no restrict */,
@@ -427,6 +436,7 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
                                                      int prio, uint8_t* __restrict__ vplane, uint16_t* __restrict__ fcache,
                                                      uint8_t* __restrict__ lsm_arr /* NULL, or the done-action mode's per-env bits */,
                                                      int enum_done /* done-action mode: this step's `done` actions are the enum member (bbai_step.hpp verify_side) */,
+                                                     int hold /* the action byte of an env that sits this step out (A_HOLD), or -1: none does */,
                                                      FuseArgs fuse, int64_t block0 /* first 64-env block of this launch (bbai_step_render steps the batch in two halves) */,
                                                      uint8_t* __restrict__ cplane /* CP: [n][cpl_bytes] */, const TapArgs& tap /* mask == NULL: none */,
                                                      uint8_t* const s_obs, const int lane /* threadIdx.x */, const int blk_x /* blockIdx.x */) {
@@ -436,6 +446,14 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
     const int64_t env0 = ((int64_t)blk_x + block0) * STEP_BLOCK;
     const int64_t env = env0 + lane;
     const bool active = env < n;
+    int action = 0;
+    if (hold >= 0) {
+        // the hold action is on: the wave's actions come first, on their own (one more round trip in front of a wave that steps, the price of a
+        // wave that does not step costing one 64-byte load), and a wave none of whose envs steps is done
+        action = active ? (int)actions[env] : hold;
+        const bool listed = tap.mask && tap.mask[(int64_t)blk_x + block0] != 0;
+        if (!listed && !__ballot(action != hold)) return false;
+    }
     bool want_reset = false;
     bool frozen_copy = false; // CP: a frozen lane's row copy, deferred until every lane has read its parked plane (below)
     int my_slot = 0;
@@ -446,7 +464,7 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
         u32x4 hv = *(const u32x4*)(hots + env);
         uint64_t stale = stales[env];
         VProg vp; vp.bind(vheads[env], vsets + env, n);
-        int action = actions[env];
+        if (hold < 0) action = actions[env];
         uint32_t fc = (VP || CP) ? (uint32_t)fcache[env] : 0u;
         Lsm lsm = {lsm_arr ? (uint32_t)lsm_arr[env] : 0u, lsm_arr != nullptr};
         // CP: the env's whole grid + object positions come with the SoA state -- nothing below depends on a second memory round trip
@@ -469,7 +487,8 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
         __builtin_memcpy(&h, &hv, sizeof(h));
         my_slot = h.slot;
         uint8_t* rec = FUSE == 3 ? fuse.next_recs + ring_at(live_slot(h.slot, fuse.depth), env, fuse.depth) * (int64_t)c.rec_bytes : recs + env * (int64_t)c.rec_bytes;
-        if (!h.frozen) {
+        const bool held = action == hold;      // (never with hold = -1: a byte is 0..255)
+        if (!h.frozen && !held) {
             double reward = 0.0;
             const EnvRef r = env_ref(c, rec, vp);
             uint8_t* vrow = VP ? vplane + env * (int64_t)v_bytes(c) : nullptr;
@@ -560,9 +579,9 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
             encode_cells(cp, RowPacker(s_rows, lane));
 #endif
         }
-        // frozen envs keep re-emitting their last outputs: copy them through LDS unchanged
+        // frozen envs keep re-emitting their last outputs: copy them through LDS unchanged; so does an env that holds
         else {
-            if (h.frozen == 2 && auto_reset) {      // level the generator gave up on (last-resort guard): skip to the next one
+            if (h.frozen == 2 && auto_reset && !held) {      // level the generator gave up on (last-resort guard): skip to the next one
                 rewards[env] = 0.0f;
                 if (rewards64) rewards64[env] = 0.0;
                 dones[env] = 1;
@@ -665,6 +684,7 @@ __device__ __forceinline__ void step_body(const LevelCfg& c, int64_t n, uint8_t*
             tap.rew_out[row] = __hip_atomic_load(rewards64 + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    return true;
 }
 // The dirty cells of a step whose render is a delta render of the registered target (render_launch: k_render_dstore).  k_step's tail, after
 // step_body has stored the block's rows: lanes over (env, cell) of the block's 64 rows, 16 cells per lane and chunk -- the chunk's 16 shadow
@@ -747,7 +767,7 @@ __device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __r
 struct StepArgs {
     LevelCfg c; int64_t n; uint8_t* recs; Hot* hots; uint64_t* stales; uint32_t* vheads; uint64_t* vsets; const uint8_t* actions; uint8_t* image; uint8_t* dirs;
     float* rewards; double* rewards64; uint8_t* dones; int auto_reset; int32_t* reset_list; uint8_t* reset_slot; uint32_t* counters; int prio; uint8_t* vplane;
-    uint16_t* fcache; uint8_t* lsm_arr; int enum_done; FuseArgs fuse; int64_t block0; uint8_t* cplane; TapArgs tap;
+    uint16_t* fcache; uint8_t* lsm_arr; int enum_done; int hold /* step_body: the hold action's byte, or -1 */; FuseArgs fuse; int64_t block0; uint8_t* cplane; TapArgs tap;
     int ticks;            // k_step_ticks: steps this launch takes; tick t reads actions + t n and logs into the tap rows t * tap.count further on
     uint8_t* dshadow; uint64_t* dmask; const uint8_t* lut;     // k_step: dshadow != NULL = the dirty cells of this step for its delta render (step_dirty)
 };
@@ -756,8 +776,15 @@ __global__ __launch_bounds__(STEP_BLOCK, BBAI_STEP_WAVES) void k_step(StepArgs a
     // the block's observation rows at the OUTPUT pitch of 147 bytes (bbai_step.hpp RowPacker), 16 bytes of front padding
     __shared__ __attribute__((aligned(16))) uint8_t s_obs[ROWS_FRONT + STEP_BLOCK * OBS_BYTES + 16];
     __shared__ __attribute__((aligned(8))) uint8_t s_lut[512];      // step_dirty (9 952 bytes in all: 16 blocks = 16 waves still fit a CU's 160 KiB)
-    step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset, a.reset_list,
-                            a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.fuse, a.block0, a.cplane, a.tap, s_obs, (int)threadIdx.x, (int)blockIdx.x);
+    const bool stepped = step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset,
+                            a.reset_list, a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.hold, a.fuse, a.block0, a.cplane, a.tap, s_obs, (int)threadIdx.x,
+                            (int)blockIdx.x);
+    if (!stepped) {
+        // every env of the wave held: none of their cells is dirty -- said here, or the store-only render would store last step's pieces again
+        const int64_t env = ((int64_t)blockIdx.x + a.block0) * STEP_BLOCK + threadIdx.x;
+        if (a.dshadow && env < a.n) a.dmask[env] = 0;
+        return;
+    }
     if (a.dshadow) step_dirty(a.n, ((int64_t)blockIdx.x + a.block0) * STEP_BLOCK, a.dshadow, a.dmask, a.lut, s_obs + ROWS_FRONT, s_lut, (int)threadIdx.x);
 }
 // Several ticks in one launch (bbai_rollout, open-loop actions): an env's step touches only its own state, its block's LDS rows and -- for a
@@ -781,8 +808,9 @@ __global__ __launch_bounds__(STEP_BLOCK, 4) void k_step_ticks(StepArgs a_) {
         const StepArgs a = *(const StepArgs*)ap;          // (InferAddressSpaces turns these back into scalar loads of the constant segment)
         TapArgs tap = a.tap;
         tap.image_out += (int64_t)t * tap.count * OBS_BYTES; tap.dir_out += (int64_t)t * tap.count; tap.rew_out += (int64_t)t * tap.count; tap.done_out += (int64_t)t * tap.count;
+        // (a tick in which the whole wave holds -- step_body returns false behind its action load -- is just the next tick)
         step_body<VP, FUSE, CP>(a.c, a.n, a.recs, a.hots, a.stales, a.vheads, a.vsets, a.actions + (int64_t)t * a.n, a.image, a.dirs, a.rewards, a.rewards64, a.dones, a.auto_reset,
-                                a.reset_list, a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.fuse, a.block0, a.cplane, tap, s_obs, lane, blk_x);
+                                a.reset_list, a.reset_slot, a.counters, a.prio, a.vplane, a.fcache, a.lsm_arr, a.enum_done, a.hold, a.fuse, a.block0, a.cplane, tap, s_obs, lane, blk_x);
         __syncthreads();        // (one wave per block: orders this tick's LDS reads before the next one's writes for the compiler)
     }
 }

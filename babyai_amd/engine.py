@@ -600,17 +600,29 @@ class BatchedBabyAIEnv(object):
                                               self._stream()), "bbai_reset")
         return self._obs()
 
-    def step(self, actions, validate=None):
+    def _step_actions(self, actions, validate, count, hold_ok):
+        """step()'s actions as a contiguous uint8[count] tensor on the device.  Host data is checked for free and a device tensor under
+        validate / validate_actions: AssertionError("unknown action") beyond RESET_ENV -- beyond HOLD where a hold means something
+        (`hold_ok`: True, or None = ask the handle's option "step_hold", and only when an 8 turns up)."""
         torch = self.torch
+
+        def limit(hi):
+            ok = hold_ok if hold_ok is not None or hi != self.HOLD else bool(self.get_option("step_hold"))
+            return self.HOLD if ok else self.RESET_ENV
+
         if not isinstance(actions, torch.Tensor):
             actions = np.asarray(actions)
-            if actions.size and (int(actions.max()) > self.RESET_ENV or int(actions.min()) < 0):      # host data: checked for free
-                raise AssertionError("unknown action")
+            if actions.size:                                  # host data: checked for free
+                lo, hi = int(actions.min()), int(actions.max())
+                if lo < 0 or hi > limit(hi):
+                    raise AssertionError("unknown action")
+            else:
+                actions = actions.astype(np.uint8)            # (an empty list has no integer type of its own)
             actions = torch.as_tensor(actions, device=self.device)
         elif self.validate_actions if validate is None else validate:
-            # MiniGridEnv.step: `assert False, "unknown action"` (7 = RESET_ENV is this engine's per-env reset command)
+            # MiniGridEnv.step: `assert False, "unknown action"` (7 = RESET_ENV is this engine's per-env reset command, 8 = HOLD where it is on)
             lo, hi = (int(v) for v in torch.stack([actions.min(), actions.max()]).tolist())
-            if hi > self.RESET_ENV or lo < 0:
+            if lo < 0 or hi > limit(hi):
                 raise AssertionError("unknown action")
         if actions.dtype != torch.uint8:
             # a wider integer must not WRAP into a valid action on its way to a byte (263 -> 7 = RESET_ENV, 256 -> 0 = left):
@@ -623,9 +635,12 @@ class BatchedBabyAIEnv(object):
             actions = torch.where((actions & -256) != 0, 255, actions)
         if actions.dtype != torch.uint8 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.uint8).contiguous()
-        if actions.numel() != self.num_envs:
-            raise ValueError("need %d actions" % self.num_envs)
-        self._hold["actions"] = actions
+        if actions.numel() != count:
+            raise ValueError("need %d actions" % count)
+        return actions.reshape(-1)
+
+    def _step_native(self, actions):
+        """One step of the whole batch with `actions` uint8[num_envs] on the device: the entry this batch's observation mode steps through."""
         ev = self._ev_begin()
         if self.full_obs and not self.pixel and self.kernel_events is None:
             # FullyObsWrapper's step: transition + the full observation of every env as ONE call (include/bbai.h bbai_step_full)
@@ -641,6 +656,66 @@ class BatchedBabyAIEnv(object):
         self._ev_end("step", ev)
         return self._obs(), self.reward, self.done, {}
 
+    def step(self, actions, validate=None, ids=None):
+        """env.step(actions[i]) for every env.  `ids` (an int sequence, an ndarray or an int64 device tensor of length k): step ONLY the listed
+        envs -- `actions` has length k, env ids[j] takes actions[j] and every other env HOLDS (include/bbai.h BBAI_ACTION_HOLD): its state,
+        step count and level stream stay, its observation rows are written again unchanged and its reward / done entries keep the values
+        of its last step.  A 64-env block without a listed env costs one 64-byte load, so a sparse step costs little more than its launch.
+        An id outside [0, num_envs) is skipped (pad with -1); a host list that names an env twice is a ValueError (in a device list it is
+        undefined which action wins); a device list causes no host synchronisation.  Without `ids`, a full vector may carry HOLD bytes
+        itself once set_option("step_hold", 1) is on.  Unknown actions: see validate_actions -- 8 is known exactly where it means hold."""
+        if ids is None:
+            actions = self._step_actions(actions, validate, self.num_envs, None)
+            self._hold["actions"] = actions
+            return self._step_native(actions)
+        torch = self.torch
+        self._no_env_twice("step", ids, padding=True)
+        k, _, ids_t = self._ids(ids)
+        actions = self._step_actions(actions, validate, k, True)
+        n = self.num_envs
+        buf = getattr(self, "_hold_actions", None)
+        if buf is None:                 # uint8[N] full of HOLD between the calls, one spare entry behind it for the ids that name no env
+            buf = self._hold_actions = torch.full((n + 1,), self.HOLD, dtype=torch.uint8, device=self.device)
+        at = torch.where((ids_t < 0) | (ids_t >= n), n, ids_t)
+        buf.index_copy_(0, at, actions)
+        self._hold["actions"] = (buf, at, actions)
+        before = self.get_option("step_hold")
+        if before != 1:
+            self.set_option("step_hold", 1)         # (a host value, read when the call below is enqueued: no synchronisation)
+        try:
+            return self._step_native(buf[:n])
+        finally:
+            if before != 1:
+                self.set_option("step_hold", before)
+            buf.index_fill_(0, at, self.HOLD)       # (behind the step on the same stream)
+
+    def lookahead(self, ids, scratch):
+        """Expand the states of the k listed envs with all seven actions, moving no other env and without a host trip: `scratch` = 7 k distinct
+        envs of this batch, none of them listed, that the caller sets aside (their states are overwritten; ids in [0, num_envs)).  Scratch env
+        7 j + a gets the state of env ids[j] (save_state / load_state) and takes action a in a step that every other env holds.  Returns the
+        children's outputs, child (j, a) = env ids[j] after action a: {"image": the observation image (encoded, pixels or full, as step()
+        returns it) [k, 7, ...], "direction", "reward", "reward64", "done": [k, 7]}.  The roots themselves do not move; a child whose
+        episode ended shows the scratch env's own next level (auto_reset) and the terminal step's reward and done."""
+        torch = self.torch
+        self._no_env_twice("lookahead", scratch)
+        if not isinstance(ids, torch.Tensor) and not isinstance(scratch, torch.Tensor):
+            if set(np.asarray(ids, dtype=np.int64).reshape(-1).tolist()) & set(np.asarray(scratch, dtype=np.int64).reshape(-1).tolist()):
+                raise ValueError("lookahead: a scratch env is one of the listed envs")
+        k, _, ids_t = self._ids(ids)
+        ks, _, scratch_t = self._ids(scratch)
+        if ids_t is None or scratch_t is None or ks != 7 * k:
+            raise ValueError("lookahead: %d scratch envs for %d listed envs (7 each)" % (ks, k))
+        snap = self.save_state(ids_t)
+        rows = torch.arange(k, dtype=torch.int64, device=self.device).repeat_interleave(7)
+        self.load_state(snap, scratch_t, rows)
+        acts = torch.arange(7, dtype=torch.uint8, device=self.device).repeat(k)
+        obs = self.step(acts, validate=False, ids=scratch_t)[0]
+        img = obs["image"].index_select(0, scratch_t)
+        out = {"image": img.view((k, 7) + tuple(img.shape[1:]))}
+        for name in ("direction", "reward", "reward64", "done"):
+            out[name] = getattr(self, name).index_select(0, scratch_t).view(k, 7)
+        return out
+
     def rollout(self, actions, tap=None, obs_row0=0, row0=0, step_tap=False):
         """An open-loop rollout (include/bbai.h bbai_rollout): `actions` uint8[T, N] on the device; T steps (+ the pixel render
         in pixel mode) are enqueued by ONE call, exactly what T calls of step() enqueue.  `tap`: a log dict as bench.py builds
@@ -649,7 +724,8 @@ class BatchedBabyAIEnv(object):
         obs_row0 + t / result row row0 + t.  Afterwards image / direction / reward / done (/ pixels) hold the last step's
         outputs; returns the observation dict of that step.  step_tap=True: the log's rows are written by the stepping lanes for the envs
         listed with set_step_tap() (log row k = listed env k; no "ids" needed, no pixel rows) -- with encoded observations one k_step launch then
-        takes every step the look-ahead window has left (include/bbai.h bbai_rollout)."""
+        takes every step the look-ahead window has left (include/bbai.h bbai_rollout).  Under set_option("step_hold", 1) a HOLD byte holds
+        its env for that tick, as in step()."""
         torch = self.torch
         if actions.dtype != torch.uint8 or actions.device != self.device or not actions.is_contiguous() or actions.dim() != 2 \
                 or actions.shape[1] != self.num_envs:
@@ -854,6 +930,7 @@ class BatchedBabyAIEnv(object):
 
     BOT_GAVE_UP = 255
     RESET_ENV = 7          # step() "action": abandon the episode of that env (include/bbai.h BBAI_ACTION_RESET_ENV)
+    HOLD = 8               # step() "action" under set_option("step_hold", 1) / step(ids=...): this env sits the step out (BBAI_ACTION_HOLD)
 
     def bot_actions(self, prev_actions=None, out=None):
         """One decision of the reference's expert (babyai/bot.py Bot.replan) for every env, on the device:
@@ -964,7 +1041,7 @@ class BatchedBabyAIEnv(object):
 
     def set_option(self, name, value):
         """A performance knob of the live handle by name (include/bbai.h bbai_set_option: launch shapes, render input,
-        priorities -- never semantics, but for "done_action_enum" and "reseed_levels": see reseed()).  What measurements alternate inside
+        priorities -- never semantics, but for "done_action_enum", "reseed_levels" (see reseed()) and "step_hold" (see step())).  What measurements alternate inside
         one process (tools/ab.py)."""
         _check(self.lib, self.lib.bbai_set_option(self.handle, name.encode(), int(value)), "bbai_set_option(%s)" % name)
     

@@ -94,8 +94,17 @@ int bbai_reset(bbai_env* env, uint8_t* image_dev, uint8_t* dir_dev, void* stream
  * are host arrays anyway, always check and raise AssertionError("unknown action")).
  * reward_dev[i]   = float32 rounding of the reward (what babyai/rl/algos/base.py:162-167 makes of it);
  * reward64_dev[i] = the reference's own return value: MiniGridEnv._reward() as a Python float (levelgen.py:59-61),
- *                   bit for bit (what babyai/evaluate.py:128 accumulates).  May be NULL. */
+ *                   bit for bit (what babyai/evaluate.py:128 accumulates).  May be NULL.
+ * THE HOLD ACTION: under bbai_set_option(env, "step_hold", 1) an env whose byte is BBAI_ACTION_HOLD takes no part in the step -- the way to
+ * step only some envs of a batch (expand a stored state, evaluate a few, step the envs whose actions are ready).  Its state, step_count,
+ * level stream, lastStepMatch byte and the expert's view of it are untouched; its rows of image_dev / dir_dev are written again unchanged;
+ * its entries of reward_dev / reward64_dev / done_dev are LEFT ALONE -- the frozen env's contract: the caller's buffers must hold the env's
+ * last outputs.  A frozen or parked env that holds stays frozen or parked; BBAI_ACTION_RESET_ENV is unaffected.  A 64-env block (envs
+ * 64 b .. 64 b + 63) in which every env holds costs one 64-byte load, so a step that holds nearly everybody costs little more than its launch.
+ * Honoured by bbai_step, bbai_step_render, bbai_step_full, bbai_step_tapped (a held listed env logs its unchanged outputs) and, per tick,
+ * bbai_rollout; never by bbai_bot_rollout (its actions are the expert's).  With the option at 0 (default) byte 8 is `done` like 9..255. */
 #define BBAI_ACTION_RESET_ENV 7
+#define BBAI_ACTION_HOLD 8
 int bbai_step(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_dev, uint8_t* dir_dev,
               float* reward_dev, double* reward64_dev, uint8_t* done_dev, int auto_reset, void* stream);
 
@@ -294,7 +303,8 @@ int bbai_checkpoint_load(bbai_env* env, const void* host_buf, int64_t bytes);
  * (babyai/bot.py:547-597; callers babyai/utils/agent.py:139-146 BotAgent.act, scripts/make_agent_demos.py:93-107).
  * `prev_actions_dev` = the action each env was actually stepped with since the previous call (advising mode,
  * bot.py:88-98), or NULL = "the suggestion was taken" (replan(None)).  An env whose episode has just started
- * (step_count == 0), or whose expert was not consulted on the previous step, gets a fresh Bot (= `Bot(env)` there).  `actions_dev[i]` = suggested action 0..6, or 255 where the reference bot would
+ * (step_count == 0), or whose expert was not consulted on the previous step, gets a fresh Bot (= `Bot(env)` there) -- so does an env that
+ * held since (BBAI_ACTION_HOLD: its step_count did not advance, which to the expert is a step it was not consulted on).  `actions_dev[i]` = suggested action 0..6, or 255 where the reference bot would
  * have raised (assertion / DisappearedBoxError / endless replanning); it stays 255 until the episode ends.
  * Decision-for-decision parity with the reference bot: tests/test_hostsim_bot.py, tests/golden/bot/.
  * The expert's plan lives in the handle (allocated on first use, ~1.7 KB per env) and is not part of
@@ -516,8 +526,11 @@ int bbai_get_done_actions(bbai_env* env);
  *   "bot_group"         the expert's kernel (bbai_bot_act / bbai_bot_rollout): 0 (default) = one lane per env (k_bot), 16 = one 16-lane
  *                       group per env with the first search in LDS (k_botg: same decisions, measured ~2 x slower -- an experiment
  *                       kept for reference); also BBAI_BOT_GROUP at bbai_create
- *   "done_action_enum"  a semantic switch (one of two in this list), meaningful in done-action mode only: see bbai_set_done_actions
- *   "reseed_levels"     the other semantic switch: how many levels of the new stream the following bbai_reseed calls generate per listed env (see
+ *   "done_action_enum"  a semantic switch (one of three in this list), meaningful in done-action mode only: see bbai_set_done_actions
+ *   "step_hold"         the third semantic switch: 1 = action byte BBAI_ACTION_HOLD means "this env sits the step out" (see bbai_step), 0 (default) =
+ *                       byte 8 is `done` like every unknown action; any non-zero value is stored as 1.  Read on the host when a stepping call is
+ *                       enqueued, so setting it does not synchronise the device: a caller sets it around single calls of a running loop
+ *   "reseed_levels"     the second semantic switch: how many levels of the new stream the following bbai_reseed calls generate per listed env (see
  *                       bbai_reseed).  0 (default), or anything >= the ring's depth: the whole ring.  Negative values are stored as 0.  Read on the
  *                       host when a bbai_reseed is enqueued, so setting it does not synchronise the device and costs no allocation
  * BBAI_ERR_ARG for an unknown name. */
