@@ -258,7 +258,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* cplane;      // [n][cpl_bytes] C plane rows of the small single rooms (bbai_types.hpp cpl_ok; in-place layout only); BBAI_CPLANE=0: none
     uint8_t* lsm;         // [n] done-action verifier mode only (BABYAI_DONE_ACTIONS / bbai_set_done_actions): bit k = leaf k's
                           //     lastStepMatch (babyai/levels/verifier.py:213-230); NULL = the normal mode
-    unsigned int* render_tickets;   // [64][64] ticket counters of k_render_q + its departure counter; zero between launches (the kernel leaves them so)
+    unsigned int* render_tickets;   // [64][64] ticket counters of k_render_q + its departure counter (rows 0 .. 8), k_render_dstore_lw's (rows 32, 33); zero between launches (the kernels leave them so)
     int render_queue;     // -1 = by batch size (default), 0 = one-shot blocks only, m = queue shape m (render_launch)
     int render_queue_bpc; // persistent render blocks per CU (0 = 1024 threads' worth: ONE 1024-thread block per CU --
                           // profiles/r04/render_queue_ab_1M_b.jsonl: k_render 1.50 ms against 1.61 with two)
@@ -269,9 +269,9 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     RenderTarget rt;      // (bbai_target.hpp: the record, and the planner every render asks)
     int rt_next_ts;       // "render_target_tile_size": the tile size the NEXT bbai_set_render_target registers (8, default)
     int render_delta;     // 1 (default) = renders into the registered buffer store only changed lines
-    int render_delta_sched;    // 0 (default) = interleaved groups per block, 1 = contiguous ranges (k_render delta)
+    int render_delta_sched;    // k_render_delta: 0 (default) = interleaved groups per block, 1 = contiguous ranges, 2 as 0; the store-only render of pieces: 0 / 1 = the ticket queue (k_render_dstore_lw), 2 = the static split (k_render_dstore)
     int render_delta_tpb;      // 512 (default, also for 0) or 1024 threads per delta render block
-    int render_delta_bpc;      // delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024)
+    int render_delta_bpc;      // delta render blocks per CU (0 = the default: 3 of 512 threads, 1 of 1024; 1 of k_render_dstore_lw's 576)
     int render_piece_bytes;    // the delta render's store unit, 64-byte pieces (default) or 128 (whole lines)
     int render_delta_from_step;   // 1 = a step + render call finds the dirty cells in k_step, 0 = in the render, -1 (default) = by batch size
     int n_cus;            // compute units of the device
@@ -1134,7 +1134,9 @@ static RenderPlan plan_render(const bbai_env* e, uint8_t* shadow) {
 // One render's range: envs [env_off, env_off + nr) of the batch, `input` and `pixels` at its first env
 struct RenderRange { const uint8_t* input; uint8_t* pixels; int64_t nr, env_off; hipStream_t stream; };
 
-// The delta render of target envs whose shadow is valid: k_render_dstore behind a step that found the dirty cells, else k_render_delta.
+// The delta render of target envs whose shadow is valid: behind a step that found the dirty cells the store-only render (k_render_dstore_lw
+// for 64-byte pieces, launch_dstore_lw below; k_render_dstore for 128-byte lines and, option "render_delta_sched" 2, for pieces with the
+// static split: the previous kernel, kept as the reference), else k_render_delta, of which the following was measured:
 // 1 048 576 BossLevel envs, random actions, settings alternated in one process (tools/ab.py; profiles/render_delta/ab.jsonl),
 // k_render ms per launch: (1024 threads, 1 block per CU) interleaved 0.813, contiguous ranges 0.795, 2 blocks per CU 0.795;
 // (512, 1) 0.795; (512, 3) 0.665 <- default: three independent blocks per CU hide one another's encoding / shadow loads and
@@ -1152,6 +1154,17 @@ template <int P>
 static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
     hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles);
 }
+// The store-only render of 64-byte pieces (the default): k_render_dstore_lw -- groups from one ticket counter, two per ticket, ONE
+// 576-thread block per CU (no more blocks than tickets: every block opens with one).  1 048 576 BossLevel envs, bench.py's actions,
+// settings alternated in one process (tools/ab.py; profiles/render_store_queue/), ms per step in five processes: k_render_dstore's static
+// split, three blocks per CU, 0.634-0.643; this kernel at three blocks per CU 0.618-0.625, at two 0.621-0.630, at one 0.595-0.610 -- the
+// fewer blocks share the one in-order stream of groups, the more compact the window the chip's stores advance through.
+static void launch_dstore_lw(const bbai_env* e, const RenderRange& r, int64_t groups, uint8_t* sh) {
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : 1);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (groups + DSTORE_LW_K - 1) / DSTORE_LW_K));
+    hipLaunchKernelGGL((k_render_dstore_lw<64>), dim3(blocks), dim3(DSTORE_LW_T), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles, e->render_tickets);
+}
 static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool from_step) {
     const int cus = e->n_cus > 0 ? e->n_cus : 256;
     const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
@@ -1160,7 +1173,8 @@ static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool fr
     const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
     uint8_t* sh = e->rt.shadow + r.env_off * CELLS;
-    if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
+    if (from_step && e->render_piece_bytes != 128 && e->render_delta_sched != 2) launch_dstore_lw(e, r, groups, sh);
+    else if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
     else if (T == 512) launch_delta_t<512>(e, r, blocks, sh);
     else launch_delta_t<1024>(e, r, blocks, sh);
 }

@@ -1,6 +1,6 @@
 // bbai_render.hpp -- the partial-view pixel render (RGBImgPartialObsWrapper as a tile-atlas gather): the full render (k_render, k_render_q),
 // the delta render into the registered target (k_render_delta) and its store-only form behind a step that found the dirty cells itself
-// (k_render_dstore).  Every stage the kernels share is written once: load_atlas_lds / load_lut_lds, tile_id, store_chunk16, delta_cell,
+// (k_render_dstore; k_render_dstore_lw: its 64-byte pieces from a ticket queue).  Every stage the kernels share is written once: load_atlas_lds / load_lut_lds, tile_id, store_chunk16, delta_cell,
 // init_line_table, list_dirty_lines, store_listed_lines, init_piece_cells, init_chunk_table, store_chunk16_t, store_dirty_pieces.  The piece
 // stores address their chunks through a per-block table (chunk_recipe below: the frame geometry of a 16-byte chunk, worked out once per
 // block and not once per store); the full renders keep the arithmetic form (render_chunk).  Two copies remain, each marked where it
@@ -597,6 +597,147 @@ __global__ __launch_bounds__(T) void k_render_dstore(int64_t n, uint8_t* __restr
         // B2: 16 bytes per lane, 8 lanes per listed line (as k_render_delta)
         store_listed_lines(s_list[buf], (int)s_nd[buf], s_atlas, s_tile[buf], (u32x4*)(pixels + env0 * PIX_BYTES), ne * VEC_PER_ENV, tid, T);
     }
+    }
+}
+
+// k_render_dstore_lw: k_render_dstore's piece branch as a queue.  Eight waves only store and a ninth, the loader, only loads; a group's
+// dirty envs go to the storing waves as they come free; groups go to blocks from one ticket counter, and ONE block runs per CU.
+//   * the loader (wave 8) issues every global load of the loop -- the 196 eight-byte shadow pieces of the NEXT group's dirty envs (four
+//     rounds of 64 lanes) and the 32 masks of the group after it -- waits for them and writes them to LDS inside its own branch: nothing
+//     it loads is in a register where the two paths join, and the storing waves' path holds no vmcnt wait (k_render_dstore's waves
+//     carry ids and masks in registers across their stores and drain their store queue once per group; measured, the drain costs
+//     nothing -- profiles/render_store_queue/README.md -- the loader is here for what follows);
+//   * one workgroup barrier per group, reached by all nine waves after `if (loader) ... else ...`; ids in two buffers, masks (and what
+//     goes with them: the list of dirty envs, its length and take counter, the group's index) in three -- a buffer the loader writes
+//     between barriers k and k + 1 was last read between barriers k - 1 and k;
+//   * the loader lists the group's dirty envs (a ballot over the 32 masks); a storing wave takes its next env with one LDS atomic add
+//     by one lane, so the group's bytes spread over the waves as they come free (statically, wave w stores envs w, w + 8, w + 16,
+//     w + 24: 60 % of env-steps are clean and the slowest wave of a group carries about twice the mean);
+//   * groups come from ONE ticket counter, two consecutive groups per ticket (16 384 tickets per launch at 1 048 576 envs), in order:
+//     the chip's stores advance through the buffer as one compact window, as k_render_q's do -- with the static interleaved split a
+//     block runs as far ahead as its own groups let it.  The loader takes a ticket one ahead of the one it prefetches for (the spare
+//     rides in LDS, not in a register) and publishes every phase's group in LDS; all nine waves read "no more groups" from there
+//     behind the barrier and so run the same number of barriers.  Counters: words of the handle's render_tickets that k_render_q
+//     leaves alone; the last block to leave zeroes them, as there (its comment: two launches never share them; every ticket a block
+//     took has returned -- it went through LDS -- before the block departs).
+// The stored bytes are k_render_dstore's: the same masks select the same pieces (store_dirty_pieces).
+constexpr int DSTORE_LW_T = 9 * 64;                                    // 8 storing waves + the loader
+constexpr int DSTORE_LW_K = 2;                                         // groups per ticket
+constexpr int DSTORE_LW_COUNTER = 32 * 64, DSTORE_LW_DEPARTED = 33 * 64;     // words of render_tickets (k_render_q: rows 0 .. 8)
+__device__ __forceinline__ int64_t uniform64(int64_t v) {        // a wave-uniform value read from LDS, for the scalar unit
+    return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
+}
+template <int P>
+__global__ __launch_bounds__(DSTORE_LW_T) void k_render_dstore_lw(int64_t n, uint8_t* __restrict__ pixels, const uint8_t* __restrict__ shadow /* [n][49], row 0 = env 0 of this range */,
+                                                                  const uint64_t* __restrict__ dmask /* [n] */, const uint8_t* __restrict__ atlas, int n_tiles,
+                                                                  unsigned int* __restrict__ tickets) {
+    static_assert(P < LINE_BYTES, "pieces");
+    constexpr int G = 32, T = DSTORE_LW_T, W = 8, K = DSTORE_LW_K, ROUNDS = (DSTORE_PIECES + 63) / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_atlas[MAX_TILES * TILE_BYTES];
+    __shared__ __attribute__((aligned(8))) uint8_t s_tile[2][G * CELLS + 8];
+    __shared__ uint64_t s_pm[Pieces<P>::NP];
+    __shared__ uint16_t s_wl[W][Pieces<P>::NP];
+    __shared__ uint64_t s_dm3[3][G];
+    __shared__ uint32_t s_ct[VEC_PER_ENV];
+    __shared__ uint8_t s_list[3][G];                  // the group's dirty envs, ...
+    __shared__ unsigned int s_cnt[3], s_next[3];      // ... how many, and how many the storing waves have taken
+    __shared__ int64_t s_grp[3];                      // the group of the phase (>= ngroups: none, and none behind it)
+    __shared__ unsigned int s_spare;                  // the ticket taken ahead
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool loader = wave == W;
+    const int64_t ngroups = (n + G - 1) / G;
+    load_atlas_lds(s_atlas, atlas, n_tiles, tid, T);
+    init_piece_cells<P>(s_pm, tid, T);
+    init_chunk_table(s_ct, tid, T);
+    // One step of the loader, "iteration k" (k = -2, -1: the prologue): the ids of phase k + 1 (group g1, masks in buffer m1) into tile
+    // buffer tb and the masks of phase k + 2 into buffer m2, with the list, the counters and the group's index.  Every load is issued
+    // without a branch around it (a lane with nothing to load reads the range's first bytes), so that they are in flight together.
+    unsigned int* counter = tickets + DSTORE_LW_COUNTER;
+    int64_t g1 = ngroups;                             // (no phase -1)
+    auto loader_step = [&](int k, int m1, int tb, int m2) {
+        const int64_t end = n * CELLS;
+        const bool opens = (k + 2) % K == 0;          // every K-th phase opens a ticket: the spare one from LDS, the next spare into it below
+        int64_t g2 = g1 + 1;
+        unsigned int spare = 0;
+        if (opens) {
+            g2 = (int64_t)s_spare * K;
+            if (lane == 0) spare = atomicAdd(counter, 1u);
+        }
+        uint2 v[ROUNDS];
+        bool need[ROUNDS], tail = false;
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int p = r * 64 + lane, pc = p < DSTORE_PIECES ? p : DSTORE_PIECES - 1;
+            const int64_t base = g1 * G * CELLS + 8 * p;
+            // an 8-byte piece is loaded when an env it holds cells of is dirty (masks past the end of the range are 0)
+            need[r] = p < DSTORE_PIECES && g1 < ngroups && (s_dm3[m1][(8 * pc) / CELLS] || s_dm3[m1][(8 * pc + 7) / CELLS]);
+            const bool whole = base + 8 <= end;
+            tail |= need[r] && !whole;
+            v[r] = *(const uint2*)(shadow + (need[r] && whole ? base : 0));
+        }
+        const int64_t env = g2 * G + lane;
+        const bool live = lane < G && g2 < ngroups && env < n;
+        uint64_t m = dmask[live ? env : 0];
+        if (!live) m = 0;
+        if (__any(tail)) {                            // the range's ids end inside a piece: byte by byte (as k_render_dstore's load_piece)
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) {
+                const int64_t base = g1 * G * CELLS + 8 * (r * 64 + lane);
+                if (!need[r] || base + 8 <= end) continue;
+                uint32_t w[2] = {0u, 0u};
+                for (int i = 0; i < 8 && base + i < end; ++i) w[i >> 2] |= (uint32_t)shadow[base + i] << (8 * (i & 3));
+                v[r] = make_uint2(w[0], w[1]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int p = r * 64 + lane;
+            if (p < DSTORE_PIECES) *(uint2*)(s_tile[tb] + 8 * p) = need[r] ? v[r] : make_uint2(0u, 0u);
+        }
+        if (lane < G) s_dm3[m2][lane] = m;
+        const uint64_t dirty = __ballot(m != 0);
+        if (m) s_list[m2][__builtin_popcountll(dirty & ((1ull << lane) - 1))] = (uint8_t)lane;
+        if (lane == 0) {
+            s_cnt[m2] = (unsigned int)__builtin_popcountll(dirty);
+            s_next[m2] = 0;
+            s_grp[m2] = g2;
+            if (opens) s_spare = spare;
+        }
+        g1 = g2;
+    };
+    if (loader) {
+        if (lane == 0) s_spare = atomicAdd(counter, 1u);
+        wave_lds_sync();
+        loader_step(-2, 2, 1, 0);                     // phase 0's masks
+        wave_lds_sync();
+        loader_step(-1, 0, 0, 1);                     // phase 0's ids, phase 1's masks
+    }
+    __syncthreads();                                  // atlas, piece and chunk tables; phase 0's ids and masks, phase 1's masks
+    int buf = 0, mb = 0;
+    for (int k = 0;; ++k, buf ^= 1, mb = mb == 2 ? 0 : mb + 1) {
+        const int64_t g = uniform64(s_grp[mb]);
+        if (g >= ngroups) break;
+        if (loader) {
+            const int m1 = mb == 2 ? 0 : mb + 1, m2 = m1 == 2 ? 0 : m1 + 1;
+            loader_step(k, m1, buf ^ 1, m2);
+        } else {
+            const int64_t env0 = g * G;
+            const unsigned int cnt = __builtin_amdgcn_readfirstlane(s_cnt[mb]);
+            for (;;) {
+                unsigned int i = 0;
+                if (lane == 0) i = atomicAdd(&s_next[mb], 1u);
+                i = __builtin_amdgcn_readfirstlane(i);
+                if (i >= cnt) break;
+                const int e = __builtin_amdgcn_readfirstlane(s_list[mb][i]);
+                store_dirty_pieces<P>(s_dm3[mb][e], s_pm, s_wl[wave], s_atlas, s_ct, s_tile[buf] + e * CELLS, (u32x4*)(pixels + (env0 + e) * PIX_BYTES), lane);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == W * 64) {
+        unsigned int* departed = tickets + DSTORE_LW_DEPARTED;
+        if (atomicAdd(departed, 1u) == gridDim.x - 1) { atomicExch(counter, 0u); atomicExch(departed, 0u); }
     }
 }
 #endif  // __HIPCC__

@@ -496,8 +496,10 @@ int bbai_get_done_actions(bbai_env* env);
  *   "render_target_tile_size"   8 (default), 16 or 32 (anything else: BBAI_ERR_ARG): the frame size of the NEXT bbai_set_render_target
  *                       registration, uint8[N][7 ts][7 ts][3] -- at 16 / 32 the target is bbai_render_view's
  *   "render_delta_sched", "render_delta_tpb", "render_delta_bpc"   the delta render's work split (0 = interleaved groups per
- *                       block, 1 = contiguous ranges), threads per block (512 default / 1024) and blocks per CU (0 = 3 of 512
- *                       threads, 1 of 1024)
+ *                       block, 1 = contiguous ranges, 2 as 0), threads per block (512 default / 1024) and blocks per CU (0 = 3 of 512
+ *                       threads, 1 of 1024).  The store-only render behind a step that found the dirty cells, 64-byte pieces:
+ *                       "render_delta_sched" 0 / 1 = groups handed out by a ticket counter, 2 = the static interleaved split (the
+ *                       previous kernel, kept as the reference); "render_delta_bpc" 0 = 1 block per CU with the tickets, 3 without
  *   "step_prio", "pregen_group", "pregen_blocks", "pregen_min", "consume_fused"   as BBAI_STEP_PRIO / BBAI_PREGEN_GROUP /
  *                       BBAI_PREGEN_BLOCKS / BBAI_PREGEN_MIN / BBAI_CONSUME_FUSED
  *   "step_render_split" bbai_step_render / bbai_rollout with pixels: 1 = step the batch in two halves, the second under the first half's

@@ -107,7 +107,7 @@ def counters(d, names):
 
 
 SQ_NAMES = ("SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_WAIT_INST_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE",
-            "SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU")
+            "SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_BUSY_CYCLES", "SQ_INSTS_VMEM_WR", "SQ_INSTS_LDS")
 
 
 def main():
@@ -185,7 +185,7 @@ def main():
                 wc = c.get("SQ_WAVE_CYCLES") or 1.0
                 f.write("%-34s launches=%4d %s\n" % (k, max(v[1] for v in sq[k].values()), json.dumps({n: round(v) for n, v in c.items()})))
                 f.write("%-34s   waiting %.0f %% of wave cycles, issuing %.0f %%, VALU %.0f %% of the issuing cycles%s\n" % (
-                    "", 100 * c.get("SQ_WAIT_ANY", 0) / wc, 100 * c.get("SQ_ACTIVE_INST_ANY", 0) / wc,
+                    "", 100 * c.get("SQ_WAIT_ANY", c.get("SQ_WAIT_INST_ANY", 0)) / wc, 100 * c.get("SQ_ACTIVE_INST_ANY", 0) / wc,
                     100 * c.get("SQ_ACTIVE_INST_VALU", 0) / (c.get("SQ_ACTIVE_INST_ANY") or 1.0),
                     (", %.0f VALU instructions per wave-launch unit" % c["SQ_INSTS_VALU"]) if "SQ_INSTS_VALU" in c else ""))
 
@@ -209,7 +209,7 @@ def main():
     print("\n".join(lines))
     for k in sorted(sq):
         c = {n: v[0] for n, v in sq[k].items()}
-        print("SQ %-30s wait %.0f %% issue %.0f %% valu/issue %.0f %%" % (k, 100 * c.get("SQ_WAIT_ANY", 0) / (c.get("SQ_WAVE_CYCLES") or 1),
+        print("SQ %-30s wait %.0f %% issue %.0f %% valu/issue %.0f %%" % (k, 100 * c.get("SQ_WAIT_ANY", c.get("SQ_WAIT_INST_ANY", 0)) / (c.get("SQ_WAVE_CYCLES") or 1),
                                                                       100 * c.get("SQ_ACTIVE_INST_ANY", 0) / (c.get("SQ_WAVE_CYCLES") or 1),
                                                                       100 * c.get("SQ_ACTIVE_INST_VALU", 0) / (c.get("SQ_ACTIVE_INST_ANY") or 1)))
 
