@@ -6,6 +6,9 @@
 //   k_demo_jobs   one chunk of history of a POOL of envs that play listed seeds (DemoStore.collect_seeds) -> the episodes that ended,
 //                 kept or dropped, and the next seed of every env that finished
 //   k_demo_pack_list  k_demo_pack for a list of (stream, first step, length) records in a ring of history chunks
+//   k_demo_replay_feed / k_demo_replay_judge  a POOL of envs that plays a store's demonstrations back (DemoStore.replay):
+//                 before the step, compare every playing env's observation with the recorded frame and hand out the recorded action;
+//                 behind it, score the envs that were fed and give the free ones the next demos
 // The two copies write ALIGNED 16-byte chunks of one contiguous destination; a chunk's bytes come from at most two source
 // runs (147-byte history rows in k_demo_pack, whole demos in k_demo_batch), each fetched as two aligned 16-byte loads
 // and byte-aligned in registers.  Every unaligned 16-byte window that is fetched lies INSIDE a source run (a chunk that
@@ -209,6 +212,147 @@ __global__ __launch_bounds__(64) void k_demo_jobs(int64_t n, int chunk, const ui
         }
     }
     ids_out[i] = id;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_demo_replay_feed : a GROUP of 16 lanes = one env of a POOL that plays a store's demonstrations back (DemoStore.replay: DemoAgent of
+// babyai/utils/agent.py:101-137, which asserts at every frame that the env shows the recorded observation).  Env i plays demo job[i] (< 0:
+// nobody's) and stands at its frame pos[i]; it is FED iff 0 <= job < n_demos and 0 <= pos < the demo's length and the frame
+// f = offset[job] + pos lies in [0, frames) -- anything else never becomes an address, and the env gets BBAI_ACTION_HOLD and fed = 0 with
+// the results untouched.  A fed env's current observation (row i of `image` [n][147] and of `dir`) is compared with frame f of the store:
+// lanes 0..9 of the group take the ten 16-byte windows [0,16) .. [128,144), [131,147) of the two 147-byte rows -- every window lies INSIDE
+// its row, so the aligned 16-byte words around it (DemoWindow) stay inside an allocation that starts 16-byte aligned and is a multiple of 16
+// bytes long, at any of the 16 byte phases of 147 i and 147 f; consecutive groups read consecutive env rows -- lane 10 the direction bytes,
+// and at pos == 0 lanes 0..8 the nine 8-byte pieces of the two 72-byte token rows (both 8-byte aligned).  "Differs" is reduced by one ballot
+// each; the group's lane 0 keeps the demo's books -- mismatches, first_mismatch (set while it is < 0), mission_ok at pos == 0 -- with plain
+// loads and stores: one group owns one demo at a time.  It also writes actions_out[i] = the recorded action and fed[i] = 1.
+// ------------------------------------------------------------------------------------------
+constexpr int REPLAY_GROUP = 16;                // lanes per env
+constexpr int REPLAY_ENVS = DEMO_BLOCK / REPLAY_GROUP;      // envs per block
+constexpr uint8_t REPLAY_HOLD = 8;              // include/bbai.h BBAI_ACTION_HOLD
+
+struct DemoReplayFeedArgs {
+    int64_t n, n_demos, frames;
+    const uint8_t* __restrict__ image; const uint8_t* __restrict__ dir; const uint8_t* __restrict__ tokens;       // the pool's current rows
+    const int32_t* __restrict__ job; const int32_t* __restrict__ pos;
+    const int64_t* __restrict__ offset;
+    const uint8_t* __restrict__ s_image; const uint8_t* __restrict__ s_dir; const uint8_t* __restrict__ s_action; const uint8_t* __restrict__ s_tokens;
+    int32_t* mismatches; int32_t* first_mismatch; uint8_t* mission_ok;
+    uint8_t* actions_out; uint8_t* fed;
+};
+
+__device__ __forceinline__ bool demo_differs(const u32x4 a, const u32x4 b) {
+    return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u;
+}
+
+__global__ __launch_bounds__(DEMO_BLOCK) void k_demo_replay_feed(DemoReplayFeedArgs a) {
+    const int tid = threadIdx.x;
+    const int sub = tid & (REPLAY_GROUP - 1);
+    const int64_t i = (int64_t)blockIdx.x * REPLAY_ENVS + (tid >> 4);
+    int64_t d = -1, f = 0;
+    int32_t p = 0;
+    if (i < a.n) {                              // (the group's 16 lanes read the same words: one broadcast load each)
+        const int32_t j = a.job[i];
+        p = a.pos[i];
+        if (j >= 0 && (int64_t)j < a.n_demos && p >= 0) {
+            const int64_t lo = a.offset[j], hi = a.offset[j + 1];
+            f = lo + p;
+            if (f < hi && f >= 0 && f < a.frames) d = j;
+        }
+    }
+    const bool play = d >= 0;
+    bool diff = false, tdiff = false;
+    if (play) {
+        if (sub < 10) {
+            const uint32_t at = sub < 9 ? (uint32_t)sub * 16u : DEMO_ROW - 16u;
+            DemoWindow we, ws;
+            we.load(a.image + i * (int64_t)DEMO_ROW + at);
+            ws.load(a.s_image + f * (int64_t)DEMO_ROW + at);
+            diff = demo_differs(we.get(), ws.get());
+        } else if (sub == 10) {
+            diff = a.dir[i] != a.s_dir[f];
+        }
+        if (p == 0 && sub < 9) {
+            const uint2 te = ((const uint2*)(a.tokens + i * 72))[sub], ts = ((const uint2*)(a.s_tokens + d * 72))[sub];
+            tdiff = ((te.x ^ ts.x) | (te.y ^ ts.y)) != 0u;
+        }
+    }
+    const int shift = (tid & 63) & ~(REPLAY_GROUP - 1);        // the group's first lane in its wave
+    const bool any = ((__ballot(diff) >> shift) & 0xffffull) != 0ull;
+    const bool tany = ((__ballot(tdiff) >> shift) & 0xffffull) != 0ull;
+    if (sub != 0 || i >= a.n) return;
+    if (play) {
+        if (any) {
+            a.mismatches[d] += 1;
+            if (a.first_mismatch[d] < 0) a.first_mismatch[d] = p;
+        }
+        if (p == 0) a.mission_ok[d] = tany ? 0 : 1;
+    }
+    a.actions_out[i] = play ? a.s_action[f] : REPLAY_HOLD;
+    a.fed[i] = play ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_demo_replay_judge : lane = env, behind the step that took k_demo_replay_feed's actions; modelled on k_demo_jobs.  It acts on FED envs
+// only: a held env's done / reward64 entries are stale by the HOLD contract, and a reseeded env's done reads 1 until its first real step.  A
+// fed env advances pos; with done set its demo's done_at = played = pos and return64 = the env's reward64, bit for bit; with the demo used up
+// and no done, played = pos, done_at = 0, return64 = 0.0; either way the env gives its demo up (job = -1: WAITING, which is what idle is).
+// With claim != 0 every env with job < 0 -- those that finished just now included -- claims the next position of the job list: one ballot
+// and one returning add per wave, none per lane; position k < n_jobs gives job = job_demo[k] (k itself where job_demo is null), pos = 0,
+// ids_out[i] = i and seeds_out[i] = job_seeds[k] for bbai_reseed; every other env gets ids_out[i] = -1.  With claim == 0 nothing is
+// claimed and ids_out / seeds_out are not touched.  counters: [0] job cursor (in / out; may pass n_jobs by the claims that found nothing),
+// [1] demos finished (running total; one add per wave that has any).
+// ------------------------------------------------------------------------------------------
+struct DemoReplayJudgeArgs {
+    int64_t n, n_demos, n_jobs; int claim;
+    const uint8_t* __restrict__ fed; const uint8_t* __restrict__ done; const double* __restrict__ reward64;
+    int32_t* job; int32_t* pos;
+    const int64_t* __restrict__ offset;
+    int32_t* played; int32_t* done_at; double* return64;
+    const int32_t* __restrict__ job_demo; const uint64_t* __restrict__ job_seeds;
+    int64_t* ids_out; uint64_t* seeds_out; unsigned long long* counters;
+};
+
+__global__ __launch_bounds__(64) void k_demo_replay_judge(DemoReplayJudgeArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int lane = (int)threadIdx.x;
+    bool fin = false, want = false;
+    if (i < a.n) {
+        int32_t j = a.job[i];
+        if (a.fed[i] != 0 && j >= 0 && (int64_t)j < a.n_demos) {
+            const int32_t p = a.pos[i] + 1;
+            a.pos[i] = p;
+            const bool dn = a.done[i] != 0;
+            if (dn || (int64_t)p >= a.offset[j + 1] - a.offset[j]) {
+                a.played[j] = p;
+                a.done_at[j] = dn ? p : 0;
+                a.return64[j] = dn ? a.reward64[i] : 0.0;
+                a.job[i] = j = -1;
+                fin = true;
+            }
+        }
+        want = a.claim != 0 && j < 0;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long fin_bal = __ballot(fin), want_bal = __ballot(want);
+    unsigned long long base = 0;
+    if (lane == 0) {
+        if (fin_bal) atomicAdd(a.counters + 1, (unsigned long long)__popcll(fin_bal));
+        if (want_bal) base = atomicAdd(a.counters, (unsigned long long)__popcll(want_bal));
+    }
+    base = __shfl(base, 0);
+    if (i >= a.n || a.claim == 0) return;
+    int64_t id = -1;
+    if (want) {
+        const unsigned long long next = base + (unsigned long long)__popcll(want_bal & below);
+        if (next < (unsigned long long)a.n_jobs) {
+            id = i;
+            a.seeds_out[i] = a.job_seeds[next];
+            a.job[i] = a.job_demo ? a.job_demo[next] : (int32_t)next;
+            a.pos[i] = 0;
+        }
+    }
+    a.ids_out[i] = id;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -23,7 +23,8 @@
 //                     batch into the target registered at that size, only the 64-byte pieces whose cells changed.  (view_delta_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
-//   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch / k_demo_jobs / k_demo_pack_list: demonstrations that stay on the device.
+//   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch / k_demo_jobs / k_demo_pack_list: demonstrations that stay on the device;
+//                     k_demo_replay_feed / k_demo_replay_judge: a pool of envs plays them back (include/bbai_demo_replay.h).
 //   bbai_statek.hpp   k_state_save / k_state_load / k_state_tokens: device snapshots of listed envs (bbai_save_state, bbai_load_state).
 //   bbai_reseedk.hpp  k_reseed_seed / k_reseed_consume: env.seed(s); env.reset() for listed envs of a live batch (bbai_reseed).
 //
@@ -39,6 +40,7 @@
 __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase timers of the expert (bbai_bot.hpp)
 #endif
 #include "../../include/bbai.h"
+#include "../../include/bbai_demo_replay.h"
 #include "bbai_types.hpp"
 #include "bbai_target.hpp"
 #include "bbai_kernels.hpp"
@@ -2090,6 +2092,45 @@ int bbai_demo_pack_list(int64_t count, int64_t frames, int64_t n_streams, int ch
     a.image = image_out; a.dir = dir_out; a.action = action_out; a.tokens = tokens_out;
     if (a.img_blocks + a.meta_blocks + tok_blocks > 0x7fffffff) ARG_FAIL("list too large for one launch");
     hipLaunchKernelGGL(k_demo_pack_list, dim3((unsigned)(a.img_blocks + a.meta_blocks + tok_blocks)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+// The replay entries (include/bbai_demo_replay.h): one tick of a pool that plays a store back = feed, bbai_step, judge.
+int bbai_demo_replay_feed(int64_t n, const uint8_t* image, const uint8_t* dir, const uint8_t* tokens, const int32_t* job, const int32_t* pos,
+                          int64_t n_demos, int64_t frames, const int64_t* offset, const uint8_t* store_image, const uint8_t* store_dir,
+                          const uint8_t* store_action, const uint8_t* store_tokens, int32_t* mismatches, int32_t* first_mismatch, uint8_t* mission_ok,
+                          uint8_t* actions_out, uint8_t* fed_out, void* stream) {
+    if (n < 0 || n > 0x7fffffff || n_demos < 1 || n_demos > 0x7fffffff || frames < 1) ARG_FAIL("pool, demo or frame count out of range");
+    if (n == 0) return BBAI_OK;
+    if (!image || !dir || !tokens || !job || !pos || !offset || !store_image || !store_dir || !store_action || !store_tokens || !mismatches ||
+        !first_mismatch || !mission_ok || !actions_out || !fed_out) ARG_FAIL("null pointer");
+    if (!aligned16(image) || !aligned16(store_image)) ARG_FAIL("image arrays must be 16-byte aligned");
+    if (((uintptr_t)tokens | (uintptr_t)store_tokens) & 7u) ARG_FAIL("token rows must be 8-byte aligned");
+    DemoReplayFeedArgs a;
+    a.n = n; a.n_demos = n_demos; a.frames = frames;
+    a.image = image; a.dir = dir; a.tokens = tokens; a.job = job; a.pos = pos; a.offset = offset;
+    a.s_image = store_image; a.s_dir = store_dir; a.s_action = store_action; a.s_tokens = store_tokens;
+    a.mismatches = mismatches; a.first_mismatch = first_mismatch; a.mission_ok = mission_ok; a.actions_out = actions_out; a.fed = fed_out;
+    hipLaunchKernelGGL(k_demo_replay_feed, dim3((unsigned)((n + REPLAY_ENVS - 1) / REPLAY_ENVS)), dim3(DEMO_BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+int bbai_demo_replay_judge(int64_t n, const uint8_t* fed, const uint8_t* done, const double* reward64, int32_t* job, int32_t* pos, int64_t n_demos,
+                           const int64_t* offset, int32_t* played, int32_t* done_at, double* return64, int claim, const int32_t* job_demo,
+                           const uint64_t* job_seeds, int64_t n_jobs, int64_t* ids_out, uint64_t* seeds_out, uint64_t* counters, void* stream) {
+    if (n < 0 || n > 0x7fffffff || n_demos < 1 || n_demos > 0x7fffffff || n_jobs < 0 || n_jobs > 0x7fffffff)
+        ARG_FAIL("pool, demo or job count out of range");
+    if (n == 0) return BBAI_OK;
+    if (!fed || !done || !reward64 || !job || !pos || !offset || !played || !done_at || !return64 || !counters) ARG_FAIL("null pointer");
+    if (claim && (!ids_out || !seeds_out || (n_jobs && !job_seeds))) ARG_FAIL("a claim needs ids_out, seeds_out and the job list");
+    DemoReplayJudgeArgs a;
+    a.n = n; a.n_demos = n_demos; a.n_jobs = n_jobs; a.claim = claim;
+    a.fed = fed; a.done = done; a.reward64 = reward64; a.job = job; a.pos = pos; a.offset = offset;
+    a.played = played; a.done_at = done_at; a.return64 = return64; a.job_demo = job_demo; a.job_seeds = job_seeds;
+    a.ids_out = ids_out; a.seeds_out = seeds_out; a.counters = (unsigned long long*)counters;
+    hipLaunchKernelGGL(k_demo_replay_judge, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }

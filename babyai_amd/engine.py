@@ -109,11 +109,18 @@ ABI = {
 }
 EXPORTED_SYMBOLS = tuple(ABI)
 
+# include/bbai_demo_replay.h, the companion header of the replay entries, the same way (tests/test_demo_replay_abi.py holds the rows to it)
+ABI_REPLAY = {
+    "bbai_demo_replay_feed": (I32, [I64, P, P, P, P, P, I64, I64] + [P] * 11),
+    "bbai_demo_replay_judge": (I32, [I64, P, P, P, P, P, I64, P, P, P, P, I32, P, P, I64, P, P, P, P]),
+}
+REPLAY_SYMBOLS = tuple(ABI_REPLAY)
+
 
 def bind(lib):
-    """Give every entry of ABI that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older experiment
-    builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
-    for name, (restype, argtypes) in ABI.items():
+    """Give every entry of ABI and ABI_REPLAY that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
+    experiment builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

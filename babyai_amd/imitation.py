@@ -18,6 +18,10 @@ steps in torch ops, as `rollout.gae_env_major` does, so that the pin tests run w
 
 `DemoStore.collect_seeds` (one demonstration per LISTED seed, a pool of envs playing the list), `DemoStore.extend` and
 `grow_training_set` are scripts/train_intelligent_expert.py:106-176 on the same footing (bbai_demo_jobs / bbai_demo_pack_list).
+
+`DemoStore.replay` plays a store back, every demo in the episode its seed starts, and reports per demo whether the engine reproduces it
+frame for frame and what it returns: `DemoAgent` (babyai/utils/agent.py:101-137) and scripts/evaluate.py:45-57 for a whole store on a pool
+of envs (include/bbai_demo_replay.h bbai_demo_replay_feed / bbai_demo_replay_judge).
 """
 import ctypes
 
@@ -288,6 +292,28 @@ class DemoStore(object):
         parks until the round's reseed instead of playing on through rows nobody reads -- the same (store, kept), less generator and
         expert work."""
         return _collect_seeds(cls, env_name, seeds, device, pool, chunk, env, reseed_levels)
+
+    def replay(self, env_name, seeds, device="cuda:0", pool=32768, reseed_every=None, poll_every=16, env=None):
+        """Play every demonstration back in the episode its seed starts and report, per demo, whether the engine reproduces it: `DemoAgent`
+        (babyai/utils/agent.py:101-137) and the `--demos` evaluation built on it (scripts/evaluate.py:45-57), for the whole store at once and
+        without the assert -- a mismatch is counted, the recorded actions go on being applied, frames behind `done` are never compared.
+        `seeds`: one per demo (what `engine.seeds_u64` takes; ValueError for another number): demo j is replayed in the episode that
+        `env.seed(seeds[j]); env.reset()` starts -- after `store, kept = DemoStore.collect_seeds(name, s)` that is `np.asarray(s)[kept]`.
+        -> DemoReplay (played, done_at, return64, mismatches, first_mismatch, mission_ok per demo; `.exact`, `.logs()`).
+        min(pool, D') envs (auto_reset=False) play the D' non-empty demos -- a zero-length demo is reported as played = done_at = 0 --; an env
+        that has finished one waits for the next reseed tick.  `reseed_every` = r: the free envs claim their next demos and are reseeded
+        (levels=1) every r ticks; None = 16, chosen from profiles/demo_replay/demo_replay_bench.jsonl (tools/demo_replay_bench.py): a reseed
+        call costs 0.4-0.7 ms of device time whatever it finds to do, ten times a tick's feed + step + judge, so at pools 4 096 / 32 768
+        r = 16 replays BossLevel (84 frames per demo) 1.74x / 1.23x as fast as r = 4 and 4.8x / 2.1x as fast as r = 1, and GoToLocal (5
+        frames per demo, where waiting costs most) within 5 % / 2 % of its best, r = 4; at pool 131 072 r makes no difference.
+        `poll_every`: the host reads the two counters every that many ticks and stops when every demo has finished; nothing else
+        synchronises.  The results do not depend on pool, reseed_every or poll_every.  RuntimeError when (ceil(D' / P) + 1) * (the longest
+        demo + r) + poll_every ticks do not finish the store.  `env`: a prepared pool as for collect_seeds(env=...) -- num_envs (<= D'),
+        device, image, direction, reward64, done, instr, step(actions) that honours HOLD bytes, reseed(ids, seeds, levels=), close() --
+        created on the seeds of the first num_envs non-empty demos, auto_reset=False, token rows on, reset() behind it; it stays the
+        caller's.  A pool in the reference's done-action mode is refused (ValueError): a store does not say whether a recorded `done` was
+        the enum member."""
+        return _replay(self, env_name, seeds, device, pool, reseed_every, poll_every, env)
 
     # ---- ways out ----
     def to_reference(self, pack=None):
@@ -624,6 +650,200 @@ def _collect_seeds(cls, env_name, seeds, device, pool, chunk, env, reseed_levels
             torch.cuda.current_stream(dev).synchronize()                       # the ring may be freed (and the env closed) after this
         return result, jobs[order]
     finally:
+        if own:
+            env.close()
+
+
+HOLD = 8                    # include/bbai.h BBAI_ACTION_HOLD
+REPLAY_RESEED_EVERY = 16    # DemoStore.replay(reseed_every=None): see its docstring for the measurement behind it
+
+
+def replay_feed(image, direction, instr, job, pos, store, mismatches, first_mismatch, mission_ok, actions_out, fed):
+    """Before the step of a pool that plays `store` back (include/bbai_demo_replay.h bbai_demo_replay_feed): image uint8[n, 7, 7, 3], direction
+    uint8[n] and instr uint8[n, 72] = the pool's current observations and token rows; job int32[n] = the demo env i plays (< 0: none), pos
+    int32[n] = the frame it stands at.  An env with 0 <= job < len(store) and 0 <= pos < the demo's length is FED: its observation is compared
+    with the demo's frame `pos` (a difference adds 1 to mismatches[job] and sets first_mismatch[job] = pos while that is -1), at pos == 0 its
+    token row with the demo's (mission_ok[job] = 1 / 0), actions_out[i] = the recorded action and fed[i] = 1.  Every other env gets
+    actions_out[i] = HOLD and fed[i] = 0.  mismatches / first_mismatch int32[D], mission_ok uint8[D], actions_out / fed uint8[n], all written
+    in place.  ROCm tensors: k_demo_replay_feed; host tensors: the same in torch ops."""
+    import torch
+    n, D, F = int(job.shape[0]), len(store), store.num_frames
+    if image.is_cuda:
+        assert pos.shape[0] == actions_out.shape[0] == fed.shape[0] == direction.shape[0] == n and tuple(instr.shape) == (n, TOK_MAX)
+        assert image.numel() == n * 147 and mismatches.shape[0] == first_mismatch.shape[0] == mission_ok.shape[0] == D
+        _launch("bbai_demo_replay_feed", n, (image, torch.uint8), (direction, torch.uint8), (instr, torch.uint8), (job, torch.int32), (pos, torch.int32),
+                D, F, (store.offset, torch.int64), (store.image, torch.uint8), (store.direction, torch.uint8), (store.action, torch.uint8),
+                (store.tokens, torch.uint8), (mismatches, torch.int32), (first_mismatch, torch.int32), (mission_ok, torch.uint8),
+                (actions_out, torch.uint8), (fed, torch.uint8))
+        return
+    j, p = job.to(torch.int64), pos.to(torch.int64)
+    jc = j.clamp(0, max(D - 1, 0))
+    lo = store.offset[jc]
+    f = lo + p
+    play = (j >= 0) & (j < D) & (p >= 0) & (f < store.offset[jc + 1]) & (f < F)
+    env = play.nonzero().reshape(-1)
+    d, f, p = jc[env], f[env], p[env]
+    diff = (image[env].reshape(-1, 147) != store.image[f].reshape(-1, 147)).any(dim=1) | (direction[env] != store.direction[f])
+    mismatches.index_add_(0, d, diff.to(torch.int32))
+    new = diff & (first_mismatch[d] < 0)
+    first_mismatch[d[new]] = p[new].to(torch.int32)
+    at0 = p == 0
+    mission_ok[d[at0]] = (instr[env[at0]] == store.tokens[d[at0]]).all(dim=1).to(torch.uint8)
+    actions_out.fill_(HOLD)
+    actions_out[env] = store.action[f]
+    fed.zero_()
+    fed[env] = 1
+
+
+def replay_judge(fed, done, reward64, job, pos, offset, played, done_at, return64, claim, job_demo, job_seeds, ids_out, seeds_out, counters):
+    """Behind that step (bbai_demo_replay_judge): fed envs ONLY -- a held env's done / reward64 are stale, a reseeded env's done reads 1 until its
+    first real step -- advance pos; with done set the demo's done_at = played = pos and return64 = the env's reward64; with the demo used up
+    and no done, played = pos, done_at = 0, return64 = 0; either way job = -1 (waiting).  `claim`: every env with job < 0 then takes the next
+    position k of the job list (job_demo int32[J], job_seeds int64[J]): job = job_demo[k], pos = 0, ids_out[i] = i, seeds_out[i] =
+    job_seeds[k] while k < J, ids_out[i] = -1 for every env that took nothing; without `claim`, ids_out / seeds_out are left alone.  counters
+    int64[2] = the job cursor (in / out, may pass J) and the demos finished (running total).  ROCm tensors: k_demo_replay_judge, which hands
+    positions out wave by wave in the order the waves arrive; host tensors: the same in torch ops, positions in env order."""
+    import torch
+    n, D, J = int(job.shape[0]), int(offset.shape[0]) - 1, int(job_seeds.shape[0])
+    if fed.is_cuda:
+        assert fed.shape[0] == done.shape[0] == reward64.shape[0] == pos.shape[0] == ids_out.shape[0] == seeds_out.shape[0] == n
+        assert played.shape[0] == done_at.shape[0] == return64.shape[0] == D and job_demo.shape[0] == J and counters.shape[0] == 2
+        _launch("bbai_demo_replay_judge", n, (fed, torch.uint8), (done, torch.uint8), (reward64, torch.float64), (job, torch.int32), (pos, torch.int32),
+                D, (offset, torch.int64), (played, torch.int32), (done_at, torch.int32), (return64, torch.float64), 1 if claim else 0,
+                (job_demo, torch.int32), (job_seeds, torch.int64), J, (ids_out, torch.int64), (seeds_out, torch.int64), (counters, torch.int64))
+        return counters
+    env = ((fed != 0) & (job >= 0) & (job < D)).nonzero().reshape(-1)
+    pos[env] += 1
+    d, p = job[env].to(torch.int64), pos[env]
+    dn = done[env] != 0
+    end = dn | (p >= offset[d + 1] - offset[d])
+    env, d, p, dn = env[end], d[end], p[end], dn[end]
+    played[d] = p
+    done_at[d] = torch.where(dn, p, torch.zeros_like(p))
+    return64[d] = torch.where(dn, reward64[env], torch.zeros_like(reward64[env]))
+    job[env] = -1
+    counters[1] += len(env)
+    if claim:
+        free = (job < 0).nonzero().reshape(-1)
+        k = int(counters[0]) + torch.arange(len(free))
+        got, k = free[k < J], k[k < J]
+        ids_out.fill_(-1)
+        ids_out[got] = got
+        seeds_out[got] = job_seeds[k]
+        job[got] = job_demo[k]
+        pos[got] = 0
+        counters[0] += len(free)
+    return counters
+
+
+class DemoReplay(object):
+    """What `DemoStore.replay` found, per demo, on the store's device and in the store's order: played int32 (actions of the demo that were
+    applied; below the length iff the episode ended early), done_at int32 (the number of actions after which `done` arrived; 0 = not within
+    the demo), return64 float64 (the env's reward of that step, bit for bit; 0.0 with done_at == 0), mismatches int32 (played frames whose
+    (image, direction) differ from the recorded ones), first_mismatch int32 (the first such frame, -1 = none), mission_ok uint8 (the env's
+    token row at frame 0 equals the store's); `length` int32 and `seeds` (uint64 on the host) as given."""
+
+    def __init__(self, played, done_at, return64, mismatches, first_mismatch, mission_ok, length, seeds):
+        self.played, self.done_at, self.return64 = played, done_at, return64
+        self.mismatches, self.first_mismatch, self.mission_ok = mismatches, first_mismatch, mission_ok
+        self.length, self.seeds = length, seeds
+
+    def __len__(self):
+        return int(self.played.shape[0])
+
+    @property
+    def exact(self):
+        """The demo is the engine's episode of its seed, frame for frame and to its end."""
+        return (self.done_at == self.length) & (self.mismatches == 0) & (self.mission_ok != 0)
+
+    def logs(self):
+        """The shape `evaluate` logs (babyai/evaluate.py:40-46)."""
+        return {"num_frames_per_episode": self.played.cpu().tolist(), "return_per_episode": self.return64.cpu().tolist(),
+                "seed_per_episode": [int(s) for s in self.seeds]}
+
+
+def _replay(store, env_name, seeds, device, pool, reseed_every, poll_every, env):
+    """`DemoStore.replay`.  The D' non-empty demos are the jobs, in the store's order; P = min(pool, D') envs (auto_reset=False, HOLD on, token
+    rows on) start on the first P of them.  One tick: replay_feed (compare, hand out the recorded actions, HOLD for the rest), env.step,
+    replay_judge (score the fed envs; on every r-th tick the free envs claim the next jobs) and, on those ticks, env.reseed(ids_out,
+    seeds_out, levels=1) with the device lists the judge wrote -- no host data hands out work.  The host reads the two counters every
+    `poll_every` ticks and stops at finished == D'; once the cursor has passed D' nothing can be claimed and the claims and reseeds stop."""
+    import torch
+    from .engine import seeds_u64
+    seeds_h = seeds_u64(seeds, "replay")
+    D = len(store)
+    if len(seeds_h) != D:
+        raise ValueError("replay: %d seeds for %d demonstrations" % (len(seeds_h), D))
+    r = REPLAY_RESEED_EVERY if reseed_every is None else int(reseed_every)
+    poll = int(poll_every)
+    if r < 1 or poll < 1 or (env is None and int(pool) < 1):
+        raise ValueError("replay: pool, reseed_every and poll_every must be at least 1")
+    lens = store.lengths
+    jobs_h = np.flatnonzero(lens > 0).astype(np.int32)
+    J = len(jobs_h)
+    dev = store.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    played, done_at, mismatches = torch.zeros(D, **i32), torch.zeros(D, **i32), torch.zeros(D, **i32)
+    first_mismatch = torch.full((D,), -1, **i32)
+    return64 = torch.zeros(D, dtype=torch.float64, device=dev)
+    mission_ok = torch.zeros(D, dtype=torch.uint8, device=dev)
+    rep = DemoReplay(played, done_at, return64, mismatches, first_mismatch, mission_ok, torch.as_tensor(lens.astype(np.int32), device=dev), seeds_h)
+    if J == 0:
+        return rep
+    job_seeds_h = seeds_h[jobs_h]
+    own = env is None
+    if own:
+        from .engine import BatchedBabyAIEnv
+        P = min(int(pool), J)
+        env = BatchedBabyAIEnv(env_name, P, device=device, seeds=job_seeds_h[:P], auto_reset=False)
+    hold_before = None
+    try:
+        P = int(env.num_envs)
+        if torch.device(env.device) != dev:
+            raise ValueError("replay: the store is on %s, the pool on %s" % (dev, env.device))
+        if P > J:
+            raise ValueError("replay: %d envs for %d non-empty demonstrations" % (P, J))
+        if getattr(env, "done_actions", False):
+            raise ValueError("replay: the pool is in the reference's done-action mode; a store does not say whether a recorded `done` was the "
+                             "enum member, so such a replay is undefined")
+        if own:
+            env.enable_instr_tokens()
+            env.reset()
+        if hasattr(env, "set_option"):
+            hold_before = env.get_option("step_hold")
+            env.set_option("step_hold", 1)
+        job_demo = torch.as_tensor(jobs_h, device=dev)
+        job_seeds = torch.as_tensor(job_seeds_h.view(np.int64), device=dev)
+        job, pos = job_demo[:P].clone(), torch.zeros(P, **i32)
+        actions, fed = torch.full((P,), HOLD, dtype=torch.uint8, device=dev), torch.zeros(P, dtype=torch.uint8, device=dev)
+        ids_out, seeds_out = torch.full((P,), -1, dtype=torch.int64, device=dev), torch.zeros(P, dtype=torch.int64, device=dev)
+        counters = torch.as_tensor(np.array([P, 0], dtype=np.int64), device=dev)
+        budget = (-(-J // P) + 1) * (int(lens.max()) + r) + poll
+        tick, claiming = 0, P < J
+        while True:
+            if tick >= budget:
+                raise RuntimeError("replay: %d ticks and not every demonstration finished (a pool that never reports `done`?)" % tick)
+            with _Timed(dev, "feed"):
+                replay_feed(env.image, env.direction, env.instr, job, pos, store, mismatches, first_mismatch, mission_ok, actions, fed)
+            with _Timed(dev, "step"):
+                env.step(actions)
+            tick += 1
+            claim = claiming and tick % r == 0
+            with _Timed(dev, "judge"):
+                replay_judge(fed, env.done, env.reward64, job, pos, store.offset, played, done_at, return64, claim, job_demo, job_seeds,
+                             ids_out, seeds_out, counters)
+            if claim:
+                with _Timed(dev, "reseed"):
+                    env.reseed(ids_out, seeds_out, levels=1)
+            if tick % poll == 0:
+                c = counters.cpu().numpy()                                      # 16 bytes: the loop's one synchronisation
+                if int(c[1]) >= J:
+                    break
+                claiming = claiming and int(c[0]) < J
+        return rep
+    finally:
+        if hold_before is not None and hold_before != 1:
+            env.set_option("step_hold", hold_before)
         if own:
             env.close()
 
