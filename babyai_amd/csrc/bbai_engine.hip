@@ -19,6 +19,7 @@
 //                     k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
 //                     the buffer holds are stored.  (render_launch)
 //   bbai_gridk.hpp    k_render_grid<TS>: the full-grid picture; k_full_obs: the fully observable encoding.  (render_grid_launch, full_launch)
+//   bbai_viewn.hpp    k_view_obs<V>: the egocentric observation at view sizes 3 .. 11 (ViewSizeWrapper).  (viewn_launch)
 //   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32 (render_view_launch); k_view_delta<TS> / k_view_ids: a whole
 //                     batch into the target registered at that size, only the 64-byte pieces whose cells changed.  (view_delta_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
@@ -41,6 +42,7 @@ __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase
 #endif
 #include "../../include/bbai.h"
 #include "../../include/bbai_demo_replay.h"
+#include "../../include/bbai_view_size.h"
 #include "bbai_types.hpp"
 #include "bbai_target.hpp"
 #include "bbai_kernels.hpp"
@@ -318,6 +320,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_botk.hpp"
 #include "bbai_render.hpp"
 #include "bbai_gridk.hpp"
+#include "bbai_viewn.hpp"
 #include "bbai_viewpx.hpp"
 #include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
@@ -1488,6 +1491,64 @@ int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
     BBAI_TRY(call.rc);
     BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
     BBAI_TRY(full_launch(e, nullptr, e->n, full, s));
+    return call.leave();
+}
+
+}  // extern "C"
+
+// The view-size entries (include/bbai_view_size.h).  Launch shape of k_view_obs<V>: items of ViewN<V>::EPI envs, persistent blocks, VIEWN_BPC per CU.
+template <int V>
+static void viewn_launch_v(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    ViewNArgs a;
+    a.c = e->cfg; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
+    a.ids = ids; a.count = count; a.out = out;
+    a.items = (count + ViewN<V>::EPI - 1) / ViewN<V>::EPI;
+    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * VIEWN_BPC));
+    hipLaunchKernelGGL((k_view_obs<V>), dim3(blocks), dim3(VIEWN_BLOCK), 0, s, a);
+}
+static int viewn_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    switch (view_size) {
+        case 3: viewn_launch_v<3>(e, ids, count, out, s); break;
+        case 5: viewn_launch_v<5>(e, ids, count, out, s); break;
+        case 7: viewn_launch_v<7>(e, ids, count, out, s); break;
+        case 9: viewn_launch_v<9>(e, ids, count, out, s); break;
+        case 11: viewn_launch_v<11>(e, ids, count, out, s); break;
+        default: ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
+    }
+    HIP_TRY(hipGetLastError());
+    return BBAI_OK;
+}
+
+extern "C" {
+
+int bbai_observe_view(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    if (!e) ARG_FAIL("null handle");
+    if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
+    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
+    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "observe_view before reset"); return BBAI_ERR_STATE; }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    BBAI_TRY(viewn_launch(e, view_size, ids, count, out, s));
+    return call.leave();
+}
+
+int bbai_step_view(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
+                   uint8_t* dones, int auto_reset, int view_size, uint8_t* view, void* stream) {
+    if (!e || !actions || !image || !dirs || !rewards || !dones || !view) ARG_FAIL("null handle or buffer");
+    if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
+    if ((uintptr_t)view & 15) ARG_FAIL("view observation buffer not 16-byte aligned");
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
+    BBAI_TRY(viewn_launch(e, view_size, nullptr, e->n, view, s));
     return call.leave();
 }
 

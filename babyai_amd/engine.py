@@ -48,6 +48,20 @@ def check_tile_size(tile_size):
     return ts
 
 
+VIEW_SIZES = (3, 5, 7, 9, 11)
+
+
+def check_view_size(view_size, pixel=False, full_obs=False):
+    """ViewSizeWrapper's agent_view_size, checked before any device work: an odd int in VIEW_SIZES; another size than 7 goes with neither
+    pixel nor full_obs (the pixel view kernels draw 7x7 views; the full observation has no view)."""
+    if isinstance(view_size, (bool, np.bool_)) or not isinstance(view_size, (int, np.integer)) or int(view_size) not in VIEW_SIZES:
+        raise ValueError("view_size %r: an odd int in %s" % (view_size, VIEW_SIZES))
+    if int(view_size) != 7 and (pixel or full_obs):
+        raise ValueError("view_size %d with %s: partial-view pixels and the full observation exist at the 7x7 view only"
+                         % (view_size, "pixel=True" if pixel else "full_obs=True"))
+    return int(view_size)
+
+
 P, I64, I32, F64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
 _STEP = [P, P, P, P, P, P, P, I32]      # env, actions, image, direction, reward, reward64, done, auto_reset: how every stepping entry begins
 
@@ -116,11 +130,18 @@ ABI_REPLAY = {
 }
 REPLAY_SYMBOLS = tuple(ABI_REPLAY)
 
+# include/bbai_view_size.h, the companion header of the view-size entries, the same way (tests/test_view_size_host.py holds the rows to it)
+ABI_VIEW = {
+    "bbai_observe_view": (I32, [P, I32, P, I64, P, P]),
+    "bbai_step_view": (I32, _STEP + [I32, P, P]),
+}
+VIEW_SYMBOLS = tuple(ABI_VIEW)
+
 
 def bind(lib):
-    """Give every entry of ABI and ABI_REPLAY that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
+    """Give every entry of ABI, ABI_REPLAY and ABI_VIEW that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
     experiment builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()) + list(ABI_VIEW.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -309,16 +330,24 @@ class BatchedBabyAIEnv(object):
                  load_state() and reseed() store only the 64-byte pieces of a frame that changed (include/bbai.h bbai_render_view,
                  option "render_target_tile_size"; set_option("render_delta", 0) draws every frame whole again; after writing into
                  `pixels` yourself call render_invalidate())
+    view_size : ViewSizeWrapper(env, view_size): the egocentric view at 3, 5, 9 or 11 cells instead of 7 -- obs image = uint8[N, V, V, 3]
+                 (`view`; include/bbai_view_size.h bbai_observe_view / bbai_step_view), the agent at view cell (V // 2, V - 1).  `image` stays the 7x7
+                 encoding and direction, rewards and dones are what they are without it.  Only with pixel=False and full_obs=False, and
+                 anything but an odd int in 3..11 is a ValueError; the device expert (bot_actions, bot_rollout) sees 7x7 whatever is
+                 observed, so those calls raise on such a batch
     validate_actions : check every step()'s actions on the device first and raise AssertionError("unknown action") like
                  the reference (gym_minigrid MiniGridEnv.step) instead of treating bytes 8..255 as `done` (include/bbai.h);
                  costs one reduction and a host synchronisation per step, so it is off by default
     """
 
+    view_size, view = 7, None          # (class defaults: a batch is the 7x7 one until __init__ says otherwise)
+
     def __init__(self, env_id, num_envs, device="cuda:0", seeds=None, pixel=False, auto_reset=True, validate_actions=False,
-                 done_actions=None, full_obs=False, tile_size=8):
+                 done_actions=None, full_obs=False, tile_size=8, view_size=7):
         import torch
         self.torch = torch
         self.full_obs = bool(full_obs)
+        self.view_size = check_view_size(view_size, pixel, full_obs)
         self.tile_size = check_tile_size(tile_size) if pixel else int(tile_size)
         if not torch.cuda.is_available():
             raise EngineError("no ROCm GPU visible: the batched engine has no CPU path")
@@ -356,6 +385,9 @@ class BatchedBabyAIEnv(object):
             self.done = torch.zeros((n,), dtype=torch.uint8, device=self.device)
             self.pixels = None
             self.full = None        # full_obs: the observation image (observe_full)
+            self.view = None        # view_size != 7: the observation image (observe_view)
+            if self.view_size != 7:
+                self.view = torch.zeros((n, self.view_size, self.view_size, 3), dtype=torch.uint8, device=self.device)
             if self.full_obs:
                 c, ts = self.cfg, self.tile_size
                 shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
@@ -418,6 +450,12 @@ class BatchedBabyAIEnv(object):
                 self.observe_full()
                 self._ev_end("full_obs", ev)
             img = self.full
+        elif self.view is not None:
+            if not rendered:
+                ev = self._ev_begin()
+                self.observe_view()
+                self._ev_end("view_obs", ev)
+            img = self.view
         elif self.pixel and rendered:
             img = self.pixels
         elif self.pixel:
@@ -591,6 +629,26 @@ class BatchedBabyAIEnv(object):
                "bbai_observe_full")
         return out
 
+    def observe_view(self, ids=None, view_size=None, out=None):
+        """ViewSizeWrapper(env, view_size)'s observation image of envs `ids` (None = every env; else an int sequence or an int64 device
+        tensor, any order, repeats allowed) from the current state -> uint8[k, V, V, 3] on the device, asynchronous on the current stream
+        (include/bbai_view_size.h bbai_observe_view; view_size None = the batch's; any of VIEW_SIZES on any batch).  ids = out = None at the batch's
+        own size in a view_size batch refreshes `view`, the observation step() returns (after load_checkpoint or import_state, which do
+        not carry it).  An id outside [0, num_envs) gives an all-zero frame."""
+        v = self.view_size if view_size is None else check_view_size(view_size)
+        if self.view is not None and ids is None and out is None and v == self.view_size:
+            out = self.view
+        k, ids_ptr, self._hold["observe_view"] = self._ids(ids)
+        out = self._frames_out(out, (k, v, v, 3))
+        _check(self.lib, self.lib.bbai_observe_view(self.handle, v, ids_ptr, k, out.data_ptr() if k else None, self._stream()),
+               "bbai_observe_view")
+        return out
+
+    def _expert_sees_7x7(self, what):
+        """The device expert keeps a 7x7 visibility mask; the reference's bot would use the env's agent_view_size (babyai/bot.py:663-674)."""
+        if self.view_size != 7:
+            raise EngineError("%s on a view_size=%d batch: the device expert sees 7x7 and would diverge from the reference's bot" % (what, self.view_size))
+
     def render_invalidate(self):
         """Call after writing into self.pixels yourself: the next render rewrites every byte (include/bbai.h bbai_render_invalidate)."""
         _check(self.lib, self.lib.bbai_render_invalidate(self.handle), "bbai_render_invalidate")
@@ -653,6 +711,11 @@ class BatchedBabyAIEnv(object):
             # FullyObsWrapper's step: transition + the full observation of every env as ONE call (include/bbai.h bbai_step_full)
             _check(self.lib, self.lib.bbai_step_full(self.handle, actions.data_ptr(), *self._step_out(), self.full.data_ptr(), self._stream()),
                    "bbai_step_full")
+            return self._obs(rendered=True), self.reward, self.done, {}
+        if self.view is not None and self.kernel_events is None:
+            # ViewSizeWrapper's step: transition + the V x V view of every env as ONE call (include/bbai_view_size.h bbai_step_view)
+            _check(self.lib, self.lib.bbai_step_view(self.handle, actions.data_ptr(), *self._step_out(), self.view_size, self.view.data_ptr(),
+                                                     self._stream()), "bbai_step_view")
             return self._obs(rendered=True), self.reward, self.done, {}
         if self.pixel and not self.full_obs and self.tile_size == 8 and self.kernel_events is None and hasattr(self.lib, "bbai_step_render"):
             # the wrapped env's step: transition + render as ONE call (include/bbai.h bbai_step_render)
@@ -762,7 +825,9 @@ class BatchedBabyAIEnv(object):
             self._render_batch_into(self.image, self.tile_size, self.pixels)
         if self.full_obs:
             self.observe_full()          # the last step's full observation (the tap log keeps its 7x7 rows)
-        return self._obs_dict(self.full if self.full_obs else self.pixels if self.pixel else self.image)
+        if self.view is not None:
+            self.observe_view()          # the last step's view (the tap log keeps its 7x7 rows)
+        return self._obs_dict(self.full if self.full_obs else self.view if self.view is not None else self.pixels if self.pixel else self.image)
 
     # ---- state access -------------------------------------------------------------------
     def programs(self, first=0, count=None):
@@ -944,6 +1009,7 @@ class BatchedBabyAIEnv(object):
         uint8[N] suggested actions, BOT_GAVE_UP (255) where the reference bot would have raised.  `prev_actions` = the
         actions the envs were really stepped with since the last call (advising mode), None = the suggestions."""
         torch = self.torch
+        self._expert_sees_7x7("bot_actions")
         if out is None:
             if self._bot_out is None:
                 self._bot_out = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
@@ -970,6 +1036,7 @@ class BatchedBabyAIEnv(object):
         reused allocates nothing."""
         torch = self.torch
         T, n = int(steps), self.num_envs
+        self._expert_sees_7x7("bot_rollout")
         if not self.auto_reset:
             raise EngineError("bot_rollout steps with ParallelEnv semantics: construct the env with auto_reset=True")
         shapes = {"image": (T, n, 7, 7, 3), "direction": (T, n), "action": (T, n), "reward": (T, n), "done": (T, n), "gave_up": (T, n)}

@@ -61,9 +61,10 @@ def uninstall():
         ref_eval.batch_evaluate = _saved.pop("batch_evaluate")
 
 
-def make_envs(env_name, procs, seed, pixel=False, device="cuda:0", full_obs=False, tile_size=8):
+def make_envs(env_name, procs, seed, pixel=False, device="cuda:0", full_obs=False, tile_size=8, view_size=7):
     """The env list of scripts/train_rl.py:53-60 as ONE engine batch: env i seeded with 100 * seed + i.  full_obs=True: every env
     wrapped in FullyObsWrapper (pixel=False) or RGBImgObsWrapper(env, tile_size) (pixel=True); pixel=True without it:
-    RGBImgPartialObsWrapper(env, tile_size), tile sizes 8 / 16 / 32."""
+    RGBImgPartialObsWrapper(env, tile_size), tile sizes 8 / 16 / 32.  view_size (3, 5, 9, 11; encoded observations only): every env
+    wrapped in ViewSizeWrapper(env, view_size)."""
     return BatchedParallelEnv(env_name, procs, device=device, pixel=pixel, seeds=[100 * seed + i for i in range(procs)], full_obs=full_obs,
-                              tile_size=tile_size)
+                              tile_size=tile_size, view_size=view_size)

@@ -93,7 +93,8 @@ class TensorObssPreprocessor(object):
         torch = self.env.torch
         if obs is None:
             env = self.env
-            obs = {"image": env.full if getattr(env, "full_obs", False) else env.pixels if env.pixel else env.image}
+            obs = {"image": env.full if getattr(env, "full_obs", False) else env.view if getattr(env, "view", None) is not None
+                   else env.pixels if env.pixel else env.image}
         image = obs["image"].to(torch.float32)                  # RawImagePreprocessor: float image, no scaling
         tok = self.tokens
         width = max(int((tok != 0).sum(dim=1).max().item()), 1) if trim else self.width

@@ -17,7 +17,7 @@ the no-edit route (`babyai_amd.integrate.install()`).
 """
 import numpy as np
 
-from .engine import BatchedBabyAIEnv, check_tile_size
+from .engine import BatchedBabyAIEnv, check_tile_size, check_view_size
 from .levels import LEVELS, level_name, make_cfg
 
 
@@ -48,21 +48,23 @@ class _Discrete(object):
         self.n = n
 
 
-def _spaces(pixel, full_obs=False, env_id=None, tile_size=8):
+def _spaces(pixel, full_obs=False, env_id=None, tile_size=8, view_size=7):
     """observation_space['image'] has the shape of the returned image: RGBImgPartialObsWrapper's (7 * tile_size, 7 * tile_size, 3) --
     (56, 56, 3) at the default 8 -- or the 7x7 view; with full_obs FullyObsWrapper's (W, H, 3) or RGBImgObsWrapper's
-    (H * tile_size, W * tile_size, 3) -- not square on 19 levels."""
+    (H * tile_size, W * tile_size, 3) -- not square on 19 levels; with view_size V (encoded only) ViewSizeWrapper's (V, V, 3)."""
     if full_obs:
         c = make_cfg(env_id)
         shape = (c.H * tile_size, c.W * tile_size, 3) if pixel else (c.W, c.H, 3)
     else:
-        shape = (7 * tile_size, 7 * tile_size, 3) if pixel else (7, 7, 3)
+        shape = (7 * tile_size, 7 * tile_size, 3) if pixel else (view_size, view_size, 3)
     return _DictSpace({"image": _Box(shape)}), _Discrete(7)
 
 
-def _full_args(full_obs, pixel, tile_size):
-    """(full_obs, tile_size) checked before any device work: a tile size without an atlas raises ValueError here."""
+def _full_args(full_obs, pixel, tile_size, view_size=7):
+    """(full_obs, tile_size) checked before any device work: a tile size without an atlas, or a view size the engine does not have or
+    that does not go with the other two (engine.check_view_size), raises ValueError here."""
     full_obs = bool(full_obs)
+    check_view_size(view_size, pixel, full_obs)
     return full_obs, check_tile_size(tile_size) if pixel else int(tile_size)
 
 
@@ -98,20 +100,23 @@ class _EnvView(object):
 
 
 class _VecBase(object):
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, engine=None, full_obs=False, tile_size=8):
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, engine=None, full_obs=False, tile_size=8, view_size=7):
         """`engine`: an object with BatchedBabyAIEnv's tensor protocol to run on instead of building one (tests put the
         CPU oracle there to drive the reference's consumers through this adapter code without a GPU).  `full_obs` / `tile_size`:
         FullyObsWrapper (pixel=False) or RGBImgObsWrapper(env, tile_size) (pixel=True) instead of the 7x7 view (BatchedBabyAIEnv);
         pixel=True without full_obs: RGBImgPartialObsWrapper(env, tile_size), images (7 * tile_size, 7 * tile_size, 3) -- 37.6 KB /
-        150.5 KB per env per frame at 16 / 32, copied to the host every step by these list-of-dicts adapters."""
-        full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
+        150.5 KB per env per frame at 16 / 32, copied to the host every step by these list-of-dicts adapters.  `view_size`:
+        ViewSizeWrapper(env, view_size), images (V, V, 3) for V in 3, 5, 9, 11 (encoded observations only)."""
+        full_obs, tile_size = _full_args(full_obs, pixel, tile_size, view_size)
         if engine is None:
-            engine = BatchedBabyAIEnv(env_id, num_envs, device=device, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size)
+            engine = BatchedBabyAIEnv(env_id, num_envs, device=device, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size,
+                                      view_size=view_size)
         self.engine = engine
         self.num_envs = num_envs
         self.pixel = pixel
         self.full_obs = full_obs
-        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size)
+        self.view_size = int(view_size)
+        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size, view_size)
         if seeds is not None:
             self.seed(seeds)
 
@@ -178,18 +183,18 @@ class BatchedParallelEnv(_VecBase):
     """`ParallelEnv` protocol (penv.py:18-59): auto-reset -- when an env finishes, the returned obs is the
     first obs of its next episode while reward/done belong to the terminal step (penv.py:8-11,49-50)."""
 
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8):
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8, view_size=7):
         super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=True, seeds=seeds, engine=engine, full_obs=full_obs,
-                         tile_size=tile_size)
+                         tile_size=tile_size, view_size=view_size)
 
 
 class BatchedManyEnvs(_VecBase):
     """`ManyEnvs` protocol (evaluate.py:58-81): no auto-reset; a finished env re-emits its last
     (obs, reward, done, info) until the next reset()."""
 
-    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8):
+    def __init__(self, env_id, num_envs, device="cuda:0", pixel=False, seeds=None, engine=None, full_obs=False, tile_size=8, view_size=7):
         super().__init__(env_id, num_envs, device=device, pixel=pixel, auto_reset=False, seeds=seeds, engine=engine, full_obs=full_obs,
-                         tile_size=tile_size)
+                         tile_size=tile_size, view_size=view_size)
         self.done = [False] * num_envs
 
     def reset(self):
@@ -237,12 +242,14 @@ class SingleEnv(object):
 
     actions = Actions
 
-    def __init__(self, env_id, device="cuda:0", pixel=False, seed=None, full_obs=False, tile_size=8):
-        full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
-        self.engine = BatchedBabyAIEnv(env_id, 1, device=device, pixel=pixel, auto_reset=False, full_obs=full_obs, tile_size=tile_size)
+    def __init__(self, env_id, device="cuda:0", pixel=False, seed=None, full_obs=False, tile_size=8, view_size=7):
+        full_obs, tile_size = _full_args(full_obs, pixel, tile_size, view_size)
+        self.engine = BatchedBabyAIEnv(env_id, 1, device=device, pixel=pixel, auto_reset=False, full_obs=full_obs, tile_size=tile_size,
+                                       view_size=view_size)
         self.pixel = pixel
         self.full_obs = full_obs
-        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size)
+        self.view_size = int(view_size)
+        self.observation_space, self.action_space = _spaces(pixel, full_obs, env_id, tile_size, view_size)
         self.step_count = 0
         self.mission = self.surface = ""
         if seed is not None:
@@ -312,12 +319,13 @@ class SingleEnv(object):
         self.engine.close()
 
 
-def make(env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, full_obs=False, tile_size=8):
+def make(env_id, num_envs, device="cuda:0", pixel=False, auto_reset=True, seeds=None, full_obs=False, tile_size=8, view_size=7):
     """Batched twin of `gym.make(env_id)` (ids registered at babyai/levels/levelgen.py:467-493), optionally wrapped in
     FullyObsWrapper (full_obs=True), RGBImgObsWrapper(env, tile_size) (full_obs=True, pixel=True) or
-    RGBImgPartialObsWrapper(env, tile_size) (pixel=True; tile sizes 8, 16, 32: 9.4 / 37.6 / 150.5 KB per env per frame).
+    RGBImgPartialObsWrapper(env, tile_size) (pixel=True; tile sizes 8, 16, 32: 9.4 / 37.6 / 150.5 KB per env per frame), or in ViewSizeWrapper(env, view_size) (view_size 3, 5, 9, 11; encoded observations only).
     Returns the tensor-level `BatchedBabyAIEnv`."""
     if level_name(env_id) not in LEVELS:
         raise KeyError("unknown / unsupported level id %r" % (env_id,))
-    full_obs, tile_size = _full_args(full_obs, pixel, tile_size)
-    return BatchedBabyAIEnv(env_id, num_envs, device=device, seeds=seeds, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size)
+    full_obs, tile_size = _full_args(full_obs, pixel, tile_size, view_size)
+    return BatchedBabyAIEnv(env_id, num_envs, device=device, seeds=seeds, pixel=pixel, auto_reset=auto_reset, full_obs=full_obs, tile_size=tile_size,
+                            view_size=view_size)
