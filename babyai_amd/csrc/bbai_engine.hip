@@ -934,6 +934,10 @@ struct StepIO { const uint8_t* actions; uint8_t* image; uint8_t* dirs; float* re
 };
 // The hold byte of a call that is being enqueued (option "step_hold": read here, on the host).
 static int step_hold(const bbai_env* e) { return e->step_hold ? BBAI_ACTION_HOLD : -1; }
+// What a stepping entry point hands over: its buffers, with the handle's done-action setting and hold byte.
+static StepIO step_io(const bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64, uint8_t* dones, int auto_reset) {
+    return StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)};
+}
 struct StepPlan { FuseArgs fa; bool fused; uint32_t* counter; TapArgs tap = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
                   bool dirty = false;      // k_step finds the dirty cells of the registered target for its render (step_render_launch, step_dirty)
 };
@@ -1023,7 +1027,7 @@ int bbai_step(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
+    BBAI_TRY(step_launch(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), s));
     return call.leave();
 }
 
@@ -1068,7 +1072,7 @@ int bbai_step_tapped(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_
     CallScope call(e, s);
     BBAI_TRY(call.rc);
     const TapRows rows = {image_out, dir_out, reward64_out, done_out};
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s, &rows));
+    BBAI_TRY(step_launch(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), s, &rows));
     return call.leave();
 }
 
@@ -1136,6 +1140,12 @@ static RenderPlan plan_render(const bbai_env* e, uint8_t* shadow) {
     return p;
 }
 
+// The grid of a kernel whose persistent blocks share `items` work items (groups, tickets): per_cu blocks on every CU, never more blocks than items.
+static int64_t cu_count(const bbai_env* e) { return e->n_cus > 0 ? e->n_cus : 256; }
+static unsigned persistent_blocks(const bbai_env* e, int64_t items, int per_cu) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, cu_count(e) * per_cu));
+}
+
 // One render's range: envs [env_off, env_off + nr) of the batch, `input` and `pixels` at its first env
 struct RenderRange { const uint8_t* input; uint8_t* pixels; int64_t nr, env_off; hipStream_t stream; };
 
@@ -1165,18 +1175,14 @@ static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned bl
 // split, three blocks per CU, 0.634-0.643; this kernel at three blocks per CU 0.618-0.625, at two 0.621-0.630, at one 0.595-0.610 -- the
 // fewer blocks share the one in-order stream of groups, the more compact the window the chip's stores advance through.
 static void launch_dstore_lw(const bbai_env* e, const RenderRange& r, int64_t groups, uint8_t* sh) {
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : 1);
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (groups + DSTORE_LW_K - 1) / DSTORE_LW_K));
+    const unsigned blocks = persistent_blocks(e, (groups + DSTORE_LW_K - 1) / DSTORE_LW_K, e->render_delta_bpc > 0 ? e->render_delta_bpc : 1);
     hipLaunchKernelGGL((k_render_dstore_lw<64>), dim3(blocks), dim3(DSTORE_LW_T), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles, e->render_tickets);
 }
 static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool from_step) {
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
     const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
     constexpr int G = 32;
     const int64_t groups = (r.nr + G - 1) / G;
-    const int64_t want = (int64_t)cus * (e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, groups));
+    const unsigned blocks = persistent_blocks(e, groups, e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
     uint8_t* sh = e->rt.shadow + r.env_off * CELLS;
     if (from_step && e->render_piece_bytes != 128 && e->render_delta_sched != 2) launch_dstore_lw(e, r, groups, sh);
     else if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
@@ -1201,10 +1207,10 @@ static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool fr
 // encoding is still in the memory-side cache and short-lived (512, 2) blocks win.
 template <int G, int T, int NC, int K>
 static void launch_queue_shape(const bbai_env* e, const RenderRange& r, const RenderPlan& p) {
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
+    static_assert(1024 % T == 0, "1024 / T blocks per CU");
     const int64_t tickets = ((r.nr + G - 1) / G + K - 1) / K;
-    const int64_t want = e->render_queue_blocks > 0 ? e->render_queue_blocks : (e->render_queue_bpc > 0 ? (int64_t)cus * e->render_queue_bpc : (int64_t)cus * 1024 / T);
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, tickets));
+    const unsigned blocks = e->render_queue_blocks > 0 ? (unsigned)std::max<int64_t>(1, std::min<int64_t>(e->render_queue_blocks, tickets))      // (a count for the whole chip)
+                                                        : persistent_blocks(e, tickets, e->render_queue_bpc > 0 ? e->render_queue_bpc : 1024 / T);
     hipLaunchKernelGGL((k_render_q<G, T, NC, K>), dim3(blocks), dim3(T), 0, r.stream, r.nr, r.input, r.pixels, e->atlas, e->lut, e->n_tiles, e->render_tickets, p.pace, p.shadow);
 }
 static void launch_render_queue(const bbai_env* e, const RenderRange& r, const RenderPlan& p) {
@@ -1302,6 +1308,26 @@ int bbai_set_grid_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
 
 }  // extern "C"
 
+// ---- observations of listed envs from the live state: render_grid, observe_full, observe_view (bbai_kernels.hpp: EnvList) ----
+static EnvList env_list(const bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out) {
+    return EnvList{e->cfg, e->n, e->rec, e->inplace ? e->next_rec : nullptr, e->depth, e->hot, ids, count, out};
+}
+// The frames' buffer of a call that draws `count` frames: there, and 16-byte aligned (the kernels store 16-byte chunks).
+static int frames_ready(const char* func, int64_t count, const uint8_t* out) {
+    if (count > 0 && (!out || ((uintptr_t)out & 15))) { snprintf(g_err, sizeof(g_err), "%s: output buffer missing or not 16-byte aligned", func); return BBAI_ERR_ARG; }
+    return BBAI_OK;
+}
+// What those three entry points (`func`: "bbai_<who>") ask first, in the order their callers have always seen: the count, the frames'
+// buffer, then the state -- render_grid's atlas (no_atlas_ts: the tile size that has none, else 0) in front of "<who> before reset".
+static int listed_ready(const bbai_env* e, const char* func, const int64_t* ids, int64_t count, const uint8_t* out, int no_atlas_ts = 0) {
+    const char* who = func + 5;
+    if (count < 0 || (!ids && count > e->n)) { snprintf(g_err, sizeof(g_err), "%s: env count out of range", func); return BBAI_ERR_ARG; }
+    BBAI_TRY(frames_ready(func, count, out));
+    if (no_atlas_ts) { snprintf(g_err, sizeof(g_err), "%s: no atlas for tile size %d (bbai_set_grid_atlas)", who, no_atlas_ts); return BBAI_ERR_STATE; }
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "%s before reset", who); return BBAI_ERR_STATE; }
+    return BBAI_OK;
+}
+
 // Launch shape by frame size F: small frames (F <= 64 KB: GoToLocal at tile size 8 is 12 KB) -- several envs per work item, about 128 KB
 // of frames each; large ones (BossLevel at 32: 1.49 MB) -- an env in slices of about 256 KB.  Persistent blocks: 2 per CU at tile sizes 8
 // and 32 (35 KB / 10 KB of LDS), 1 at 16 (the 102 KB atlas); option "grid_render_bpc" overrides.
@@ -1311,8 +1337,8 @@ static void render_grid_launch(bbai_env* e, int highlight, const int64_t* ids, i
     const LevelCfg& c = e->cfg;
     const int64_t F = (int64_t)c.H * TS * c.W * TS * 3;
     GridArgs a;
-    a.c = c; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
-    a.ids = ids; a.count = count; a.out = out; a.atlas = e->grid_atlas[k]; a.lut = e->grid_lut[k]; a.n_tiles = e->grid_tiles[k];
+    a.list = env_list(e, ids, count, out);
+    a.atlas = e->grid_atlas[k]; a.lut = e->grid_lut[k]; a.n_tiles = e->grid_tiles[k];
     a.highlight = highlight ? 1 : 0;
     a.envs_per_item = 1; a.slices = 1;
     if (F <= 65536) a.envs_per_item = (int)std::max<int64_t>(1, std::min<int64_t>({131072 / F, GRID_MAX_ENVS, GRID_ID_BYTES / (c.W * c.H)}));
@@ -1322,9 +1348,7 @@ static void render_grid_launch(bbai_env* e, int highlight, const int64_t* ids, i
     a.frame_magic = (1ull << 32) / a.frame16 + 1;
     a.ppr = (uint32_t)(c.W * TS * 3 / GridTile<TS>::P);
     a.ppr_magic = (1ull << 32) / a.ppr + 1;
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    const int bpc = e->grid_bpc > 0 ? e->grid_bpc : (TS == 16 ? 1 : 2);
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * bpc));
+    const unsigned blocks = persistent_blocks(e, a.items, e->grid_bpc > 0 ? e->grid_bpc : (TS == 16 ? 1 : 2));
     hipLaunchKernelGGL((k_render_grid<TS>), dim3(blocks), dim3(GRID_BLOCK), 0, s, a);
 }
 
@@ -1334,10 +1358,7 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     const int k = grid_ts_index(tile_size);
     if (!e) ARG_FAIL("null handle");
     if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
-    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
-    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
-    if (!e->grid_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_grid: no atlas for tile size %d (bbai_set_grid_atlas)", tile_size); return BBAI_ERR_STATE; }
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "render_grid before reset"); return BBAI_ERR_STATE; }
+    BBAI_TRY(listed_ready(e, __func__, ids, count, out, e->grid_tiles[k] ? 0 : tile_size));
     if (count == 0) return BBAI_OK;
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1372,15 +1393,14 @@ int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
 template <int TS>
 static void render_view_launch(bbai_env* e, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
     const int k = view_ts_index(TS);
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    const int64_t want = (int64_t)cus * 2;
+    const int64_t want = cu_count(e) * 2;
     ViewPxArgs a;
     a.image = image; a.rows = rows; a.ids = ids; a.count = count; a.out = out;
     a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
     a.envs_per_item = TS == 16 ? VIEWPX_MAX_ENVS : 1;
     a.slices = TS == 32 && count < want ? 2 : 1;
     a.items = a.slices > 1 ? count * a.slices : (count + a.envs_per_item - 1) / a.envs_per_item;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, want));
+    const unsigned blocks = persistent_blocks(e, a.items, 2);
     hipLaunchKernelGGL((k_view_pixels<TS>), dim3(blocks), dim3(VIEWPX_BLOCK), 0, s, a);
 }
 
@@ -1390,19 +1410,16 @@ static void render_view_launch(bbai_env* e, const uint8_t* image, int64_t rows, 
 template <int TS>
 static void view_delta_launch(bbai_env* e, bool fill, const uint8_t* image, uint8_t* out, hipStream_t s) {
     const int k = view_ts_index(TS);
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
     if (fill) {
         render_view_launch<TS>(e, image, e->n, nullptr, e->n, out, s);
-        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((e->n * CELLS + 255) / 256, (int64_t)cus * 8));
-        hipLaunchKernelGGL(k_view_ids, dim3(blocks), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt.shadow);
+        hipLaunchKernelGGL(k_view_ids, dim3(persistent_blocks(e, (e->n * CELLS + 255) / 256, 8)), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt.shadow);
         return;
     }
     ViewDeltaArgs a;
     a.image = image; a.n = e->n; a.out = out; a.shadow = e->rt.shadow;
     a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
     const int64_t groups = (e->n + ViewDelta<TS>::G - 1) / ViewDelta<TS>::G;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)cus * 2));
-    hipLaunchKernelGGL((k_view_delta<TS>), dim3(blocks), dim3(VIEWDELTA_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_view_delta<TS>), dim3(persistent_blocks(e, groups, 2)), dim3(VIEWDELTA_BLOCK), 0, s, a);
 }
 
 extern "C" {
@@ -1413,7 +1430,7 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
     if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_render)");
     if (rows < 0 || count < 0 || (!ids && count > rows)) ARG_FAIL("row count out of range");
     if (count > 0 && rows > 0 && !image) ARG_FAIL("encoded buffer missing");
-    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
+    BBAI_TRY(frames_ready(__func__, count, out));
     if (!e->view_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_view: no atlas for tile size %d (bbai_set_view_atlas)", tile_size); return BBAI_ERR_STATE; }
     if (count == 0) return BBAI_OK;
     ON_DEVICE(e->device);
@@ -1450,62 +1467,24 @@ static int full_launch(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* 
     const int epi = std::min({FULL_MAX_ENVS, FULL_LDS / F, FULL_APP / (c.H * c.ES)}) / align * align;
     if (epi < 1) { snprintf(g_err, sizeof(g_err), "observe_full: grid %d x %d too large", c.W, c.H); return BBAI_ERR_ARG; }
     FullArgs a;
-    a.c = c; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
-    a.ids = ids; a.count = count; a.out = out;
+    a.list = env_list(e, ids, count, out);
     a.envs_per_item = epi;
     a.items = (count + epi - 1) / epi;
     a.hw_magic = (1ull << 32) / (uint32_t)(c.W * c.H) + 1;
     a.w_magic = (1ull << 32) / (uint32_t)c.W + 1;
     a.rd_magic = (1ull << 32) / (uint32_t)(c.H * c.ES / 4) + 1;
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * FULL_BPC));
-    hipLaunchKernelGGL(k_full_obs, dim3(blocks), dim3(FULL_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_full_obs, dim3(persistent_blocks(e, a.items, FULL_BPC)), dim3(FULL_BLOCK), 0, s, a);
     HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }
-
-extern "C" {
-
-int bbai_observe_full(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
-    if (!e) ARG_FAIL("null handle");
-    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
-    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "observe_full before reset"); return BBAI_ERR_STATE; }
-    if (count == 0) return BBAI_OK;
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    BBAI_TRY(full_launch(e, ids, count, out, s));
-    return call.leave();
-}
-
-int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
-                   uint8_t* dones, int auto_reset, uint8_t* full, void* stream) {
-    if (!e || !actions || !image || !dirs || !rewards || !dones || !full) ARG_FAIL("null handle or buffer");
-    if ((uintptr_t)full & 15) ARG_FAIL("full observation buffer not 16-byte aligned");
-    BBAI_TRY(step_ready(e, auto_reset, "step"));
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
-    BBAI_TRY(full_launch(e, nullptr, e->n, full, s));
-    return call.leave();
-}
-
-}  // extern "C"
 
 // The view-size entries (include/bbai_view_size.h).  Launch shape of k_view_obs<V>: items of ViewN<V>::EPI envs, persistent blocks, VIEWN_BPC per CU.
 template <int V>
 static void viewn_launch_v(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
     ViewNArgs a;
-    a.c = e->cfg; a.n = e->n; a.recs = e->rec; a.ring = e->inplace ? e->next_rec : nullptr; a.depth = e->depth; a.hots = e->hot;
-    a.ids = ids; a.count = count; a.out = out;
+    a.list = env_list(e, ids, count, out);
     a.items = (count + ViewN<V>::EPI - 1) / ViewN<V>::EPI;
-    const int cus = e->n_cus > 0 ? e->n_cus : 256;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.items, (int64_t)cus * VIEWN_BPC));
-    hipLaunchKernelGGL((k_view_obs<V>), dim3(blocks), dim3(VIEWN_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_view_obs<V>), dim3(persistent_blocks(e, a.items, VIEWN_BPC)), dim3(VIEWN_BLOCK), 0, s, a);
 }
 static int viewn_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
     switch (view_size) {
@@ -1520,21 +1499,51 @@ static int viewn_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t 
     return BBAI_OK;
 }
 
-extern "C" {
-
-int bbai_observe_view(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
-    if (!e) ARG_FAIL("null handle");
-    if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
-    if (count < 0 || (!ids && count > e->n)) ARG_FAIL("env count out of range");
-    if (count > 0 && (!out || ((uintptr_t)out & 15))) ARG_FAIL("output buffer missing or not 16-byte aligned");
-    if (!e->live) { snprintf(g_err, sizeof(g_err), "observe_view before reset"); return BBAI_ERR_STATE; }
+// One observation launch of either kind (view_size 0: the fully observable encoding), and the two calls built on it: the listed envs'
+// frames (the entry point has asked listed_ready), and a step of the whole batch with every env's frame behind it, as one call.
+static int observe_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    return view_size ? viewn_launch(e, view_size, ids, count, out, s) : full_launch(e, ids, count, out, s);
+}
+static int observe_listed(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
     if (count == 0) return BBAI_OK;
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    BBAI_TRY(viewn_launch(e, view_size, ids, count, out, s));
+    BBAI_TRY(observe_launch(e, view_size, ids, count, out, s));
     return call.leave();
+}
+static int step_observe(bbai_env* e, const StepIO& io, int view_size, uint8_t* frames, void* stream) {
+    BBAI_TRY(step_ready(e, io.auto_reset, "step"));
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    BBAI_TRY(step_launch(e, io, s));
+    BBAI_TRY(observe_launch(e, view_size, nullptr, e->n, frames, s));
+    return call.leave();
+}
+
+extern "C" {
+
+int bbai_observe_full(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    if (!e) ARG_FAIL("null handle");
+    BBAI_TRY(listed_ready(e, __func__, ids, count, out));
+    return observe_listed(e, 0, ids, count, out, stream);
+}
+
+int bbai_step_full(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
+                   uint8_t* dones, int auto_reset, uint8_t* full, void* stream) {
+    if (!e || !actions || !image || !dirs || !rewards || !dones || !full) ARG_FAIL("null handle or buffer");
+    if ((uintptr_t)full & 15) ARG_FAIL("full observation buffer not 16-byte aligned");
+    return step_observe(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), 0, full, stream);
+}
+
+int bbai_observe_view(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
+    if (!e) ARG_FAIL("null handle");
+    if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
+    BBAI_TRY(listed_ready(e, __func__, ids, count, out));
+    return observe_listed(e, view_size, ids, count, out, stream);
 }
 
 int bbai_step_view(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
@@ -1542,14 +1551,7 @@ int bbai_step_view(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
     if (!e || !actions || !image || !dirs || !rewards || !dones || !view) ARG_FAIL("null handle or buffer");
     if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
     if ((uintptr_t)view & 15) ARG_FAIL("view observation buffer not 16-byte aligned");
-    BBAI_TRY(step_ready(e, auto_reset, "step"));
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, s));
-    BBAI_TRY(viewn_launch(e, view_size, nullptr, e->n, view, s));
-    return call.leave();
+    return step_observe(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), view_size, view, stream);
 }
 
 }  // extern "C"
@@ -1631,7 +1633,7 @@ int bbai_step_render(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_
     BBAI_TRY(step_ready(e, auto_reset, "step"));
     if (e->n_tiles <= 0) { snprintf(g_err, sizeof(g_err), "render before set_atlas"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
-    return step_render_launch(e, StepIO{actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)}, pixels, (hipStream_t)stream);
+    return step_render_launch(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), pixels, (hipStream_t)stream);
 }
 
 // Register (or clear with NULL) a caller-owned uint8[n][72] device buffer that the engine keeps filled with the
@@ -2034,7 +2036,7 @@ int bbai_rollout(bbai_env* e, int T, const uint8_t* actions, uint8_t* image, uin
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)e->n;
     const bool own_tap = tap && !tap->ids_dev;          // the envs of bbai_step_tap_set, logged by the stepping lanes
-    StepIO io = {actions, image, dirs, rewards, rewards64, dones, auto_reset, e->done_action_enum, step_hold(e)};
+    StepIO io = step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset);
     auto tap_rows = [&](int t) {                        // the tap log's rows of tick t
         const size_t c = (size_t)tap->count, orow = (size_t)(tap->obs_row0 + t), row = (size_t)(tap->row0 + t);
         return TapRows{tap->image_out + orow * c * OBS_BYTES, tap->dir_out + orow * c, tap->reward64_out + row * c, tap->done_out + row * c};

@@ -1,6 +1,8 @@
 // bbai_gridk.hpp -- whole-grid outputs of listed envs: the full-grid picture (k_render_grid<TS>, MiniGridEnv.render('rgb_array')) and the
 // fully observable encoding (k_full_obs, FullyObsWrapper.observation), with the work-item shapes and argument structs their launches fill.  The
-// per-cell parts are bbai_grid.hpp's (which the host tests compile as well).
+// per-cell parts are bbai_grid.hpp's (which the host tests compile as well).  Both argument structs open with bbai_kernels.hpp's EnvList,
+// and k_full_obs's item loop is built from the pieces that stand next to it there (list_item_load / _park / _store; k_view_obs<V> in
+// bbai_viewn.hpp is built from the same ones).
 // Part of bbai_engine.hip's translation unit: included where the code stood, at global scope.  The launches are bbai_engine.hip's
 // (render_grid_launch, full_launch).
 #pragma once
@@ -36,15 +38,7 @@ template <int TS> struct GridTile {
 };
 
 struct GridArgs {
-    LevelCfg c;
-    int64_t n;
-    const uint8_t* recs;
-    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
-    int depth;
-    const Hot* hots;
-    const int64_t* ids;          // NULL: envs 0 .. count - 1
-    int64_t count;
-    uint8_t* out;
+    EnvList list;                // the batch, the listed envs, their frames (bbai_kernels.hpp)
     const uint8_t* atlas;        // [n_tiles + 1][TS][TS][3], the last one all zero
     const uint8_t* lut;          // [2][5][256]
     int n_tiles, highlight;
@@ -55,6 +49,7 @@ struct GridArgs {
     uint32_t ppr;                // pieces per pixel row
     uint64_t ppr_magic;
 };
+static_assert(sizeof(GridArgs) == 328 && offsetof(GridArgs, atlas) == 256, "k_render_grid's argument layout");
 
 __device__ __forceinline__ uint32_t grid_div(uint32_t q, uint64_t magic) { return (uint32_t)(((uint64_t)q * magic) >> 32); }
 
@@ -77,30 +72,31 @@ __global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(Gr
     __shared__ Hot s_hot[GRID_MAX_ENVS];
     __shared__ const uint8_t* s_rec[GRID_MAX_ENVS];
     const int tid = threadIdx.x;
+    const EnvList& l = a.list;
     const uint8_t* atlas = a.atlas;
     if (G::LDS) {
         for (int k = tid; k < (a.n_tiles + 1) * G::BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_atlas)[k] = ((const u32x4*)a.atlas)[k];
         atlas = s_atlas;
     }
     for (int k = tid; k < GRID_LUT_BYTES / 16; k += GRID_BLOCK) ((u32x4*)s_lut)[k] = ((const u32x4*)a.lut)[k];
-    const int W = a.c.W, HW = a.c.W * a.c.H;
+    const int W = l.c.W, HW = l.c.W * l.c.H;
     const int64_t F16 = a.frame16;
     constexpr int ESTRIDE = GRID_BLOCK / GRID_MAX_ENVS;       // the envs' view work spread over the waves (two envs per wave)
-    u32x4* const out = (u32x4*)a.out;
+    u32x4* const out = (u32x4*)l.out;
     for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
         const int64_t first = a.slices > 1 ? item / a.slices : item * a.envs_per_item;      // first output frame of the item
         const int slice = (int)(item - first * a.slices);                                   // (0 unless sliced)
-        const int ne = a.slices > 1 ? 1 : (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
+        const int ne = a.slices > 1 ? 1 : (int)(l.count - first < a.envs_per_item ? l.count - first : a.envs_per_item);
         __syncthreads();                                  // atlas loaded / the previous item's ids consumed
         if (tid % ESTRIDE == 0 && tid / ESTRIDE < ne) {
             const int e = tid / ESTRIDE;
-            const int64_t env = a.ids ? a.ids[first + e] : first + e;
+            const int64_t env = l.ids ? l.ids[first + e] : first + e;
             const uint8_t* rec = nullptr;
             Hot h = {};
-            if (env >= 0 && env < a.n) {
-                h = a.hots[env];
-                rec = live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? h.slot : 0);
-                grid_highlight(a.c, rec, h, s_hl[e]);
+            if (env >= 0 && env < l.n) {
+                h = l.hots[env];
+                rec = live_rec(l.c, l.n, env, (uint8_t*)l.recs, (uint8_t*)l.ring, l.depth, l.ring ? h.slot : 0);
+                grid_highlight(l.c, rec, h, s_hl[e]);
             }
             s_hot[e] = h;
             s_rec[e] = rec;
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(Gr
             const int e = ci / HW, cell = ci - e * HW;
             const int y = cell / W, x = cell - y * W;
             const uint8_t* rec = s_rec[e];
-            s_ids[ci] = (uint8_t)(rec ? grid_tile(a.c, rec, s_hot[e], s_lut, a.highlight, s_hl[e], x, y) : a.n_tiles);
+            s_ids[ci] = (uint8_t)(rec ? grid_tile(l.c, rec, s_hot[e], s_lut, a.highlight, s_hl[e], x, y) : a.n_tiles);
         }
         __syncthreads();
         // chunks [q0, q1) of the item, counted from its first frame's first chunk
@@ -151,8 +147,8 @@ __global__ __launch_bounds__(GRID_BLOCK, TS == 16 ? 4 : 8) void k_render_grid(Gr
 //   3. stores the item's frames -- ONE contiguous byte range of `out` -- from LDS as 16-byte nontemporal chunks that cross frame boundaries
 //      freely (BossLevel: F = 1452, not a multiple of 16).  envs_per_item is a multiple of 16 / gcd(F, 16), so every item starts 16-byte
 //      aligned and only the end of the whole output can hold a partial chunk: that tail is stored byte by byte.
-// The next item's ids and Hots are loaded into registers while the current one is worked on.  Writes nothing but `out`.  An id outside
-// [0, n) gives an all-zero frame.
+// The next item's ids and Hots are loaded into registers while the current one is worked on (the item skeleton: bbai_kernels.hpp,
+// list_item_*).  Writes nothing but `out`.  An id outside [0, n) gives an all-zero frame.
 constexpr int FULL_BLOCK = 512;
 constexpr int FULL_LDS = 24576;               // frame bytes of one work item (3 x 25 x 25 x 16 = 30 000 > this: see full_launch)
 constexpr int FULL_APP = 16384;               // appearance rows of one work item
@@ -161,27 +157,12 @@ constexpr int FULL_BPC = 3;                   // persistent blocks per CU (≈ 4
 constexpr int FULL_UNROLL = 8;                // dword loads per lane in flight
 
 struct FullArgs {
-    LevelCfg c;
-    int64_t n;
-    const uint8_t* recs;
-    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
-    int depth;
-    const Hot* hots;
-    const int64_t* ids;          // NULL: envs 0 .. count - 1
-    int64_t count;
-    uint8_t* out;
+    EnvList list;                // the batch, the listed envs, their frames (bbai_kernels.hpp)
     int envs_per_item;
     int64_t items;
     uint64_t hw_magic, w_magic, rd_magic;   // multiply-high divides by W H, W and the dwords of an env's rows (grid_div; q < 2^16)
 };
-
-// (env, Hot) of entry k of an item: the Hot as one 16-byte load, zero for an id outside [0, n)
-__device__ __forceinline__ void full_entry(const FullArgs& a, int64_t k, int64_t& env, u32x4& h) {
-    env = a.ids ? a.ids[k] : k;
-    h = u32x4{0u, 0u, 0u, 0u};
-    if (env >= 0 && env < a.n) h = ((const u32x4*)a.hots)[env];
-    else env = -1;
-}
+static_assert(sizeof(FullArgs) == 296 && offsetof(FullArgs, envs_per_item) == 256, "k_full_obs's argument layout");
 
 __global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      // (6 waves per SIMD: FULL_BPC blocks per CU)
     __shared__ __attribute__((aligned(16))) uint8_t s_frames[FULL_LDS];
@@ -189,23 +170,18 @@ __global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      /
     __shared__ __attribute__((aligned(16))) Hot s_hot[FULL_MAX_ENVS];
     __shared__ const uint8_t* s_rec[FULL_MAX_ENVS];
     const int tid = threadIdx.x;
-    const int W = a.c.W, H = a.c.H, HW = W * H, F = 3 * HW, ES = a.c.ES;
+    const EnvList& l = a.list;
+    const int W = l.c.W, H = l.c.H, HW = W * H, F = 3 * HW, ES = l.c.ES;
     const int RD = H * ES / 4;                          // dwords of an env's interior rows (ES: a multiple of 4)
     const int D0 = MARGIN * ES / 4;                     // first dword of the interior rows
-    int64_t env = -1;
     u32x4 h = {0u, 0u, 0u, 0u};
     int64_t item = blockIdx.x;
-    if (item < a.items && tid < a.envs_per_item && item * a.envs_per_item + tid < a.count) full_entry(a, item * a.envs_per_item + tid, env, h);
+    int64_t env = item < a.items ? list_item_load(l, item, a.envs_per_item, tid, h) : -1;
     for (; item < a.items; item += gridDim.x) {
         const int64_t first = item * a.envs_per_item;
-        const int ne = (int)(a.count - first < a.envs_per_item ? a.count - first : a.envs_per_item);
+        const int ne = list_item_envs(l, first, a.envs_per_item);
         __syncthreads();                                  // the previous item's frames are stored
-        if (tid < ne) {
-            const uint8_t* rec = env >= 0 ? live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? (int)(h.w >> 24) : 0)      // (h.w >> 24 = slot)
-                                          : nullptr;
-            ((u32x4*)s_hot)[tid] = h;
-            s_rec[tid] = rec;
-        }
+        if (tid < ne) list_item_park(l, tid, env, h, s_hot, s_rec);
         __syncthreads();
         for (int k0 = tid; k0 < ne * RD; k0 += FULL_UNROLL * FULL_BLOCK) {
             uint32_t v[FULL_UNROLL];
@@ -223,11 +199,7 @@ __global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      /
             for (int u = 0; u < FULL_UNROLL; ++u)
                 if (k0 + u * FULL_BLOCK < ne * RD) s_app[k0 + u * FULL_BLOCK] = v[u];
         }
-        {   // the next item's entries, under this item's work
-            const int64_t nf = (item + gridDim.x) * a.envs_per_item;
-            env = -1;
-            if (item + gridDim.x < a.items && tid < a.envs_per_item && nf + tid < a.count) full_entry(a, nf + tid, env, h);
-        }
+        env = item + gridDim.x < a.items ? list_item_load(l, item + gridDim.x, a.envs_per_item, tid, h) : -1;      // the next item's entries, under this item's work
         __syncthreads();
         for (int ci = tid; ci < ne * HW; ci += FULL_BLOCK) {
             const int e = (int)grid_div((uint32_t)ci, a.hw_magic), cell = ci - e * HW;
@@ -237,9 +209,6 @@ __global__ __launch_bounds__(FULL_BLOCK, 6) void k_full_obs(FullArgs a) {      /
             else o[0] = o[1] = o[2] = 0;
         }
         __syncthreads();
-        const int bytes = ne * F, chunks = bytes >> 4;
-        uint8_t* const dst = a.out + first * F;           // 16-byte aligned (see above)
-        for (int q = tid; q < chunks; q += FULL_BLOCK) __builtin_nontemporal_store(((const u32x4*)s_frames)[q], (u32x4*)dst + q);
-        for (int b = (chunks << 4) + tid; b < bytes; b += FULL_BLOCK) dst[b] = s_frames[b];      // (the last item only)
+        list_item_store<FULL_BLOCK>(l.out + first * F, s_frames, ne * F, tid);       // 16-byte aligned (see above)
     }
 }

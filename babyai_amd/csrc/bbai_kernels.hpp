@@ -1,6 +1,7 @@
 // bbai_kernels.hpp -- what the engine's translation units and kernel headers share on the device side: the 16-byte vector type, the view's
 // cell count, the windows' bookkeeping and its constants, the look-ahead ring's addressing and the live record of both state layouts, the
-// refill list's shape, the lane-group context of the generators.  A definition that one kernel family alone uses is in that family's header.
+// refill list's shape, the listed-env observation kernels' argument record (EnvList) and item skeleton (list_item_*), the lane-group
+// context of the generators.  A definition that one kernel family alone uses is in that family's header.
 // (bbai_engine.hip: the host side; it includes a header per kernel family -- bbai_stepk.hpp, bbai_pregen.hpp, bbai_ring.hpp, bbai_botk.hpp,
 // bbai_render.hpp, bbai_gridk.hpp, bbai_tokens.hpp, bbai_demo.hpp, bbai_statek.hpp, bbai_reseedk.hpp -- and each of them includes this one.  bbai_genlane.hip: k_pregen_lane.)
 #pragma once
@@ -69,6 +70,58 @@ __device__ __forceinline__ int live_slot(int next_slot, int depth) { return (nex
 __device__ __forceinline__ uint8_t* live_rec(const LevelCfg& c, int64_t n, int64_t env, uint8_t* recs, uint8_t* ring, int depth, int next_slot) {
     (void)n;
     return ring ? ring + ring_at(live_slot(next_slot, depth), env, depth) * (int64_t)c.rec_bytes : recs + env * (int64_t)c.rec_bytes;
+}
+
+// ---- observations of LISTED envs, drawn from the live state (bbai_gridk.hpp: k_render_grid, k_full_obs; bbai_viewn.hpp: k_view_obs) -------
+// The batch's live state, the listed envs, and where their frames go: frame k of `out` is the observation of env ids[k].  Each family's
+// argument struct opens with this record (bbai_engine.hip: env_list fills it).
+struct EnvList {
+    LevelCfg c;
+    int64_t n;
+    const uint8_t* recs;
+    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
+    int depth;
+    const Hot* hots;
+    const int64_t* ids;          // NULL: envs 0 .. count - 1
+    int64_t count;
+    uint8_t* out;
+};
+
+// (env, Hot) of entry k: the Hot as one 16-byte load; env = -1 and a zero Hot for an id outside [0, n)
+__device__ __forceinline__ void list_entry(const EnvList& l, int64_t k, int64_t& env, u32x4& h) {
+    env = l.ids ? l.ids[k] : k;
+    h = u32x4{0u, 0u, 0u, 0u};
+    if (env >= 0 && env < l.n) h = ((const u32x4*)l.hots)[env];
+    else env = -1;
+}
+// the live record of entry (env, h) in both state layouts (h.w >> 24 = Hot::slot), NULL for env = -1
+__device__ __forceinline__ const uint8_t* list_rec(const EnvList& l, int64_t env, const u32x4& h) {
+    return env >= 0 ? live_rec(l.c, l.n, env, (uint8_t*)l.recs, (uint8_t*)l.ring, l.depth, l.ring ? (int)(h.w >> 24) : 0) : nullptr;
+}
+
+// The item skeleton of the persistent blocks of k_full_obs and k_view_obs<V>, in pieces: an item is `epi` consecutive entries, one lane
+// each; block b works items b, b + gridDim.x, ...  The kernel keeps (env, h) of its CURRENT item in registers: list_item_load ahead of
+// the loop for the first item and, under an item's work, for the next one; behind a barrier list_item_park puts them, with the record,
+// where the whole block reads them; the item's frames, built in LDS, leave through list_item_store.  The barriers are the kernel's.
+__device__ __forceinline__ int list_item_envs(const EnvList& l, int64_t first, int epi) { return (int)(l.count - first < epi ? l.count - first : epi); }
+// lane tid's entry of item `item`: returns its env, the Hot in h (-1, h as it was: the item has no such entry).  Whether there IS such an
+// item is the block's question, not the lane's: the kernel asks it at the call
+__device__ __forceinline__ int64_t list_item_load(const EnvList& l, int64_t item, int epi, int tid, u32x4& h) {
+    int64_t env = -1;
+    if (tid < epi && item * epi + tid < l.count) list_entry(l, item * epi + tid, env, h);
+    return env;
+}
+// lane tid (< the item's envs) parks its entry and its live record in LDS
+__device__ __forceinline__ void list_item_park(const EnvList& l, int tid, int64_t env, const u32x4& h, Hot* s_hot, const uint8_t** s_rec) {
+    ((u32x4*)s_hot)[tid] = h;
+    s_rec[tid] = list_rec(l, env, h);
+}
+// `bytes` bytes of frames from LDS to dst (16-byte aligned) as 16-byte nontemporal chunks, the tail -- the last item's only -- byte by byte
+template <int BLOCK>
+__device__ __forceinline__ void list_item_store(uint8_t* dst, const uint8_t* s_frames, int bytes, int tid) {
+    const int chunks = bytes >> 4;
+    for (int q = tid; q < chunks; q += BLOCK) __builtin_nontemporal_store(((const u32x4*)s_frames)[q], (u32x4*)dst + q);
+    for (int b = (chunks << 4) + tid; b < bytes; b += BLOCK) dst[b] = s_frames[b];
 }
 
 // One env per group of G lanes, 64 / G envs per wavefront (bbai_gen.hpp "Execution model").  sync() orders the group's LDS

@@ -11,7 +11,8 @@
 // reset() / step(): an env with hot.step == 0 and Prog.start_carry set shows the object on pos[start_carry] with app[start_carry] and the
 // agent's cell empty -- what the 7x7 first observation of such an env shows (tests/test_full_obs_host.py::test_start_carrying_level_at_reset).
 //
-// Two forms of the same rule, both compiled by the host tests (tests/test_view_size_host.py):
+// Two forms of the same rule -- ONE body (observe_env_keys_n) over two ways of fetching a cell's appearance --, both compiled by the host
+// tests (tests/test_view_size_host.py):
 //   observe_env_n         the reference form: every cell read from the record's appearance plane;
 //   observe_env_staged_n  the kernel's form on the host: the window staged as clamped dwords (view_win_dword), cells read from the stage
 //                         (view_win_key) -- exactly the loads k_view_obs<V> issues, so the host build (and a sanitizer on it) checks the bounds.
@@ -80,28 +81,30 @@ BB_HD ViewExtra view_extra(const LevelCfg& c, const uint8_t* rec, const Hot& h) 
     return x;
 }
 
-// The three bytes of view cell (vi, vj) showing world cell (x, y) whose plane appearance is `key` (a wall outside the grid -- the caller's rule).
-BB_HD void view_cell_n(int V, const Hot& h, const ViewExtra& ex, int vi, int vj, int x, int y, int key, bool seen, uint8_t* o) {
-    int e = key;
-    if (x == ex.qx && y == ex.qy) e = ex.qapp;
-    if (vi == V / 2 && vj == V - 1) { e = ex.agent; seen = true; }
-    (void)h;
+// The override rule: what view cell (vi, vj), showing world cell (x, y) whose plane appearance is `key` (a wall outside the grid -- the
+// caller's rule), shows.  Sight is decided on the PLANE's keys: neither object blocks it.  (Both host forms and k_view_obs's row stage.)
+BB_HD int view_shown_n(int V, const ViewExtra& ex, int vi, int vj, int x, int y, int key) {
+    if (x == ex.qx && y == ex.qy) key = ex.qapp;
+    if (vi == V / 2 && vj == V - 1) key = ex.agent;
+    return key;
+}
+// The three bytes of that cell.  (The agent's cell always comes out seen: process_vis_rows_n starts its sweep there.)
+BB_HD void view_cell_n(int V, const ViewExtra& ex, int vi, int vj, int x, int y, int key, bool seen, uint8_t* o) {
+    const int e = view_shown_n(V, ex, vi, vj, x, y, key);
     o[0] = (uint8_t)(seen ? e_type(e) : 0); o[1] = (uint8_t)(seen ? e_color(e) : 0); o[2] = (uint8_t)(seen ? e_state(e) : 0);
 }
 
 BB_HD bool in_grid(const LevelCfg& c, int x, int y) { return (unsigned)x < (unsigned)c.W && (unsigned)y < (unsigned)c.H; }
 
-// Reference form: gen_obs_grid + encode at view size V for one env, out[(vi * V + vj) * 3 + channel].
-BB_HD void observe_env_n(const LevelCfg& c, const uint8_t* rec, const Hot& h, int V, uint8_t* out) {
-    uint8_t cell[VIEWN_MAX][VIEWN_MAX];
+// gen_obs_grid + encode at view size V for one env, out[(vi * V + vj) * 3 + channel]; key_at(x, y) = the plane appearance of world cell (x, y).
+template <class KeyAt>
+BB_HD void observe_env_keys_n(const LevelCfg& c, const uint8_t* rec, const Hot& h, int V, KeyAt key_at, uint8_t* out) {
     uint32_t opq[VIEWN_MAX], vis[VIEWN_MAX];
     for (int vj = 0; vj < V; ++vj) {
         uint32_t o = 0;
         for (int vi = 0; vi < V; ++vi) {
             int x, y; view_to_world_n(V, h.ax, h.ay, h.dir, vi, vj, x, y);
-            const int e = in_grid(c, x, y) ? rec[e_index(c, x, y)] : (int)E_WALL;
-            cell[vj][vi] = (uint8_t)e;
-            if (e_opaque(e)) o |= 1u << vi;
+            if (e_opaque(key_at(x, y))) o |= 1u << vi;
         }
         opq[vj] = o;
     }
@@ -110,8 +113,13 @@ BB_HD void observe_env_n(const LevelCfg& c, const uint8_t* rec, const Hot& h, in
     for (int vi = 0; vi < V; ++vi)
         for (int vj = 0; vj < V; ++vj) {
             int x, y; view_to_world_n(V, h.ax, h.ay, h.dir, vi, vj, x, y);
-            view_cell_n(V, h, ex, vi, vj, x, y, cell[vj][vi], (vis[vj] >> vi) & 1u, out + (vi * V + vj) * 3);
+            view_cell_n(V, ex, vi, vj, x, y, key_at(x, y), (vis[vj] >> vi) & 1u, out + (vi * V + vj) * 3);
         }
+}
+
+// Reference form: every cell from the record's appearance plane.
+BB_HD void observe_env_n(const LevelCfg& c, const uint8_t* rec, const Hot& h, int V, uint8_t* out) {
+    observe_env_keys_n(c, rec, h, V, [&](int x, int y) { return in_grid(c, x, y) ? rec[e_index(c, x, y)] : (int)E_WALL; }, out);
 }
 
 // ---- the staged window: V rows of ND dwords, what k_view_obs<V> loads ------------------------------------------------------------
@@ -136,26 +144,10 @@ BB_HD int view_win_key(const LevelCfg& c, int tx, int x, int y, const uint8_t* r
 BB_HD void observe_env_staged_n(const LevelCfg& c, const uint8_t* rec, const Hot& h, int V, uint8_t* out) {
     const int ND = view_nd(V);
     uint32_t win[VIEWN_MAX * 4];
-    uint32_t opq[VIEWN_MAX], vis[VIEWN_MAX];
     int tx, ty; view_top_left_n(V, h.ax, h.ay, h.dir, tx, ty);
     for (int r = 0; r < V; ++r)
         for (int k = 0; k < ND; ++k) win[r * ND + k] = ((const uint32_t*)rec)[view_win_dword(c, tx, ty, r, k)];
-    for (int vj = 0; vj < V; ++vj) {
-        uint32_t o = 0;
-        for (int vi = 0; vi < V; ++vi) {
-            int x, y; view_to_world_n(V, h.ax, h.ay, h.dir, vi, vj, x, y);
-            if (e_opaque(view_win_key(c, tx, x, y, (const uint8_t*)(win + (y - ty) * ND)))) o |= 1u << vi;
-        }
-        opq[vj] = o;
-    }
-    process_vis_rows_n(V, opq, vis);
-    const ViewExtra ex = view_extra(c, rec, h);
-    for (int vi = 0; vi < V; ++vi)
-        for (int vj = 0; vj < V; ++vj) {
-            int x, y; view_to_world_n(V, h.ax, h.ay, h.dir, vi, vj, x, y);
-            view_cell_n(V, h, ex, vi, vj, x, y, view_win_key(c, tx, x, y, (const uint8_t*)(win + (y - ty) * ND)), (vis[vj] >> vi) & 1u,
-                        out + (vi * V + vj) * 3);
-        }
+    observe_env_keys_n(c, rec, h, V, [&](int x, int y) { return view_win_key(c, tx, x, y, (const uint8_t*)(win + (y - ty) * ND)); }, out);
 }
 
 }  // namespace bbai
@@ -171,15 +163,15 @@ using namespace bbai;
 // Work item = ViewN<V>::EPI envs (a multiple of 16: F = 3 V^2 is odd, so every item's range of `out` starts 16-byte aligned and only the
 // end of the whole output can hold a partial chunk, stored byte by byte).  Per item a block
 //   1. (one lane per env) has the env's id and Hot in registers -- loaded under the previous item's work --, finds the live record
-//      (live_rec: both state layouts) and parks both in LDS;
+//      and parks both in LDS (the item skeleton k_full_obs is built from as well: bbai_kernels.hpp, list_item_load / _park);
 //   2. issues ALL loads of the item before the first use: the V x ND clamped dwords of every env's window (view_win_dword; ITER independent
 //      loads per lane, statically indexed registers), and per env the carried object's appearance and Prog.start_carry -- ONE round trip.
 //      Only an env of a start-carrying level at step 0 pays a second one (its object's cell and appearance);
-//   3. a lane per view row vj: the row's V appearance bytes (view_win_key; the agent's cell and the quirk's cell as view_cell_n overrides
+//   3. a lane per view row vj: the row's V appearance bytes (view_win_key; the agent's cell and the quirk's cell as view_shown_n overrides
 //      them) parked in LDS in output order [vi][vj], and its opacity mask; then process_vis_rows_n, a lane per env, in place; then the
 //      cells, FOUR per lane: one dword of parked keys in, the visibility bits, twelve bytes = three dwords into the item's frames in LDS
 //      at the output pitch (cell k of the item is bytes 3 k .. 3 k + 2 of its frames);
-//   4. stores the frames -- ONE contiguous byte range of `out` -- as 16-byte nontemporal chunks.
+//   4. stores the frames -- ONE contiguous byte range of `out` -- as 16-byte nontemporal chunks (list_item_store).
 // Writes nothing but `out`; an id outside [0, n) gives an all-zero frame.  No scratch: every register array is indexed statically.
 constexpr int VIEWN_BLOCK = 256;
 constexpr int VIEWN_BPC = 4;                  // persistent blocks per CU
@@ -195,25 +187,10 @@ template <int V> struct ViewN {
 };
 
 struct ViewNArgs {
-    LevelCfg c;
-    int64_t n;
-    const uint8_t* recs;
-    const uint8_t* ring;         // in-place layout: the live records are ring slots; else NULL
-    int depth;
-    const Hot* hots;
-    const int64_t* ids;          // NULL: envs 0 .. count - 1
-    int64_t count;
-    uint8_t* out;
+    EnvList list;                // the batch, the listed envs, their frames (bbai_kernels.hpp)
     int64_t items;
 };
-
-// (env, Hot) of entry k: the Hot as one 16-byte load, env = -1 for an id outside [0, n)
-__device__ __forceinline__ void viewn_entry(const ViewNArgs& a, int64_t k, int64_t& env, u32x4& h) {
-    env = a.ids ? a.ids[k] : k;
-    h = u32x4{0u, 0u, 0u, 0u};
-    if (env >= 0 && env < a.n) h = ((const u32x4*)a.hots)[env];
-    else env = -1;
-}
+static_assert(sizeof(ViewNArgs) == 264 && offsetof(ViewNArgs, items) == 256, "k_view_obs's argument layout");
 
 template <int V>
 __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
@@ -227,20 +204,15 @@ __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
     __shared__ uint32_t s_row[EPI * V];           // opacity rows, then visibility rows
     __shared__ __attribute__((aligned(16))) uint8_t s_key[EPI * V * V];      // the cells' appearance bytes, [env][vi][vj]
     const int tid = threadIdx.x;
-    int64_t env = -1;
+    const EnvList& l = a.list;
     u32x4 h = {0u, 0u, 0u, 0u};
     int64_t item = blockIdx.x;
-    if (item < a.items && tid < EPI && item * EPI + tid < a.count) viewn_entry(a, item * EPI + tid, env, h);
+    int64_t env = item < a.items ? list_item_load(l, item, EPI, tid, h) : -1;
     for (; item < a.items; item += gridDim.x) {
         const int64_t first = item * EPI;
-        const int ne = (int)(a.count - first < EPI ? a.count - first : EPI);
+        const int ne = list_item_envs(l, first, EPI);
         __syncthreads();                                  // the previous item's frames are stored
-        if (tid < ne) {
-            const uint8_t* rec = env >= 0 ? live_rec(a.c, a.n, env, (uint8_t*)a.recs, (uint8_t*)a.ring, a.depth, a.ring ? (int)(h.w >> 24) : 0)      // (h.w >> 24 = slot)
-                                          : nullptr;
-            ((u32x4*)s_hot)[tid] = h;
-            s_rec[tid] = rec;
-        }
+        if (tid < ne) list_item_park(l, tid, env, h, s_hot, s_rec);
         __syncthreads();
         {   // every load of the item, then its uses
             uint32_t v[ITER];
@@ -257,13 +229,13 @@ __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
                     if (rec) {
                         const Hot hh = s_hot[e];
                         int tx, ty; view_top_left_n(V, hh.ax, hh.ay, hh.dir, tx, ty);
-                        v[u] = ((const uint32_t*)rec)[view_win_dword(a.c, tx, ty, r, d)];
+                        v[u] = ((const uint32_t*)rec)[view_win_dword(l.c, tx, ty, r, d)];
                     }
                 }
             }
             if (myrec) {
-                if (myhot.carry != NONE8 && myhot.carry < a.c.maxo) ce = myrec[a.c.off_app + myhot.carry];
-                sc = myrec[a.c.off_prog + (int)offsetof(Prog, start_carry)];
+                if (myhot.carry != NONE8 && myhot.carry < l.c.maxo) ce = myrec[l.c.off_app + myhot.carry];
+                sc = myrec[l.c.off_prog + (int)offsetof(Prog, start_carry)];
             }
 #pragma unroll
             for (int u = 0; u < ITER; ++u)
@@ -271,18 +243,14 @@ __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
             if (tid < ne) {
                 ViewExtra ex;
                 ex.agent = ce; ex.qx = ex.qy = -1; ex.qapp = E_EMPTY;
-                if (myrec && myhot.step == 0 && sc != NONE8 && sc < a.c.maxo) {      // the start-carrying quirk: a second round trip, at reset only
-                    ex.qx = myrec[a.c.off_pos + 2 * sc]; ex.qy = myrec[a.c.off_pos + 2 * sc + 1]; ex.qapp = myrec[a.c.off_app + sc];
+                if (myrec && myhot.step == 0 && sc != NONE8 && sc < l.c.maxo) {      // the start-carrying quirk: a second round trip, at reset only
+                    ex.qx = myrec[l.c.off_pos + 2 * sc]; ex.qy = myrec[l.c.off_pos + 2 * sc + 1]; ex.qapp = myrec[l.c.off_app + sc];
                     ex.agent = E_EMPTY;
                 }
                 s_ex[tid] = ex;
             }
         }
-        {   // the next item's entries, under this item's work
-            const int64_t nf = (item + gridDim.x) * EPI;
-            env = -1;
-            if (item + gridDim.x < a.items && tid < EPI && nf + tid < a.count) viewn_entry(a, nf + tid, env, h);
-        }
+        env = item + gridDim.x < a.items ? list_item_load(l, item + gridDim.x, EPI, tid, h) : -1;      // the next item's entries, under this item's work
         __syncthreads();
         for (int k = tid; k < ne * V; k += VIEWN_BLOCK) {             // view row vj of env e: its keys and its opacity mask
             const int e = k / V, vj = k - e * V;
@@ -295,11 +263,9 @@ __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
 #pragma unroll
                 for (int vi = 0; vi < V; ++vi) {
                     int x, y; view_to_world_n(V, hh.ax, hh.ay, hh.dir, vi, vj, x, y);
-                    int key = view_win_key(a.c, tx, x, y, (const uint8_t*)(s_win + e * WIN + (y - ty) * ND));
+                    int key = view_win_key(l.c, tx, x, y, (const uint8_t*)(s_win + e * WIN + (y - ty) * ND));
                     if (e_opaque(key)) o |= 1u << vi;
-                    if (x == ex.qx && y == ex.qy) key = ex.qapp;                    // (as view_cell_n: neither object blocks sight)
-                    if (vi == V / 2 && vj == V - 1) key = ex.agent;
-                    keys[vi * V] = (uint8_t)key;
+                    keys[vi * V] = (uint8_t)view_shown_n(V, ex, vi, vj, x, y, key);
                 }
             } else {
 #pragma unroll
@@ -328,10 +294,7 @@ __global__ __launch_bounds__(VIEWN_BLOCK, 4) void k_view_obs(ViewNArgs a) {
             o[2] = (b[2] >> 16) | (b[3] << 8);
         }
         __syncthreads();
-        const int bytes = ne * F, chunks = bytes >> 4;
-        uint8_t* const dst = a.out + first * F;           // 16-byte aligned (see above)
-        for (int q = tid; q < chunks; q += VIEWN_BLOCK) __builtin_nontemporal_store(((const u32x4*)s_frames)[q], (u32x4*)dst + q);
-        for (int b = (chunks << 4) + tid; b < bytes; b += VIEWN_BLOCK) dst[b] = s_frames[b];      // (the last item only)
+        list_item_store<VIEWN_BLOCK>(l.out + first * F, s_frames, ne * F, tid);      // 16-byte aligned (see above)
     }
 }
 #endif
