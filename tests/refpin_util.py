@@ -56,6 +56,65 @@ class Digest(object):
         return self.h.hexdigest()
 
 
+def level_digest(grid, image, agent, max_steps, mission):
+    """The level digest of tests/golden/refpin/gen_digest/: the first 4 bytes of sha256 (little endian, as a uint32) over
+      - the grid after the reset, uint8[H][W], one byte per cell: type | color << 3 | state << 6;
+      - the first observation, uint8[7][7][3] (on the *Carrying levels taken BEFORE the object moves into the agent's hands; the grid after);
+      - agent x, y, dir, one byte each;
+      - max_steps, 2 bytes little endian;
+      - the mission string, UTF-8.
+    Four producers feed it: a reference env (tools/gen_golden_refpin.py gen), an oracle env, the engine's host build and the engine."""
+    grid, image = np.asarray(grid), np.asarray(image)
+    assert grid.ndim == 2 and grid.dtype == np.uint8 and image.shape == (7, 7, 3) and image.dtype == np.uint8
+    h = hashlib.sha256()
+    h.update(np.ascontiguousarray(grid).tobytes())
+    h.update(np.ascontiguousarray(image).tobytes())
+    h.update(bytes([int(agent[0]), int(agent[1]), int(agent[2])]))
+    h.update(int(max_steps).to_bytes(2, "little"))
+    h.update(mission.encode("utf-8"))
+    return int.from_bytes(h.digest()[:4], "little")
+
+
+def env_level_digest(env, obs):
+    """level_digest of a reference or oracle env right after `obs = env.reset()`."""
+    g = np.asarray(env.grid.encode())
+    grid = (g[:, :, 0] | (g[:, :, 1] << 3) | (g[:, :, 2] << 6)).T.astype(np.uint8)
+    return level_digest(grid, np.asarray(obs["image"], dtype=np.uint8), (env.agent_pos[0], env.agent_pos[1], env.agent_dir),
+                        env.max_steps, obs["mission"])
+
+
+def record_level_digests(cfg, rec, hot, image, missions=None):
+    """uint32[N]: level_digest of every env of a batch in the engine's state format -- records uint8[N, rec_bytes], hot uint8[N, 16]
+    (bytes 0, 1, 2 = agent x, y, dir; 6, 7 = max_steps), the first observations uint8[N, 7, 7, 3] -- as HostBatch holds it and as
+    export_state() / env.image return it.  `missions`: the N strings (env.missions()); None = rendered from each record's program."""
+    from babyai_amd.missions import prog_surface
+    rec, hot, image = np.asarray(rec), np.asarray(hot).view(np.uint8).reshape(len(rec), -1), np.asarray(image)
+    grids = rec[:, :cfg.ES * cfg.EH].reshape(-1, cfg.EH, cfg.ES)[:, 5:5 + cfg.H, 5:5 + cfg.W]
+    out = np.zeros(len(rec), np.uint32)
+    for i in range(len(rec)):
+        m = missions[i] if missions is not None else prog_surface(rec[i, cfg.off_prog:cfg.off_prog + 112])
+        out[i] = level_digest(grids[i], image[i], hot[i, :3], int(hot[i, 6]) | int(hot[i, 7]) << 8, m)
+    return out
+
+
+GEN_DIGEST_SEED0, GEN_DIGEST_SEEDS, GEN_DIGEST_LEVELS = 52000, 512, 6
+
+
+def gen_digest_fixture(name):
+    """uint32[512, 6]: the reference's level digests of kind `name`, seeds 52000 + i, six consecutive resets each."""
+    return np.load(golden_path(os.path.join("gen_digest", name + ".npy")))
+
+
+def digest_mismatch(name, got, want, what):
+    """Raise with the number of (seed, level) pairs whose digests differ and the first few of them (got, want: uint32[n_seeds, n_levels])."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.uint32, (got.shape, want.shape, got.dtype, want.dtype)
+    if not np.array_equal(got, want):
+        bad = np.argwhere(got != want)
+        raise AssertionError("%s %s: %d of %d digests differ from the reference's, first (seed, level) %s"
+                             % (name, what, len(bad), got.size, [(GEN_DIGEST_SEED0 + int(i), int(k)) for i, k in bad[:8]]))
+
+
 def reference_level(level_dict, name, **kw):
     """A reference level object as the tests always built it: without the stale `locked_room` the reference's entropy-seeded
     constructor leaves behind (tools/gen_golden.py)."""

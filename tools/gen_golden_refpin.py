@@ -4,7 +4,7 @@ gym_minigrid shim of oracle/shim (oracle/refenv.py finds the tree; BABYAI_REFERE
 travels with the repository: the fixtures are committed, and the tests replay the protocols of tests/refpin_util.py on the oracle
 and on the engine's host build against them.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_refpin.py [part ...]      parts: levels random strict vocab rollout bot (default: all)
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_refpin.py [part ...]      parts: levels random strict vocab rollout bot gen (default: all)
 
   levels   the 105 registered ids, the constructor attributes of every level, and what the reference's own smoke test of
            levelgen.py reads (surface / grid of a seed-0 construction, the mission of its first reset)  -> levels.json
@@ -14,6 +14,8 @@ and on the engine's host build against them.
   rollout  the reference's BaseAlgo.collect_experiences (babyai/rl/algos/base.py) over tests/rollout_util.ToyACModel -> rollout.npz
   bot      the reference's expert (babyai/bot.py) answering tests/test_hostsim_bot.py's live protocols: every decision, step result
            and stack depth, in call order (refpin_util.Recording; the tests replay them)                 -> bot_reference.json.gz
+  gen      the level digest (refpin_util.level_digest: grid, first observation, pose, max_steps, mission) of every registered level,
+           seeds 52000 .. 52511, six consecutive resets each, over at most 8 worker processes         -> gen_digest/<Level>.npy, README.md
 """
 import json
 import os
@@ -184,7 +186,48 @@ def part_bot():
     print("wrote", rp.golden_path("bot_reference.json.gz"))
 
 
-PARTS = {"levels": part_levels, "random": part_random, "strict": part_strict, "vocab": part_vocab, "rollout": part_rollout, "bot": part_bot}
+def _gen_kind(name):
+    """uint32[512, 6]: the reference's digests of one kind -- Level(), .seed(52000 + i), six reset()s in a row."""
+    out = np.zeros((rp.GEN_DIGEST_SEEDS, rp.GEN_DIGEST_LEVELS), np.uint32)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for i in range(rp.GEN_DIGEST_SEEDS):
+            env = rp.reference_level(level_dict, name)
+            env.seed(rp.GEN_DIGEST_SEED0 + i)
+            for k in range(rp.GEN_DIGEST_LEVELS):
+                obs = env.reset()
+                out[i, k] = rp.env_level_digest(env, obs)
+    return name, out
+
+
+def part_gen():
+    import multiprocessing
+    names = sorted(level_dict)
+    d = rp.golden_path("gen_digest")
+    os.makedirs(d, exist_ok=True)
+    with multiprocessing.get_context("fork").Pool(min(8, os.cpu_count() or 1)) as pool:
+        got = dict(pool.imap_unordered(_gen_kind, names))
+    lines = ["# Level digests of the reference's generator", "",
+             "`<Level>.npy` = `uint32[%d, %d]`: `refpin_util.level_digest` (grid after the reset, first observation, agent pose, `max_steps`,"
+             % (rp.GEN_DIGEST_SEEDS, rp.GEN_DIGEST_LEVELS),
+             "mission) of the reference's level object after `.seed(%d + i)` and each of six `reset()` calls in a row.  Recorded from the"
+             % rp.GEN_DIGEST_SEED0,
+             "reference itself, never edited by hand; regenerate (byte-identical) where the reference tree can be imported with", "",
+             "    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_refpin.py gen", "",
+             "Distinct digests among the %d of each kind (a kind with few objects and a small room repeats levels; a digest that"
+             % (rp.GEN_DIGEST_SEEDS * rp.GEN_DIGEST_LEVELS),
+             "saw less than the whole level would repeat far more often):", "", "| level | distinct |", "|---|---|"]
+    for name in names:
+        np.save(os.path.join(d, name + ".npy"), got[name])
+        distinct = len(np.unique(got[name]))
+        print("%-28s %4d distinct of %d" % (name, distinct, got[name].size))
+        lines.append("| %s | %d |" % (name, distinct))
+    with open(os.path.join(d, "README.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", d)
+
+
+PARTS = {"levels": part_levels, "random": part_random, "strict": part_strict, "vocab": part_vocab, "rollout": part_rollout, "bot": part_bot, "gen": part_gen}
 
 if __name__ == "__main__":
     for p in sys.argv[1:] or list(PARTS):
