@@ -1572,12 +1572,14 @@ constexpr int64_t STEP_RENDER_SPLIT_MIN = 262144;
 #ifndef STEP_RENDER_SPLIT_DEFAULT
 #define STEP_RENDER_SPLIT_DEFAULT 0
 #endif
-// Option "render_delta_from_step" -1 (default): from this batch size up.  BossLevel pixels, bench.py's random actions, kernel medians
-// (profiles/render_delta_from_step/): at 1 048 576 envs the render gains more than k_step pays (k_render 608 -> 529 us, k_step 100 -> 143,
-// settings alternated in one process: 0.704 -> 0.666 ms per step); at 131 072 / 262 144 / 524 288 envs the render's inputs stay in the
-// memory-side cache, k_render_delta's input stage is nearly free and the render does not gain (82 / 153 / 288 us either way) while k_step
-// pays 11-22 us.
-constexpr int64_t RENDER_FROM_STEP_MIN_ENVS = 786432;
+// Option "render_delta_from_step" -1 (default): from this batch size up.  BossLevel pixels, bench.py's random actions.  First set to 786 432
+// (profiles/render_delta_from_step/): at 1 048 576 envs the render gained more than k_step paid (k_render 608 -> 529 us, k_step 100 -> 143,
+// settings alternated in one process: 0.704 -> 0.666 ms per step), while at 131 072 / 262 144 / 524 288 envs k_render_delta's input stage
+// was nearly free (82 / 153 / 288 us either way) and k_step paid 11-22 us.  Both sides have moved since: the store-only render is the
+// ticketed k_render_dstore_lw, and step_dirty works on four cells per word.  Option 0 against 1 alternated in one process, four repetitions
+// each (profiles/step_dirty_packed/ab_from_step_*.jsonl), ms per step: 131 072 envs 0.0964-0.0992 against 0.0958-0.0975 (the ranges
+// overlap), 262 144 envs 0.1652-0.1686 against 0.1585-0.1611, 524 288 envs 0.3126-0.3191 against 0.2969-0.3002 (apart, -4 to -5 %).
+constexpr int64_t RENDER_FROM_STEP_MIN_ENVS = 262144;
 static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, hipStream_t s, bool& dirty) {
     StepPlan p;
     {

@@ -17,6 +17,7 @@
 #include "bbai_kernels.hpp"
 #include "bbai_step.hpp"
 #include "bbai_view.hpp"
+#include "bbai_dirty.hpp"
 
 using namespace bbai;
 
@@ -690,10 +691,12 @@ __device__ __forceinline__ bool step_body(const LevelCfg& c, int64_t n, uint8_t*
 // step_body has stored the block's rows: lanes over (env, cell) of the block's 64 rows, 16 cells per lane and chunk -- the chunk's 16 shadow
 // bytes in one coalesced 16-byte load, its 48 encoding bytes in three 16-byte LDS reads (a row is 49 cells at the output pitch of 147 =
 // 3 x 49: cell b of the block is LDS bytes [3 b, 3 b + 3)) -- the new tile id of every cell (the same s_lut lookup as k_render, the agent's
-// table for AGENT_CELL), the changed ones written back to the shadow (the chunk whole, where one differs), and per env a 64-bit dirty mask
-// (bit = cell) into `dmask`: gathered by LDS atomics in the first 512 bytes of the row area, which nothing reads any more.
+// table for AGENT_CELL; four cells per word, dirty_chunk of bbai_dirty.hpp), the changed ones written back to the shadow (the chunk whole,
+// where one differs), and per env a 64-bit dirty mask (bit = cell) into `dmask`: the chunk's 16 changed-cell bits split at the env boundary
+// (dirty_split) and gathered by LDS atomics in the first 512 bytes of the row area, which nothing reads any more.
 constexpr int DIRTY_CHUNKS = (STEP_BLOCK * CELLS / 16 + STEP_BLOCK - 1) / STEP_BLOCK;      // 16-byte shadow chunks per lane: 196 per block -> 4
 static_assert(STEP_BLOCK * CELLS % 16 == 0 && OBS_BYTES == 3 * CELLS, "a block's shadow rows are whole 16-byte chunks; a row is 3 bytes per cell");
+static_assert(DIRTY_CELLS == CELLS && DIRTY_AGENT == AGENT_CELL && DIRTY_CHUNK == 16, "bbai_dirty.hpp restates the view's geometry for the host build");
 __device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __restrict__ shadow /* [n][49] */, uint64_t* __restrict__ dmask /* [n] */,
                                            const uint8_t* __restrict__ lut, uint8_t* const s_rows, uint8_t* const s_lut, const int lane) {
     const int nb = n - env0 < STEP_BLOCK ? (int)(n - env0) : STEP_BLOCK;
@@ -723,28 +726,12 @@ __device__ __forceinline__ void step_dirty(int64_t n, int64_t env0, uint8_t* __r
         const u32x4* enc = (const u32x4*)(s_rows + 48 * v);
         const u32x4 q0 = enc[0], q1 = enc[1], q2 = enc[2];
         const uint32_t ew[12] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2[0], q2[1], q2[2], q2[3]};
-        const int ea = 16 * v / CELLS;
-        int cell = 16 * v - ea * CELLS;
-        bool second = false;
-        uint32_t nw[4] = {0, 0, 0, 0};
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            if (16 * v + i < nbytes) {
-                const int o0 = (ew[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 0xFF;
-                const int o1 = (ew[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 0xFF;
-                const int o2 = (ew[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 0xFF;
-                const int key = o0 | (o1 << 3) | (o2 << 6);
-                const uint32_t id = s_lut[(cell == AGENT_CELL ? 256 : 0) + key];
-                nw[i >> 2] |= id << (8 * (i & 3));
-                if (id != ((old[k][i >> 2] >> (8 * (i & 3))) & 0xFFu)) {
-                    any = true;
-                    if (second) mb[k] |= 1ull << cell; else ma[k] |= 1ull << cell;
-                }
-            }
-            if (++cell == CELLS) { cell = 0; second = true; }
-        }
-        if (any) {
+        // four cells per word (bbai_dirty.hpp): keys by byte permutes, the agent's id patched in once per chunk, the changed cells as 16 bits
+        const int c0 = 16 * v - 16 * v / CELLS * CELLS;          // the chunk's first cell
+        uint32_t nw[4];
+        const uint32_t bits = dirty_chunk(ew, old[k], s_lut, c0, nbytes - 16 * v, nw);
+        dirty_split(bits, c0, ma[k], mb[k]);
+        if (bits) {
             if (16 * v + 16 <= nbytes) { u32x4 w = {nw[0], nw[1], nw[2], nw[3]}; ((u32x4*)sh)[v] = w; }
             else for (int i = 0; i < 16 && 16 * v + i < nbytes; ++i) sh[16 * v + i] = (uint8_t)(nw[i >> 2] >> (8 * (i & 3)));
         }
