@@ -22,6 +22,8 @@
 //   bbai_viewn.hpp    k_view_obs<V>: the egocentric observation at view sizes 3 .. 11 (ViewSizeWrapper).  (viewn_launch)
 //   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32 (render_view_launch); k_view_delta<TS> / k_view_ids: a whole
 //                     batch into the target registered at that size, only the 64-byte pieces whose cells changed.  (view_delta_launch)
+//   bbai_viewpxn.hpp  k_view_pixels_n<V, TS>: the V x V view as pixels, view sizes 3 .. 11 at tile sizes 8 / 16 / 32, of rows of an encoded
+//                     buffer (include/bbai_view_pixels.h).  (view_pixels_launch)
 //   bbai_tokens.hpp   k_tokens: mission text as fixed-vocabulary token ids of the envs that started a new episode (window_end); k_tap (tap_launch);
 //                     k_gae (bbai_gae).
 //   bbai_demo.hpp     k_demo_spans / k_demo_pack / k_demo_batch / k_demo_jobs / k_demo_pack_list: demonstrations that stay on the device;
@@ -43,6 +45,7 @@ __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase
 #include "../../include/bbai.h"
 #include "../../include/bbai_demo_replay.h"
 #include "../../include/bbai_view_size.h"
+#include "../../include/bbai_view_pixels.h"
 #include "bbai_types.hpp"
 #include "bbai_target.hpp"
 #include "bbai_kernels.hpp"
@@ -294,6 +297,9 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* view_atlas[2];   // the 7x7 view's picture (bbai_set_view_atlas), tile sizes 16 / 32: [VIEWPX_MAX_TILES + 1][ts][ts][3]
     uint8_t* view_lut[2];     // [2][256]
     int view_tiles[2];        // installed tiles (0: none)
+    uint8_t* vpx_atlas[3];    // the V x V view's picture (bbai_set_view_pixels_atlas), tile sizes 8 / 16 / 32: [VIEWPX_MAX_TILES + 1][ts][ts][3]
+    uint8_t* vpx_lut[3];      // [2][256]
+    int vpx_tiles[3];         // installed tiles (0: none)
     bool seeded, live;
     uint8_t* bot_state;   // [n][bot_state_bytes(bot_stack)] the expert's per-env plan (bbai_bot_act; allocated on first use)
     int bot_stack;        // subgoal stack capacity per env (BBAI_BOT_STACK, default 48)
@@ -322,6 +328,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_gridk.hpp"
 #include "bbai_viewn.hpp"
 #include "bbai_viewpx.hpp"
+#include "bbai_viewpxn.hpp"
 #include "bbai_tokens.hpp"
 #include "bbai_demo.hpp"
 #include "bbai_statek.hpp"
@@ -1449,6 +1456,70 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
         HIP_TRY(hipGetLastError());
         return call.leave();
     }();
+    commit_target(e->rt, tp, rc == BBAI_OK);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- the V x V view as pixels, view sizes 3 .. 11 at tile sizes 8 / 16 / 32 (include/bbai_view_pixels.h: k_view_pixels_n) ----
+// Launch shape: viewpxn_items' work items (bbai_viewpxn.hpp), persistent blocks, two per CU.
+template <int V, int TS>
+static void view_pixels_launch_vt(bbai_env* e, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    const int k = grid_ts_index(TS);
+    const ViewPxItems it = viewpxn_items(V, TS, count, cu_count(e) * 2);
+    ViewPxArgs a;
+    a.image = image; a.rows = rows; a.ids = ids; a.count = count; a.out = out;
+    a.atlas = e->vpx_atlas[k]; a.lut = e->vpx_lut[k]; a.n_tiles = e->vpx_tiles[k];
+    a.envs_per_item = it.envs_per_item; a.slices = it.slices; a.items = it.items;
+    hipLaunchKernelGGL((k_view_pixels_n<V, TS>), dim3(persistent_blocks(e, a.items, 2)), dim3(VIEWPXN_BLOCK), 0, s, a);
+}
+template <int V>
+static void view_pixels_launch_v(bbai_env* e, int ts, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    if (ts == 8) view_pixels_launch_vt<V, 8>(e, image, rows, ids, count, out, s);
+    else if (ts == 16) view_pixels_launch_vt<V, 16>(e, image, rows, ids, count, out, s);
+    else view_pixels_launch_vt<V, 32>(e, image, rows, ids, count, out, s);
+}
+static void view_pixels_launch(bbai_env* e, int view_size, int ts, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
+    switch (view_size) {      // (the entry has checked both sizes)
+        case 3: view_pixels_launch_v<3>(e, ts, image, rows, ids, count, out, s); break;
+        case 5: view_pixels_launch_v<5>(e, ts, image, rows, ids, count, out, s); break;
+        case 7: view_pixels_launch_v<7>(e, ts, image, rows, ids, count, out, s); break;
+        case 9: view_pixels_launch_v<9>(e, ts, image, rows, ids, count, out, s); break;
+        default: view_pixels_launch_v<11>(e, ts, image, rows, ids, count, out, s); break;
+    }
+}
+
+extern "C" {
+
+int bbai_set_view_pixels_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_tiles, const uint8_t* lut) {
+    const int k = grid_ts_index(tile_size);
+    if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
+    if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    // (this entry's own atlases: no registered target's frame was drawn with them, so no history to invalidate)
+    return atlas_install(e, __func__, e->vpx_atlas, e->vpx_lut, e->vpx_tiles, k, tile_size, VIEWPX_MAX_TILES, VIEWPX_LUT_BYTES, tiles, n_tiles, lut);
+}
+
+int bbai_render_view_pixels(bbai_env* e, int view_size, int tile_size, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count,
+                            uint8_t* out, void* stream) {
+    const int k = grid_ts_index(tile_size);
+    if (!e) ARG_FAIL("null handle");
+    if (!viewpxn_view_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
+    if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    if (rows < 0 || count < 0 || (!ids && count > rows)) ARG_FAIL("row count out of range");
+    if (count > 0 && rows > 0 && !image) ARG_FAIL("encoded buffer missing");
+    BBAI_TRY(frames_ready(__func__, count, out));
+    if (!e->vpx_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_view_pixels: no atlas for tile size %d (bbai_set_view_pixels_atlas)", tile_size); return BBAI_ERR_STATE; }
+    if (count == 0) return BBAI_OK;
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    // never a render of target envs into their own rows: whole frames, and where they land in the registered buffer its history is gone
+    const TargetPlan tp = plan_foreign(e->rt, (uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size));
+    view_pixels_launch(e, view_size, tile_size, image, rows, ids, count, out, s);
+    HIP_TRY(hipGetLastError());
+    const int rc = call.leave();
     commit_target(e->rt, tp, rc == BBAI_OK);
     return rc;
 }

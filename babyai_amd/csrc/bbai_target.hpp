@@ -85,6 +85,12 @@ inline TargetPlan plan_target(RenderTarget& t, const RenderRequest& q) {
     return p;
 }
 
+// A render that is never one of target envs into their own rows -- whole frames of another picture (bbai_render_view_pixels: any view size,
+// atlases of its own), `bytes` bytes at `out`: a foreign write where it overlaps the registered buffer (tile size 0 is no registration's).
+inline TargetPlan plan_foreign(RenderTarget& t, uintptr_t out, int64_t bytes) {
+    return plan_target(t, RenderRequest{0, out, bytes, 0, 0, true, false});
+}
+
 // Would a tile-size-8 render of the whole batch into `pixels` be a DELTA render?  (bbai_step_render asks before its step kernel, which
 // then finds the dirty cells for it; plans and changes nothing.)
 inline bool whole_batch_delta(const RenderTarget& t, uintptr_t pixels, bool delta) {

@@ -137,11 +137,45 @@ ABI_VIEW = {
 }
 VIEW_SYMBOLS = tuple(ABI_VIEW)
 
+# include/bbai_view_pixels.h, the companion header of the any-view-size pixel entries, the same way (tests/test_view_pixels_host.py holds the rows to it)
+ABI_VIEW_PIXELS = {
+    "bbai_set_view_pixels_atlas": (I32, [P, I32, P, I32, P]),
+    "bbai_render_view_pixels": (I32, [P, I32, I32, P, I64, P, I64, P, P]),
+}
+VIEW_PIXELS_SYMBOLS = tuple(ABI_VIEW_PIXELS)
+
+# k_view_pixels_n's launch shape (babyai_amd/csrc/bbai_viewpxn.hpp: VIEWPXN_BLOCK, VIEWPXN_ITEM_BYTES, VIEWPXN_SLICE_MIN, viewpxn_items;
+# tests/test_view_pixels_host.py holds view_pixels_items to the header's function)
+VIEW_PIXELS_BLOCK = 1024
+VIEW_PIXELS_ITEM_BYTES = 150528
+VIEW_PIXELS_SLICE_MIN = 65536
+VIEW_PIXELS_BLOCKS_PER_CU = 2
+
+
+def view_pixels_items(view_size, tile_size, count, cus):
+    """(envs_per_item, slices, items, blocks) of a bbai_render_view_pixels launch of `count` frames on a device with `cus` compute units:
+    work items of at most VIEW_PIXELS_ITEM_BYTES of frames -- whole frames, as many as the block has lanes for their cells, fewer while that
+    still leaves an item per block; or slices of one frame where a frame is larger, twice as many for frames of VIEW_PIXELS_SLICE_MIN
+    bytes or more while there are fewer items than blocks -- over persistent blocks, VIEW_PIXELS_BLOCKS_PER_CU per compute unit."""
+    want = cus * VIEW_PIXELS_BLOCKS_PER_CU
+    cells = view_size * view_size
+    nbytes = 3 * cells * tile_size * tile_size
+    epi, slices = min(VIEW_PIXELS_ITEM_BYTES // nbytes, VIEW_PIXELS_BLOCK // cells), 1
+    if epi > 1 and count // want < epi:
+        epi = count // want
+    epi = max(epi, 1)
+    if epi == 1:
+        slices = -(-nbytes // VIEW_PIXELS_ITEM_BYTES)
+        if nbytes >= VIEW_PIXELS_SLICE_MIN and count * slices < want:
+            slices *= 2
+    items = count * slices if slices > 1 else -(-count // epi)
+    return epi, slices, items, max(1, min(items, want))
+
 
 def bind(lib):
-    """Give every entry of ABI, ABI_REPLAY and ABI_VIEW that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
+    """Give every entry of ABI, ABI_REPLAY, ABI_VIEW and ABI_VIEW_PIXELS that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
     experiment builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()) + list(ABI_VIEW.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()) + list(ABI_VIEW.items()) + list(ABI_VIEW_PIXELS.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -478,11 +512,24 @@ class BatchedBabyAIEnv(object):
         """What every stepping entry takes behind its actions (include/bbai.h bbai_step): image, direction, reward, reward64, done, auto_reset."""
         return self._out_ptrs + (1 if self.auto_reset else 0,)
 
-    def render_encoding(self, image=None, out=None, tile_size=None):
+    def render_encoding(self, image=None, out=None, tile_size=None, view_size=None):
         """RGBImgPartialObsWrapper(env, tile_size).observation for ANY encoded batch uint8[N,7,7,3] on the device (default: the current
         one) -> uint8[N,7ts,7ts,3], at the batch's tile size or the one given (include/bbai.h bbai_render at 8 -> [N,56,56,3];
         bbai_render_view at 16 / 32, any number of rows, `out` allocated when there is none of that shape).  step() / reset() already
-        return pixels in pixel mode; this is for stored or hand-made encodings."""
+        return pixels in pixel mode; this is for stored or hand-made encodings.
+        view_size=V other than 7: the picture RGBImgPartialObsWrapper(ViewSizeWrapper(env, V), tile_size) draws of a contiguous
+        uint8[k, V, V, 3] encoding on the device (observe_view's frames, stored ones) -> uint8[k, V ts, V ts, 3]
+        (include/bbai_view_pixels.h bbai_render_view_pixels; `out` allocated when none is given; tile_size None = the batch's)."""
+        if view_size is not None and check_view_size(view_size) != 7:
+            v = int(view_size)
+            ts = check_tile_size(self.tile_size if tile_size is None else tile_size)
+            torch = self.torch
+            if image is None or image.dtype != torch.uint8 or image.device != self.device or not image.is_contiguous() or \
+                    image.dim() != 4 or tuple(image.shape[1:]) != (v, v, 3):
+                raise ValueError("image: contiguous uint8[k, %d, %d, 3] on %s" % (v, v, self.device))
+            k = int(image.shape[0])
+            out = self._frames_out(out, (k, v * ts, v * ts, 3))
+            return self._view_pixels_into(image, None, k, v, ts, out)
         image = self.image if image is None else image
         ts = self.tile_size if tile_size is None and self.pixel and not self.full_obs else 8 if tile_size is None else check_tile_size(tile_size)
         if ts != 8:
@@ -498,12 +545,18 @@ class BatchedBabyAIEnv(object):
 
     def _install_atlas(self, picture, ts):
         """The tile atlas of `picture` at tile size ts on the handle, on first use: "view" = the agent's 7x7 view (8: bbai_render's 56x56 atlas;
-        16 / 32: bbai_render_view's), "grid" = the full grid (bbai_render_grid)."""
+        16 / 32: bbai_render_view's), "grid" = the full grid (bbai_render_grid), "view_pixels" = the view at any view size
+        (bbai_render_view_pixels)."""
         if (picture, ts) in self._atlases:
             return
         if picture == "grid":
             tiles, lut = load_atlas(GRID_ATLAS_PATH % ts, "tools/gen_grid_atlas.py")
             _check(self.lib, self.lib.bbai_set_grid_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_grid_atlas")
+        elif picture == "view_pixels":      # (the view's atlas files once more, for bbai_render_view_pixels: the handle keeps them apart)
+            if not all(hasattr(self.lib, name) for name in VIEW_PIXELS_SYMBOLS):
+                raise EngineError("this engine library has no %s (pixels at view_size other than 7)" % " / ".join(VIEW_PIXELS_SYMBOLS))
+            tiles, lut = load_atlas(VIEW_ATLAS_PATH % ts, "tools/gen_atlas.py" + (" --tile-size %d" % ts if ts != 8 else ""))
+            _check(self.lib, self.lib.bbai_set_view_pixels_atlas(self.handle, ts, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_view_pixels_atlas")
         elif ts == 8:
             tiles, lut = load_atlas(ATLAS_PATH, "tools/gen_atlas.py")
             _check(self.lib, self.lib.bbai_set_atlas(self.handle, tiles.ctypes.data, tiles.shape[0], lut.ctypes.data), "bbai_set_atlas")
@@ -528,14 +581,47 @@ class BatchedBabyAIEnv(object):
         _check(self.lib, self.lib.bbai_render(self.handle, image.data_ptr(), out.data_ptr(), self._stream()), "bbai_render")
         return out
 
-    def render_view(self, ids=None, tile_size=None, out=None):
+    def _view_pixels_into(self, image, ids_ptr, k, v, ts, out):
+        """bbai_render_view_pixels: rows `ids_ptr` (None = the first k) of the encoded buffer `image` uint8[rows, v, v, 3] -> out uint8[k, v ts, v ts, 3]."""
+        self._install_atlas("view_pixels", ts)
+        _check(self.lib, self.lib.bbai_render_view_pixels(self.handle, v, ts, image.data_ptr() if image.numel() else None, image.numel() // (3 * v * v),
+                                                           ids_ptr, k, out.data_ptr() if k else None, self._stream()), "bbai_render_view_pixels")
+        return out
+
+    def render_view(self, ids=None, tile_size=None, out=None, view_size=None):
         """The agent's view of envs `ids` (None = every env; else an int sequence or an int64 device tensor, any order, repeats allowed) as
         RGBImgPartialObsWrapper(env, tile_size) draws it, from the current `self.image` -> uint8[k, 7ts, 7ts, 3] on the device,
         asynchronous on the current stream (include/bbai.h bbai_render_view; tile_size None = the batch's).  Available on any batch, also
         an encoded one; the atlas of a tile size is installed on first use.  Writes nothing but `out` (37.6 KB a frame at 16, 150.5 KB
-        at 32); an id outside [0, num_envs) gives an all-zero frame.  tile_size=8 goes through bbai_render (56x56 frames)."""
+        at 32); an id outside [0, num_envs) gives an all-zero frame.  tile_size=8 goes through bbai_render (56x56 frames).
+        view_size=None is exactly that, the 7x7 view from `self.image`, on a view_size batch too.  view_size=V in VIEW_SIZES draws what
+        RGBImgPartialObsWrapper(ViewSizeWrapper(env, V), tile_size) shows -> uint8[k, V ts, V ts, 3] (include/bbai_view_pixels.h
+        bbai_render_view_pixels): for V other than 7 from the current STATE, on any batch -- observe_view(ids, V) into a scratch encoding,
+        or `self.view` as it stands for every env of a view_size=V batch -- and for an explicit 7 from `self.image`, which at tile size
+        8 draws the listed envs in one native launch where the default call gathers rows and pads runs for bbai_render."""
         torch = self.torch
         ts = check_tile_size(self.tile_size if tile_size is None else tile_size)
+        if view_size is not None:
+            v = check_view_size(view_size)
+            k, ids_ptr, ids_t = self._ids(ids)
+            out = self._frames_out(out, (k, v * ts, v * ts, 3))
+            if v == 7:
+                self._hold["render_view"] = ids_t
+                return self._view_pixels_into(self.image, ids_ptr, k, 7, ts, out)
+            if self.view is not None and ids is None and v == self.view_size:
+                self._hold["render_view"] = None
+                return self._view_pixels_into(self.view, None, k, v, ts, out)
+            # the listed envs' V x V encodings from the state, row j = ids[j] (an id outside the batch: a zero row, drawn as the
+            # unseen tile -- so such frames are zeroed by listing their rows as outside the scratch buffer)
+            enc = self.observe_view(ids_t, v)
+            rows_ptr, rows_t = None, None
+            if ids_t is not None:
+                with torch.cuda.device(self.dev_index):
+                    rows_t = torch.arange(k, dtype=torch.int64, device=self.device)
+                    rows_t = torch.where((ids_t < 0) | (ids_t >= self.num_envs), torch.full_like(rows_t, -1), rows_t)
+                rows_ptr = rows_t.data_ptr()
+            self._hold["render_view"] = (ids_t, enc, rows_t)
+            return self._view_pixels_into(enc, rows_ptr, k, v, ts, out)
         k, ids_ptr, ids_t = self._ids(ids)
         out = self._frames_out(out, (k, 7 * ts, 7 * ts, 3))
         if ts != 8:
