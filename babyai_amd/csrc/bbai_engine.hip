@@ -19,6 +19,8 @@
 //                     k_render_dstore, the delta render -- only the 64-byte pieces (or 128-byte lines) whose cells changed since the frame
 //                     the buffer holds are stored.  (render_launch)
 //   bbai_gridk.hpp    k_render_grid<TS>: the full-grid picture; k_full_obs: the fully observable encoding.  (render_grid_launch, full_launch)
+//   bbai_griddelta.hpp k_grid_delta<TS>: the full-grid picture of the whole batch into the registered grid target (include/bbai_grid_target.h), only the
+//                     64-byte pieces that hold a changed cell; k_grid_ids: every tile id behind a whole-frame render into it.  (grid_target_launch)
 //   bbai_viewn.hpp    k_view_obs<V>: the egocentric observation at view sizes 3 .. 11 (ViewSizeWrapper).  (viewn_launch)
 //   bbai_viewpx.hpp   k_view_pixels<TS>: the 7x7 view as pixels at tile sizes 16 / 32 (render_view_launch); k_view_delta<TS> / k_view_ids: a whole
 //                     batch into the target registered at that size, only the 64-byte pieces whose cells changed.  (view_delta_launch)
@@ -46,8 +48,10 @@ __device__ unsigned long long g_bot_prof[32];        // experiment builds: phase
 #include "../../include/bbai_demo_replay.h"
 #include "../../include/bbai_view_size.h"
 #include "../../include/bbai_view_pixels.h"
+#include "../../include/bbai_grid_target.h"
 #include "bbai_types.hpp"
 #include "bbai_target.hpp"
+#include "bbai_gridtarget.hpp"
 #include "bbai_kernels.hpp"
 #include "bbai_gen.hpp"
 #include "bbai_genl.hpp"
@@ -294,6 +298,9 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* grid_lut[3];     // [2][5][256]
     int grid_tiles[3];        // installed tiles (0: none)
     int grid_bpc;             // "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
+    GridTarget gt;            // the registered full-grid target (bbai_set_grid_target; bbai_gridtarget.hpp: the record, and the planner its renders ask)
+    int grid_render_delta;    // 1 (default) = renders into the registered grid target store only the pieces that changed
+    int grid_delta_group;     // "grid_delta_group": k_grid_delta envs per group (0 = by batch size; clamped to what its LDS planes hold: griddelta_shape)
     uint8_t* view_atlas[2];   // the 7x7 view's picture (bbai_set_view_atlas), tile sizes 16 / 32: [VIEWPX_MAX_TILES + 1][ts][ts][3]
     uint8_t* view_lut[2];     // [2][256]
     int view_tiles[2];        // installed tiles (0: none)
@@ -326,6 +333,7 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
 #include "bbai_botk.hpp"
 #include "bbai_render.hpp"
 #include "bbai_gridk.hpp"
+#include "bbai_griddelta.hpp"
 #include "bbai_viewn.hpp"
 #include "bbai_viewpx.hpp"
 #include "bbai_viewpxn.hpp"
@@ -543,6 +551,8 @@ static const Knob KNOBS[] = {
     {"render_piece_bytes", nullptr, &bbai_env::render_piece_bytes, RENDER_PIECE_DEFAULT},   // (64 or 128: bbai_set_option refuses the rest)
     {"render_target_tile_size", nullptr, &bbai_env::rt_next_ts, TILE},                        // (8, 16 or 32: bbai_set_option refuses the rest)
     {"grid_render_bpc", nullptr, &bbai_env::grid_bpc, 0, AT_LEAST, 0},
+    {"grid_render_delta", nullptr, &bbai_env::grid_render_delta, 1, FLAG},                    // (0: whole frames, the shadow kept behind them)
+    {"grid_delta_group", nullptr, &bbai_env::grid_delta_group, 0, AT_LEAST, 0},
     {"step_prio", "BBAI_STEP_PRIO", &bbai_env::step_prio, 1},                          // (never slower, GoTo 131 072 envs -2 %: profiles/r03/step_prio_ab.jsonl)
     {"pregen_group", "BBAI_PREGEN_GROUP", &bbai_env::pregen_group, 32},
     // lane groups of a refill launch at most: 16 384 = two generator waves per SIMD of the part, the other half of every SIMD stays with the step
@@ -1263,6 +1273,7 @@ static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, voi
     // plan, launch, commit (bbai_target.hpp): envs of the target go to the delta render or, while the shadow is not valid, to the full
     // render, which then also writes every tile id
     const TargetPlan tp = plan_target(e->rt, RenderRequest{TILE, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES, env_off, r.nr, false, e->render_delta != 0});
+    (void)grid_target_foreign(e->gt, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES);
     {
     ProfScope prof_(e, 2, r.stream);
     const RenderPlan p = plan_render(e, tp.kind == TargetPlan::FILL ? e->rt.shadow + tp.shadow_off : nullptr);
@@ -1310,6 +1321,7 @@ int bbai_set_grid_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = grid_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    grid_target_atlas_replaced(e->gt, tile_size);
     return atlas_install(e, __func__, e->grid_atlas, e->grid_lut, e->grid_tiles, k, tile_size, GRID_MAX_TILES, GRID_LUT_BYTES, tiles, n_tiles, lut);
 }
 
@@ -1371,6 +1383,7 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
+    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(3 * e->cfg.W * e->cfg.H * tile_size * tile_size));
     if (k == 0) render_grid_launch<8>(e, highlight, ids, count, out, s);
     else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
     else render_grid_launch<32>(e, highlight, ids, count, out, s);
@@ -1449,6 +1462,7 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
     BBAI_TRY(call.rc);
     const TargetPlan tp = plan_target(e->rt, RenderRequest{tile_size, (uintptr_t)out, count * (int64_t)(OBS_BYTES * tile_size * tile_size), 0, count,
                                                            ids || count != rows || rows != e->n, e->render_delta != 0});
+    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(OBS_BYTES * tile_size * tile_size));
     const int rc = [&]() -> int {
         if (tp.kind == TargetPlan::ELSEWHERE) { if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s); else render_view_launch<32>(e, image, rows, ids, count, out, s); }
         else if (k == 0) view_delta_launch<16>(e, tp.kind == TargetPlan::FILL, image, out, s);
@@ -1517,6 +1531,7 @@ int bbai_render_view_pixels(bbai_env* e, int view_size, int tile_size, const uin
     BBAI_TRY(call.rc);
     // never a render of target envs into their own rows: whole frames, and where they land in the registered buffer its history is gone
     const TargetPlan tp = plan_foreign(e->rt, (uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size));
+    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size));
     view_pixels_launch(e, view_size, tile_size, image, rows, ids, count, out, s);
     HIP_TRY(hipGetLastError());
     const int rc = call.leave();
@@ -1581,6 +1596,7 @@ static int observe_listed(bbai_env* e, int view_size, const int64_t* ids, int64_
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
+    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(view_size ? 3 * view_size * view_size : 3 * e->cfg.W * e->cfg.H));
     BBAI_TRY(observe_launch(e, view_size, ids, count, out, s));
     return call.leave();
 }
@@ -1623,6 +1639,119 @@ int bbai_step_view(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
     if (!view_size_ok(view_size)) ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
     if ((uintptr_t)view & 15) ARG_FAIL("view observation buffer not 16-byte aligned");
     return step_observe(e, step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset), view_size, view, stream);
+}
+
+}  // extern "C"
+
+// ---- the registered full-grid target (include/bbai_grid_target.h; bbai_gridtarget.hpp: record and planner; bbai_griddelta.hpp: k_grid_delta) ----
+// The whole batch into the registered buffer.  DELTA: k_grid_delta<TS>, persistent blocks, GRIDDELTA_BPC per CU, over static groups of
+// griddelta_shape's envs (bbai_gridtarget.hpp; option "grid_delta_group").  FILL: the frames whole (k_render_grid<TS>, unchanged) and every
+// tile id behind them (k_grid_ids).
+template <int TS>
+static void grid_target_launch(bbai_env* e, bool fill, hipStream_t s) {
+    const int k = grid_ts_index(TS);
+    const LevelCfg& c = e->cfg;
+    uint8_t* const out = (uint8_t*)e->gt.pixels;
+    if (fill) {
+        render_grid_launch<TS>(e, 0, nullptr, e->n, out, s);
+        hipLaunchKernelGGL(k_grid_ids, dim3(persistent_blocks(e, (e->n * c.W * c.H + 255) / 256, 8)), dim3(256), 0, s, env_list(e, nullptr, e->n, out), e->grid_lut[k], e->gt.shadow);
+        return;
+    }
+    const int64_t want = cu_count(e) * GRIDDELTA_BPC;
+    GridDeltaArgs a;
+    a.g.list = env_list(e, nullptr, e->n, out);
+    a.g.atlas = e->grid_atlas[k]; a.g.lut = e->grid_lut[k]; a.g.n_tiles = e->grid_tiles[k];
+    a.g.highlight = 0; a.g.envs_per_item = 1; a.g.slices = 1; a.g.items = 0;
+    a.g.frame16 = (uint32_t)((int64_t)c.H * TS * c.W * TS * 3 / 16);
+    a.g.frame_magic = (1ull << 32) / a.g.frame16 + 1;
+    a.g.ppr = (uint32_t)(c.W * TS * 3 / GridTile<TS>::P);
+    a.g.ppr_magic = (1ull << 32) / a.g.ppr + 1;
+    a.shadow = e->gt.shadow;
+    a.geom = grid_geom(c.W, c.H, TS);
+    const GridDeltaShape shape = griddelta_shape(e->n, want, c.W, c.H, c.ES, e->grid_delta_group);
+    a.envs_per_group = shape.envs_per_group;
+    a.groups = shape.groups;
+    a.hw_magic = (1ull << 32) / (uint32_t)(c.W * c.H) + 1;
+    a.w_magic = (1ull << 32) / (uint32_t)c.W + 1;
+    a.rd_magic = (1ull << 32) / (uint32_t)(c.H * c.ES / 4) + 1;
+    hipLaunchKernelGGL((k_grid_delta<TS>), dim3(persistent_blocks(e, a.groups, GRIDDELTA_BPC)), dim3(GRIDDELTA_BLOCK), 0, s, a);
+}
+static_assert(GRID_TARGET_ALIGN == GRID_PIECE, "the registered buffer starts on a piece");
+
+// What a render into the target asks of the handle first (`func`: "bbai_<who>").
+static int grid_target_ready(const bbai_env* e, const char* func) {
+    const char* who = func + 5;
+    if (!e->gt.pixels) { snprintf(g_err, sizeof(g_err), "%s: no grid target (bbai_set_grid_target)", who); return BBAI_ERR_STATE; }
+    if (!e->grid_tiles[grid_ts_index(e->gt.ts)]) { snprintf(g_err, sizeof(g_err), "%s: no atlas for tile size %d (bbai_set_grid_atlas)", who, e->gt.ts); return BBAI_ERR_STATE; }
+    if (!e->live) { snprintf(g_err, sizeof(g_err), "%s before reset", who); return BBAI_ERR_STATE; }
+    return BBAI_OK;
+}
+// plan, launch, commit (bbai_gridtarget.hpp) -- behind the step's launches where `io` names a step -- as one call.  Where the registered
+// buffer lies over the 7x7 view's target (bbai_target.hpp) that one's history is gone.
+static int grid_target_call(bbai_env* e, const StepIO* io, void* stream) {
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    const GridPlan gp = plan_grid_target(e->gt, e->grid_render_delta != 0);
+    (void)plan_foreign(e->rt, e->gt.pixels, grid_target_bytes(e->gt));
+    const int rc = [&]() -> int {
+        if (io) BBAI_TRY(step_launch(e, *io, s));
+        const bool fill = gp.kind == GridPlan::FILL;
+        if (e->gt.ts == 8) grid_target_launch<8>(e, fill, s);
+        else if (e->gt.ts == 16) grid_target_launch<16>(e, fill, s);
+        else grid_target_launch<32>(e, fill, s);
+        HIP_TRY(hipGetLastError());
+        return call.leave();
+    }();
+    commit_grid_target(e->gt, gp, rc == BBAI_OK);
+    return rc;
+}
+
+extern "C" {
+
+int bbai_set_grid_target(bbai_env* e, uint8_t* frames, int tile_size) {
+    if (!e) ARG_FAIL("null handle");
+    if (grid_ts_index(tile_size) < 0) ARG_FAIL("tile size must be 8, 16 or 32");
+    if ((uintptr_t)frames % GRID_TARGET_ALIGN) ARG_FAIL("grid target not 64-byte aligned");
+    if (frames && !grid_geom_ok(e->cfg.W, e->cfg.H, tile_size)) ARG_FAIL("grid too narrow for 64-byte pieces");
+    ON_DEVICE(e->device);
+    // the first registration: the shadow (un-registering keeps it)
+    if (frames && !e->gt.shadow) BBAI_TRY(e->own.alloc({{&e->gt.shadow, (size_t)e->n * e->cfg.W * e->cfg.H}}));
+    register_grid_target(e->gt, (uintptr_t)frames, tile_size, e->n, (int64_t)e->cfg.W * e->cfg.H);
+    return BBAI_OK;
+}
+
+int bbai_grid_target_invalidate(bbai_env* e) {
+    if (!e) ARG_FAIL("null handle");
+    invalidate_grid_target(e->gt);
+    return BBAI_OK;
+}
+
+int bbai_grid_target_shadow(bbai_env* e, uint8_t* out, void* stream) {
+    if (!e || !out) ARG_FAIL("null handle or buffer");
+    if (!e->gt.shadow) { snprintf(g_err, sizeof(g_err), "grid_target_shadow before bbai_set_grid_target"); return BBAI_ERR_STATE; }
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    HIP_TRY(hipMemcpyAsync(out, e->gt.shadow, (size_t)e->n * e->cfg.W * e->cfg.H, hipMemcpyDeviceToDevice, s));
+    return call.leave();
+}
+
+int bbai_render_grid_target(bbai_env* e, void* stream) {
+    if (!e) ARG_FAIL("null handle");
+    BBAI_TRY(grid_target_ready(e, __func__));
+    return grid_target_call(e, nullptr, stream);
+}
+
+int bbai_step_grid_target(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t* dirs, float* rewards, double* rewards64,
+                          uint8_t* dones, int auto_reset, void* stream) {
+    if (!e || !actions || !image || !dirs || !rewards || !dones) ARG_FAIL("null handle or buffer");
+    BBAI_TRY(grid_target_ready(e, __func__));
+    BBAI_TRY(step_ready(e, auto_reset, "step"));
+    const StepIO io = step_io(e, actions, image, dirs, rewards, rewards64, dones, auto_reset);
+    return grid_target_call(e, &io, stream);
 }
 
 }  // extern "C"
@@ -2363,6 +2492,7 @@ int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     if (!e || !name || !out) ARG_FAIL("null handle, name or output");
     if (const Knob* k = find_knob(name)) *out = e->*k->field;
     else if (!strcmp(name, "render_delta_valid")) *out = e->rt.valid ? 1 : 0;
+    else if (!strcmp(name, "grid_delta_valid")) *out = e->gt.valid ? 1 : 0;
     else if (!strcmp(name, "gate_fault")) *out = e->host_flags ? (int64_t)e->host_flags[0] : 0;     // sticky; no synchronisation
     else if (!strcmp(name, "profile_step_ticks")) *out = e->prof_step_ticks;
     else if (!strcmp(name, "cplane")) *out = e->cplane ? 1 : 0;

@@ -41,12 +41,17 @@ BB_HD void grid_highlight(const LevelCfg& c, const uint8_t* rec, const Hot& h, u
 }
 
 // The atlas tile of cell (x, y); highlight = 0: the reference's highlight=False (no cell highlighted).
+// The two halves of that rule, each written once: which lut row the agent selects on cell (x, y), and the lut index.
+BB_HD int grid_agent(const Hot& h, int x, int y) { return (x == h.ax && y == h.ay) ? 1 + (h.dir & 3) : 0; }
+BB_HD int grid_lut_index(int lit, int agent, int key) { return (lit * 5 + agent) * 256 + key; }
 BB_HD int grid_tile(const LevelCfg& c, const uint8_t* rec, const Hot& h, const uint8_t* lut, int highlight, const uint32_t* hl, int x, int y) {
     const int key = rec[e_index(c, x, y)];
-    const int agent = (x == h.ax && y == h.ay) ? 1 + (h.dir & 3) : 0;
+    const int agent = grid_agent(h, x, y);
     const int lit = highlight ? (int)((hl[y] >> x) & 1u) : 0;
-    return lut[(lit * 5 + agent) * 256 + key];
+    return lut[grid_lut_index(lit, agent, key)];
 }
+// grid_tile_key: the same from the cell's appearance byte `key` with no cell highlighted (k_grid_delta reads the byte from rows staged in LDS).
+BB_HD int grid_tile_key(int key, const Hot& h, const uint8_t* lut, int x, int y) { return lut[grid_lut_index(0, grid_agent(h, x, y), key)]; }
 
 // All H x W tile ids of one env, row-major (ids[y * W + x]).
 BB_HD void grid_tile_ids(const LevelCfg& c, const uint8_t* rec, const Hot& h, const uint8_t* lut, int highlight, uint8_t* ids) {

@@ -144,6 +144,16 @@ ABI_VIEW_PIXELS = {
 }
 VIEW_PIXELS_SYMBOLS = tuple(ABI_VIEW_PIXELS)
 
+# include/bbai_grid_target.h, the companion header of the registered full-grid target, the same way (tests/test_grid_delta_host.py holds the rows to it)
+ABI_GRID_TARGET = {
+    "bbai_set_grid_target": (I32, [P, P, I32]),
+    "bbai_render_grid_target": (I32, [P, P]),
+    "bbai_step_grid_target": (I32, _STEP + [P]),
+    "bbai_grid_target_invalidate": (I32, [P]),
+    "bbai_grid_target_shadow": (I32, [P, P, P]),
+}
+GRID_TARGET_SYMBOLS = tuple(ABI_GRID_TARGET)
+
 # k_view_pixels_n's launch shape (babyai_amd/csrc/bbai_viewpxn.hpp: VIEWPXN_BLOCK, VIEWPXN_ITEM_BYTES, VIEWPXN_SLICE_MIN, viewpxn_items;
 # tests/test_view_pixels_host.py holds view_pixels_items to the header's function)
 VIEW_PIXELS_BLOCK = 1024
@@ -173,9 +183,9 @@ def view_pixels_items(view_size, tile_size, count, cus):
 
 
 def bind(lib):
-    """Give every entry of ABI, ABI_REPLAY, ABI_VIEW and ABI_VIEW_PIXELS that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
+    """Give every entry of ABI, ABI_REPLAY, ABI_VIEW, ABI_VIEW_PIXELS and ABI_GRID_TARGET that `lib` has its restype and argtypes.  An entry it lacks is passed over (A/B runs against older
     experiment builds, BBAI_ENGINE_LIB: they lack the newer entries; the callers that have a way round ask hasattr(lib, name))."""
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()) + list(ABI_VIEW.items()) + list(ABI_VIEW_PIXELS.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_REPLAY.items()) + list(ABI_VIEW.items()) + list(ABI_VIEW_PIXELS.items()) + list(ABI_GRID_TARGET.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -358,7 +368,10 @@ class BatchedBabyAIEnv(object):
                  obs dict then has no use for 'direction', which the list-of-dicts adapters leave out as the wrappers do.  The 7x7
                  `image`, `direction`, rewards and dones are computed and kept as without it
     tile_size : the pixel wrappers' tile size, 8, 16 or 32 (anything else with pixel=True: ValueError) -- RGBImgObsWrapper's with
-                 full_obs=True, RGBImgPartialObsWrapper's without.  The partial view at 8 is the 56x56 path with its delta render
+                 full_obs=True, RGBImgPartialObsWrapper's without.  With full_obs=True `full` is registered as the handle's full-grid target
+                 (include/bbai_grid_target.h): reset(), step(), load_state(), reseed() and rollout() store only the 64-byte pieces of a frame
+                 that changed -- a turn changes one cell, a move two, only a reset the whole grid (set_option("grid_render_delta", 0) draws
+                 every frame whole again; after writing into `full` yourself call render_invalidate()).  The partial view at 8 is the 56x56 path with its delta render
                  (9.4 KB per env per frame); at 16 / 32 `pixels` is uint8[N,112,112,3] / [N,224,224,3], 37.6 KB / 150.5 KB per env --
                  65 536 envs at 32 are 9.9 GB -- and is registered as the handle's render target of that size: reset(), step(),
                  load_state() and reseed() store only the 64-byte pieces of a frame that changed (include/bbai.h bbai_render_view,
@@ -375,6 +388,7 @@ class BatchedBabyAIEnv(object):
     """
 
     view_size, view = 7, None          # (class defaults: a batch is the 7x7 one until __init__ says otherwise)
+    _grid_target = False               # (... and has no registered full-grid target)
 
     def __init__(self, env_id, num_envs, device="cuda:0", seeds=None, pixel=False, auto_reset=True, validate_actions=False,
                  done_actions=None, full_obs=False, tile_size=8, view_size=7):
@@ -426,6 +440,13 @@ class BatchedBabyAIEnv(object):
                 c, ts = self.cfg, self.tile_size
                 shape = (n, c.H * ts, c.W * ts, 3) if self.pixel else (n, c.W, c.H, 3)
                 self.full = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+                if self.pixel and all(hasattr(self.lib, name) for name in GRID_TARGET_SYMBOLS):
+                    # RGBImgObsWrapper(env, ts): self.full is registered as the handle's full-grid target -- reset(), step(), load_state(), reseed()
+                    # and rollout() store only the 64-byte pieces of a frame that changed (include/bbai_grid_target.h; a library without the
+                    # entries draws every frame whole with bbai_render_grid)
+                    self._install_atlas("grid", ts)
+                    _check(self.lib, self.lib.bbai_set_grid_target(self.handle, self.full.data_ptr(), ts), "bbai_set_grid_target")
+                    self._grid_target = True
             elif self.pixel:
                 # RGBImgPartialObsWrapper(env, ts): frames by bbai_render at 8, by bbai_render_view at 16 / 32.  self.pixels is registered as
                 # the handle's target of that tile size: whole-batch renders into it store only the pieces that changed (include/bbai.h
@@ -704,9 +725,15 @@ class BatchedBabyAIEnv(object):
         allowed) from the current state, asynchronous on the current stream: FullyObsWrapper's uint8[k, W, H, 3] (include/bbai.h
         bbai_observe_full) -- or, in a full_obs pixel batch, RGBImgObsWrapper's uint8[k, H*ts, W*ts, 3] (render_grid(ids, tile_size,
         highlight=False)).  ids = out = None in a full_obs batch refreshes `full`, the observation step() returns (after load_checkpoint
-        or import_state, which do not carry it).  An id outside [0, num_envs) gives an all-zero frame."""
+        or import_state, which do not carry it).  An id outside [0, num_envs) gives an all-zero frame.  In a full_obs pixel batch `full`
+        is the handle's registered full-grid target: refreshing it (ids None, out None or `full`) stores only the 64-byte pieces that
+        changed since the frame it holds (include/bbai_grid_target.h bbai_render_grid_target); every other (ids, out) draws whole frames,
+        and where `out` lies in `full`'s storage the target's history is dropped."""
         if self.full_obs and ids is None and out is None:
             out = self.full
+        if self._grid_target and ids is None and out is self.full:
+            _check(self.lib, self.lib.bbai_render_grid_target(self.handle, self._stream()), "bbai_render_grid_target")
+            return out
         if self.full_obs and self.pixel:
             return self.render_grid(ids, tile_size=self.tile_size, highlight=False, out=out)
         k, ids_ptr, self._hold["observe_full"] = self._ids(ids)
@@ -736,8 +763,19 @@ class BatchedBabyAIEnv(object):
             raise EngineError("%s on a view_size=%d batch: the device expert sees 7x7 and would diverge from the reference's bot" % (what, self.view_size))
 
     def render_invalidate(self):
-        """Call after writing into self.pixels yourself: the next render rewrites every byte (include/bbai.h bbai_render_invalidate)."""
+        """Call after writing into self.pixels -- or, in a full_obs pixel batch, into self.full -- yourself: the next render rewrites every byte
+        (include/bbai.h bbai_render_invalidate, include/bbai_grid_target.h bbai_grid_target_invalidate)."""
         _check(self.lib, self.lib.bbai_render_invalidate(self.handle), "bbai_render_invalidate")
+        if hasattr(self.lib, "bbai_grid_target_invalidate"):
+            _check(self.lib, self.lib.bbai_grid_target_invalidate(self.handle), "bbai_grid_target_invalidate")
+
+    def grid_shadow(self):
+        """The tile ids of the frames the registered full-grid target holds, uint8[N][W*H], row-major y*W + x, in the grid atlas of its tile
+        size (include/bbai_grid_target.h bbai_grid_target_shadow)."""
+        import torch
+        out = torch.empty((self.num_envs, self.cfg.W * self.cfg.H), dtype=torch.uint8, device=self.device)
+        _check(self.lib, self.lib.bbai_grid_target_shadow(self.handle, out.data_ptr(), self._stream()), "bbai_grid_target_shadow")
+        return out
 
     def render_shadow(self):
         """The tile ids of the frame the registered buffer holds, uint8[N][49] (include/bbai.h bbai_render_shadow)."""
@@ -797,6 +835,11 @@ class BatchedBabyAIEnv(object):
             # FullyObsWrapper's step: transition + the full observation of every env as ONE call (include/bbai.h bbai_step_full)
             _check(self.lib, self.lib.bbai_step_full(self.handle, actions.data_ptr(), *self._step_out(), self.full.data_ptr(), self._stream()),
                    "bbai_step_full")
+            return self._obs(rendered=True), self.reward, self.done, {}
+        if self._grid_target and self.kernel_events is None:
+            # RGBImgObsWrapper's step: transition + the changed pieces of every env's frame as ONE call (include/bbai_grid_target.h bbai_step_grid_target)
+            _check(self.lib, self.lib.bbai_step_grid_target(self.handle, actions.data_ptr(), *self._step_out(), self._stream()),
+                   "bbai_step_grid_target")
             return self._obs(rendered=True), self.reward, self.done, {}
         if self.view is not None and self.kernel_events is None:
             # ViewSizeWrapper's step: transition + the V x V view of every env as ONE call (include/bbai_view_size.h bbai_step_view)
