@@ -282,6 +282,54 @@ def test_planner_state_machine(lib):
     assert lib.gt_foreign(base, nbytes) == 0
 
 
+def test_planner_with_extents_and_addresses_beyond_4_gib(lib):
+    """Targets of 2^32 + 2^24 bytes (tests/test_gpu_large_outputs.py's) up to 2^40 bytes, at bases just above 2^32, far above it and below
+    it with the buffer running across it: grid_target_bytes and the overlap test against Python's integers, which do not wrap."""
+    FILL, DELTA = divmod(lib.gt_constants(2), 10)
+    cases = 0
+    for (W, H), ts in [((22, 22), 32), ((22, 22), 8), ((8, 8), 16), ((4, 4), 8), ((25, 25), 32)]:
+        cells, F = W * H, gdu.frame_bytes(W, H, ts)
+        for extent in ((1 << 32) + (1 << 24), (1 << 33) + 12345, 1 << 36, 1 << 40):
+            n = -(-extent // F) + 3
+            size = n * F
+            for base in ((1 << 32) + 64, 0x7F0000000000, 1 << 31, (1 << 32) - 64, 0x300000000000 + (1 << 32)):
+                lib.gt_register(0, 8, 0, 0)
+                lib.gt_register(base, ts, n, cells)
+                assert lib.gt_pixels() == base and lib.gt_bytes() == size and size > (1 << 32) + (1 << 24)
+                end = base + size
+                ranges = [(base - 4096, 4096), (base - 4096, 4097), (end, 4096), (end - 1, 4096), (end - 1, 1), (end - F, F), (base - 64, size + 128),
+                          (base + 100, 0), (end + (1 << 32), 64), (base + size + (1 << 33), 64)]
+                ranges += [(base + off, 64) for off in (1 << 31, 1 << 32, (1 << 32) + (1 << 24) - 64, size - 64)]
+                if base > (1 << 32) + 4096:
+                    ranges.append((base - (1 << 32), 64))
+                for out, nbytes in ranges:
+                    assert lib.gt_render(1, 1) in (FILL, DELTA) and lib.gt_valid() == 1
+                    hit = nbytes > 0 and out < base + size and out + nbytes > base              # Python integers
+                    assert lib.gt_foreign(out, nbytes) == (1 if hit else 0), (W, H, ts, n, hex(base), hex(out), nbytes)
+                    assert lib.gt_valid() == (0 if hit else 1), (W, H, ts, n, hex(base), hex(out), nbytes)
+                    cases += 1
+    lib.gt_register(0, 8, 0, 0)
+    assert cases >= 5 * 4 * 5 * 14
+
+
+def test_launch_shape_at_four_million_envs(lib):
+    """griddelta_shape at 2^22 + 3 envs and beyond 2^32: the groups cover the batch, the last one partial."""
+    from babyai_amd import levels
+    out = np.zeros(2, np.int64)
+    for name in ("BossLevel", "GoToLocal", "GoToObjS4", "KeyCorridorS3R1"):
+        cfg = levels.make_cfg("BabyAI-%s-v0" % name)
+        W, H, ES = int(cfg.W), int(cfg.H), int(cfg.ES)
+        G = lib.gd_group(W, H, ES)
+        for n in ((1 << 22) + 3, (1 << 31) + 5, (1 << 32) + 3, (1 << 40) + 1):
+            for blocks in (512, 608):
+                for asked in (0, 1, 5, 8, 32):
+                    lib.gd_shape(n, blocks, W, H, ES, asked, out.ctypes.data)
+                    g, groups = int(out[0]), int(out[1])
+                    want = min(G, asked) if asked else max(1, min(G, n // blocks))
+                    assert g == want and groups == -(-n // g) and (groups - 1) * g < n <= groups * g, (name, n, blocks, asked, g, groups)
+                    assert n % g != 0 or g == 1, (name, n, g)
+
+
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------
 def prototypes():
     """{entry: [kind of every parameter]} of include/bbai_grid_target.h; kinds "ptr", "i64", "int"."""

@@ -39,6 +39,7 @@ int tg_plan(int ts, unsigned long long out, long long bytes, long long env_off, 
 long long tg_shadow_off() { return g_plan.shadow_off; }
 void tg_commit(int ok) { commit_target(g, g_plan, ok != 0); }
 int tg_query(unsigned long long pixels, int delta) { const RenderTarget& c = g; return whole_batch_delta(c, (uintptr_t)pixels, delta != 0) ? 1 : 0; }
+int tg_foreign(unsigned long long out, long long bytes) { g_plan = plan_foreign(g, (uintptr_t)out, bytes); return g_plan.kind == TargetPlan::ELSEWHERE ? 0 : 1; }
 int tg_valid() { return g.valid ? 1 : 0; }
 long long tg_filled() { return g.filled; }
 void tg_state(unsigned long long* s) {
@@ -60,7 +61,7 @@ def lib(tmp_path_factory):
     U, L, I = ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_int
     for name, res, args in (("tg_new", None, []), ("tg_register", None, [U, I, L]), ("tg_invalidate", None, []), ("tg_atlas_replaced", None, [I]),
                             ("tg_force", None, [I, L]), ("tg_plan", I, [I, U, L, L, L, I, I]), ("tg_shadow_off", L, []), ("tg_commit", None, [I]),
-                            ("tg_query", I, [U, I]), ("tg_valid", I, []), ("tg_filled", L, []), ("tg_state", None, [ctypes.POINTER(U)])):
+                            ("tg_query", I, [U, I]), ("tg_foreign", I, [U, L]), ("tg_valid", I, []), ("tg_filled", L, []), ("tg_state", None, [ctypes.POINTER(U)])):
         getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     return lib
 
@@ -252,6 +253,104 @@ def test_the_query_changes_nothing_and_agrees_with_the_planner(lib):          # 
             assert got == (1 if target == 8 and aligned and valid and delta and off == 0 else 0)
             asked += got
     assert asked == 1
+
+
+# ---- A2. extents and addresses beyond 2^32 ------------------------------------------------------------------------------------------------
+# Targets of 2^32 + 2^24 bytes (the GPU cases of tests/test_gpu_large_outputs.py) up to 2^40 bytes (sizes no GPU test can afford), at
+# bases just above 2^32, far above it, and below it with the buffer running across it.  The model is Python's integers, which do not wrap.
+BIG_EXTENTS = ((1 << 32) + (1 << 24), (1 << 33) + 12345, 1 << 36, 1 << 40)
+BIG_BASES = ((1 << 32) + 128, BASE, 1 << 31, (1 << 32) - 128, 0x0000300000000000 + (1 << 32))
+
+
+def big_targets():
+    for ts in (8, 16, 32):
+        for extent in BIG_EXTENTS:
+            n = -(-extent // frame(ts))
+            n += (-n) % 8 + 8 * (ts != 8)              # whole units of 8 envs; at 16 / 32 one more unit
+            for base in BIG_BASES:
+                yield ts, n, base
+
+
+def foreign_ranges(base, size, F):
+    """(out, bytes) around and inside [base, base + size): just outside and one byte inside at both ends, at and around the offsets 2^31 and
+    2^32, where those offsets' low 32 bits land, the last frame, everything."""
+    end = base + size
+    yield base - 4096, 4096
+    yield base - 4096, 4097
+    yield end, 4096
+    yield end - 1, 4096
+    yield end - 1, 1
+    yield end - F, F
+    yield base - 64, size + 128
+    yield base + 100, 0
+    for off in (1 << 31, 1 << 32, (1 << 32) + (1 << 24) - 64, size - 64):
+        if 0 <= off < size:
+            yield base + off, 64
+    yield end + (1 << 32), 64                          # outside, at an address whose low 32 bits lie inside
+    yield (base - (1 << 32) if base > (1 << 32) + 4096 else base + size + (1 << 33)), 64
+
+
+def test_foreign_writes_into_targets_beyond_4_gib(lib):
+    cases = 0
+    for ts, n, base in big_targets():
+        F = frame(ts)
+        size = n * F
+        assert size > (1 << 32) + (1 << 24) - F
+        for out, nbytes in foreign_ranges(base, size, F):
+            for entry in ("foreign", "another tile size", "listed rows"):
+                lib.tg_new()
+                lib.tg_register(base, ts, n)
+                lib.tg_force(1, 0)
+                before = state(lib)
+                assert before[0] == base and before[6] == n
+                if entry == "foreign":
+                    kind = lib.tg_foreign(out, nbytes)
+                elif entry == "another tile size":
+                    kind = lib.tg_plan({8: 16, 16: 32, 32: 8}[ts], out, nbytes, 0, 1, 1, 1)
+                else:
+                    kind = lib.tg_plan(ts, out, nbytes, 0, 1, 1, 1)
+                hit = out < base + size and out + nbytes > base                        # Python integers
+                if entry == "listed rows" and ts == 8 and out == base:
+                    continue                                                            # (at 8 a range from env 0 on is on target)
+                assert kind == ELSEWHERE, (ts, n, hex(base), hex(out), nbytes, entry)
+                assert lib.tg_valid() == (0 if hit else 1), (ts, n, hex(base), hex(out), nbytes, entry, hit)
+                if not hit:
+                    assert state(lib) == before
+                cases += 1
+    assert cases > 3 * len(BIG_EXTENTS) * len(BIG_BASES) * 11 * 3 - 100
+
+
+def test_on_target_renders_of_targets_beyond_4_gib(lib):
+    for ts, n, base in big_targets():
+        F = frame(ts)
+        # the whole batch at the registered pointer: FILL, then DELTA
+        setup_big = lambda valid: (lib.tg_new(), lib.tg_register(base, ts, n), lib.tg_force(valid, 0))
+        setup_big(0)
+        assert lib.tg_plan(ts, base, n * F, 0, n, 0, 1) == FILL and lib.tg_shadow_off() == 0
+        lib.tg_commit(1)
+        assert lib.tg_valid() == 1 and lib.tg_filled() == n
+        assert lib.tg_plan(ts, base, n * F, 0, n, 0, 1) == DELTA
+        if ts != 8:
+            continue
+        assert lib.tg_query(base, 1) == 1 and lib.tg_query(base + (1 << 32), 1) == 0
+        # bbai_step_render's halves at 8: a range that starts on a unit of envs, its rows beyond 2^31 / 2^32 bytes into the buffer
+        for env_off in sorted({8 * (((1 << 31) // F + 8) // 8), 8 * (((1 << 32) // F + 8) // 8), n - 8, 8 * ((n // 2) // 8)}):
+            nr = n - env_off
+            assert env_off % 8 == 0 and 0 < env_off < n
+            setup_big(1)
+            assert lib.tg_plan(8, base + env_off * F, nr * F, env_off, nr, 0, 1) == DELTA, (n, hex(base), env_off)
+            assert lib.tg_shadow_off() == env_off * 49 and lib.tg_valid() == 1
+            # the same rows 2^32 bytes further on or back, or one env off: not those envs' rows -- a foreign write where it lands in the buffer
+            for wrong in (base + env_off * F + (1 << 32), base + env_off * F - (1 << 32), base + (env_off + 1) * F):
+                setup_big(1)
+                hit = wrong < base + n * F and wrong + nr * F > base
+                assert lib.tg_plan(8, wrong, nr * F, env_off, nr, 0, 1) == ELSEWHERE and lib.tg_valid() == (0 if hit else 1), (n, hex(base), env_off, hex(wrong))
+            # fills in order across the offset make the shadow valid
+            setup_big(0)
+            for off, cnt in ((0, env_off), (env_off, nr)):
+                assert lib.tg_plan(8, base + off * F, cnt * F, off, cnt, 0, 1) == FILL and lib.tg_shadow_off() == off * 49
+                lib.tg_commit(1)
+            assert lib.tg_valid() == 1 and lib.tg_filled() == n
 
 
 # ---- B. the GPU tests' call sequences -------------------------------------------------------------------------------------------------

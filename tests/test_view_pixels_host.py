@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import large_outputs_util as lou
 import view_pixels_util as vpu
 from oracle import levels as olevels
 
@@ -215,7 +216,8 @@ def test_launch_shape_is_the_headers(arith, V, ts):
     out = np.zeros(3, np.int64)
     for cus in (1, 8, 256, 304):
         blocks = cus * engine.VIEW_PIXELS_BLOCKS_PER_CU
-        for count in (1, 2, 3, 7, 100, blocks - 1, blocks, blocks + 1, 3 * blocks + 1, 20000, 1 << 20, 1 << 33):
+        # (... (1 << 22) + 3 and the frame count that crosses 4 GiB at this size: the cases of tests/test_gpu_large_outputs.py)
+        for count in (1, 2, 3, 7, 100, blocks - 1, blocks, blocks + 1, 3 * blocks + 1, 20000, 1 << 20, (1 << 22) + 3, lou.count_for(g["bytes"]), 1 << 33):
             arith.vp_items(V, ts, count, blocks, out.ctypes.data)
             epi, slices, items, nb = engine.view_pixels_items(V, ts, count, cus)
             assert (epi, slices, items) == tuple(int(x) for x in out), (V, ts, cus, count)
