@@ -39,6 +39,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #if defined(BBAI_BOT_PROF)
@@ -276,8 +277,8 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     int render_queue_blocks;   // their total number (0 = by render_queue_bpc)
     int render_pace;      // (experiment) 1/16 ns of wall clock per render ticket (then with two counters), 0 (default) = as fast as the
                           // one counter serves them
-    // delta rendering (bbai_set_render_target): the registered buffer, and the atlas tile ids of the frame it holds
-    RenderTarget rt;      // (bbai_target.hpp: the record, and the planner every render asks)
+    // delta rendering: the registered 7x7-view buffer (bbai_set_render_target) and full-grid buffer (bbai_set_grid_target), each with the atlas tile ids of the frame it holds
+    Targets targets;      // (bbai_target.hpp: the records, and the planner every frame-writing call asks -- frame_call)
     int rt_next_ts;       // "render_target_tile_size": the tile size the NEXT bbai_set_render_target registers (8, default)
     int render_delta;     // 1 (default) = renders into the registered buffer store only changed lines
     int render_delta_sched;    // k_render_delta: 0 (default) = interleaved groups per block, 1 = contiguous ranges, 2 as 0; the store-only render of pieces: 0 / 1 = the ticket queue (k_render_dstore_lw), 2 = the static split (k_render_dstore)
@@ -298,7 +299,6 @@ struct bbai_env {       // (the int knobs' option names, BBAI_* variables, defau
     uint8_t* grid_lut[3];     // [2][5][256]
     int grid_tiles[3];        // installed tiles (0: none)
     int grid_bpc;             // "grid_render_bpc": k_render_grid blocks per CU (0 = by tile size)
-    GridTarget gt;            // the registered full-grid target (bbai_set_grid_target; bbai_gridtarget.hpp: the record, and the planner its renders ask)
     int grid_render_delta;    // 1 (default) = renders into the registered grid target store only the pieces that changed
     int grid_delta_group;     // "grid_delta_group": k_grid_delta envs per group (0 = by batch size; clamped to what its LDS planes hold: griddelta_shape)
     uint8_t* view_atlas[2];   // the 7x7 view's picture (bbai_set_view_atlas), tile sizes 16 / 32: [VIEWPX_MAX_TILES + 1][ts][ts][3]
@@ -989,7 +989,7 @@ static int step_kernel(bbai_env* e, const StepPlan& p, const StepIO& io, hipStre
     a.rewards = io.rewards; a.rewards64 = io.rewards64; a.dones = io.dones; a.auto_reset = io.auto_reset; a.reset_list = e->reset_list; a.reset_slot = e->reset_slot; a.counters = p.counter;
     a.prio = e->step_prio; a.vplane = e->vplane; a.fcache = e->fcache; a.lsm_arr = e->lsm; a.enum_done = io.enum_done; a.hold = io.hold; a.fuse = p.fa; a.block0 = block0; a.cplane = e->cplane;
     a.tap = p.tap; a.ticks = ticks;
-    a.dshadow = p.dirty && ticks == 1 ? e->rt.shadow : nullptr; a.dmask = e->rt.dmask; a.lut = e->lut;
+    a.dshadow = p.dirty && ticks == 1 ? e->targets.view.shadow : nullptr; a.dmask = e->targets.view.dmask; a.lut = e->lut;
 #define STEP_LAUNCH(VV, FF, CC) do { if (ticks > 1) hipLaunchKernelGGL((k_step_ticks<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); \
                                      else hipLaunchKernelGGL((k_step<VV, FF, CC>), dim3((unsigned)nblocks), dim3(STEP_BLOCK), 0, ks, a); } while (0)
     if (e->inplace && e->cplane) STEP_LAUNCH(false, 3, true);
@@ -1099,7 +1099,7 @@ int bbai_set_atlas(bbai_env* e, const uint8_t* tiles, int n_tiles, const uint8_t
     HIP_TRY(hipMemcpy(e->atlas, tiles, (size_t)n_tiles * TILE_BYTES, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->lut, lut, 512, hipMemcpyHostToDevice));
     e->n_tiles = n_tiles;
-    target_atlas_replaced(e->rt, TILE);      // (a 16 / 32 target: bbai_set_view_atlas)
+    target_atlas_replaced(e->targets.view, TILE);      // (a 16 / 32 target: bbai_set_view_atlas)
     return BBAI_OK;
 }
 
@@ -1107,30 +1107,57 @@ int bbai_set_render_target(bbai_env* e, uint8_t* pixels) {
     if (!e) ARG_FAIL("null handle");
     ON_DEVICE(e->device);
     // the first registration: the shadow and the dirty masks, both or neither (un-registering keeps them)
-    if (pixels && !e->rt.shadow) BBAI_TRY(e->own.alloc({{&e->rt.shadow, (size_t)e->n * CELLS}, {&e->rt.dmask, (size_t)e->n * sizeof(uint64_t)}}));
+    if (pixels && !e->targets.view.shadow) BBAI_TRY(e->own.alloc({{&e->targets.view.shadow, (size_t)e->n * CELLS}, {&e->targets.view.dmask, (size_t)e->n * sizeof(uint64_t)}}));
     // option "render_target_tile_size": the frames are uint8[n][7 ts][7 ts][3], the shadow holds ids of that size's atlas
-    register_target(e->rt, (uintptr_t)pixels, e->rt_next_ts, e->n);
+    register_target(e->targets.view, (uintptr_t)pixels, e->rt_next_ts, e->n, view_frame_bytes(e->rt_next_ts));
     return BBAI_OK;
 }
 
 int bbai_render_invalidate(bbai_env* e) {
     if (!e) ARG_FAIL("null handle");
-    invalidate_target(e->rt);
+    invalidate_target(e->targets.view);
     return BBAI_OK;
 }
 
 int bbai_render_shadow(bbai_env* e, uint8_t* out, void* stream) {
     if (!e || !out) ARG_FAIL("null handle or buffer");
-    if (!e->rt.shadow) { snprintf(g_err, sizeof(g_err), "render_shadow before bbai_set_render_target"); return BBAI_ERR_STATE; }
+    if (!e->targets.view.shadow) { snprintf(g_err, sizeof(g_err), "render_shadow before bbai_set_render_target"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    HIP_TRY(hipMemcpyAsync(out, e->rt.shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out, e->targets.view.shadow, (size_t)e->n * CELLS, hipMemcpyDeviceToDevice, s));
     return call.leave();
 }
 
 }  // extern "C"
+
+// One call that writes frames or observations into a caller's buffer, the only way such a call is made: on the handle's device and inside
+// a CallScope, the write is announced to the registered targets (bbai_target.hpp: `write` is a RenderRequest, a GridRenderRequest or a
+// WriteRequest), `launch(plan, stream)` enqueues the work and returns a BBAI_* code, and the targets' state moves to what the plan promised
+// only when the launches and the call's exit succeeded.
+template <class Write, class Launch>
+static int frame_call(bbai_env* e, void* stream, const Write& write, Launch launch) {
+    ON_DEVICE(e->device);
+    hipStream_t s = (hipStream_t)stream;
+    CallScope call(e, s);
+    BBAI_TRY(call.rc);
+    const TargetPlan tp = plan_target(e->targets, write);
+    const int rc = [&]() -> int {
+        BBAI_TRY(launch(tp, s));
+        HIP_TRY(hipGetLastError());
+        return call.leave();
+    }();
+    commit_target(e->targets, tp, rc == BBAI_OK);
+    return rc;
+}
+
+// A run-time tile size (8, 16 or 32) or view size (3 .. 11, odd) as a compile-time one: f(std::integral_constant).  (The entries have checked both.)
+template <int N> using Size = std::integral_constant<int, N>;
+template <class F> static void with_tile_size(int ts, F f) { if (ts == 8) f(Size<8>()); else if (ts == 16) f(Size<16>()); else f(Size<32>()); }
+template <class F> static void with_view_size(int v, F f) {
+    if (v == 3) f(Size<3>()); else if (v == 5) f(Size<5>()); else if (v == 7) f(Size<7>()); else if (v == 9) f(Size<9>()); else f(Size<11>());
+}
 
 // Time-paced tickets (option "render_pace", off by default).  k_render_q at the rate of ONE ticket counter (11.4 ns per 8-env ticket
 // = 6.6 TB/s) beats every unpaced shape because the counter PACES the chip's stores; a wall-clock gate over two counters can set the
@@ -1184,7 +1211,7 @@ static void launch_delta_t(const bbai_env* e, const RenderRange& r, unsigned blo
 }
 template <int P>
 static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned blocks, uint8_t* sh) {
-    hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles);
+    hipLaunchKernelGGL((k_render_dstore<32, 512, P>), dim3(blocks), dim3(512), 0, r.stream, r.nr, r.pixels, sh, e->targets.view.dmask + r.env_off, e->atlas, e->n_tiles);
 }
 // The store-only render of 64-byte pieces (the default): k_render_dstore_lw -- groups from one ticket counter, two per ticket, ONE
 // 576-thread block per CU (no more blocks than tickets: every block opens with one).  1 048 576 BossLevel envs, bench.py's actions,
@@ -1193,14 +1220,14 @@ static void launch_dstore_p(const bbai_env* e, const RenderRange& r, unsigned bl
 // fewer blocks share the one in-order stream of groups, the more compact the window the chip's stores advance through.
 static void launch_dstore_lw(const bbai_env* e, const RenderRange& r, int64_t groups, uint8_t* sh) {
     const unsigned blocks = persistent_blocks(e, (groups + DSTORE_LW_K - 1) / DSTORE_LW_K, e->render_delta_bpc > 0 ? e->render_delta_bpc : 1);
-    hipLaunchKernelGGL((k_render_dstore_lw<64>), dim3(blocks), dim3(DSTORE_LW_T), 0, r.stream, r.nr, r.pixels, sh, e->rt.dmask + r.env_off, e->atlas, e->n_tiles, e->render_tickets);
+    hipLaunchKernelGGL((k_render_dstore_lw<64>), dim3(blocks), dim3(DSTORE_LW_T), 0, r.stream, r.nr, r.pixels, sh, e->targets.view.dmask + r.env_off, e->atlas, e->n_tiles, e->render_tickets);
 }
 static void launch_render_delta(const bbai_env* e, const RenderRange& r, bool from_step) {
     const int T = e->render_delta_tpb == 1024 && !from_step ? 1024 : 512;
     constexpr int G = 32;
     const int64_t groups = (r.nr + G - 1) / G;
     const unsigned blocks = persistent_blocks(e, groups, e->render_delta_bpc > 0 ? e->render_delta_bpc : (T == 512 ? 3 : 1));
-    uint8_t* sh = e->rt.shadow + r.env_off * CELLS;
+    uint8_t* sh = e->targets.view.shadow + r.env_off * CELLS;
     if (from_step && e->render_piece_bytes != 128 && e->render_delta_sched != 2) launch_dstore_lw(e, r, groups, sh);
     else if (from_step) { if (e->render_piece_bytes == 128) launch_dstore_p<128>(e, r, blocks, sh); else launch_dstore_p<64>(e, r, blocks, sh); }
     else if (T == 512) launch_delta_t<512>(e, r, blocks, sh);
@@ -1267,23 +1294,16 @@ static void launch_render_oneshot(const bbai_env* e, const RenderRange& r, uint8
 static int render_launch(bbai_env* e, const uint8_t* input, uint8_t* pixels, void* stream, int64_t n_render = -1 /* envs input / pixels hold (default: the batch); the shape follows the BATCH size */,
                          int64_t env_off = 0 /* first env of the range (bbai_step_render's split halves) */,
                          bool from_step = false /* the step in front found the dirty cells (step_dirty): store them (k_render_dstore) */) {
-    CallScope call(e, (hipStream_t)stream);
-    BBAI_TRY(call.rc);
     const RenderRange r = {input, pixels, n_render < 0 ? e->n : n_render, env_off, (hipStream_t)stream};
-    // plan, launch, commit (bbai_target.hpp): envs of the target go to the delta render or, while the shadow is not valid, to the full
-    // render, which then also writes every tile id
-    const TargetPlan tp = plan_target(e->rt, RenderRequest{TILE, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES, env_off, r.nr, false, e->render_delta != 0});
-    (void)grid_target_foreign(e->gt, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES);
-    {
-    ProfScope prof_(e, 2, r.stream);
-    const RenderPlan p = plan_render(e, tp.kind == TargetPlan::FILL ? e->rt.shadow + tp.shadow_off : nullptr);
-    if (tp.kind == TargetPlan::DELTA) launch_render_delta(e, r, from_step);
-    else if (p.queue > 0) launch_render_queue(e, r, p);
-    else launch_render_oneshot(e, r, p.shadow);
-    }
-    const int rc = [&]() -> int { HIP_TRY(hipGetLastError()); return call.leave(); }();
-    commit_target(e->rt, tp, rc == BBAI_OK);
-    return rc;
+    // envs of the target go to the delta render or, while the shadow is not valid, to the full render, which then also writes every tile id
+    return frame_call(e, stream, RenderRequest{TILE, (uintptr_t)pixels, r.nr * (int64_t)PIX_BYTES, env_off, r.nr, false, e->render_delta != 0}, [&](const TargetPlan& tp, hipStream_t) {
+        ProfScope prof_(e, 2, r.stream);
+        const RenderPlan p = plan_render(e, tp.kind == TargetPlan::FILL ? e->targets.view.shadow + tp.shadow_off : nullptr);
+        if (tp.kind == TargetPlan::DELTA) launch_render_delta(e, r, from_step);
+        else if (p.queue > 0) launch_render_queue(e, r, p);
+        else launch_render_oneshot(e, r, p.shadow);
+        return BBAI_OK;
+    });
 }
 
 extern "C" {
@@ -1291,7 +1311,6 @@ extern "C" {
 int bbai_render(bbai_env* e, const uint8_t* image, uint8_t* pixels, void* stream) {
     if (!e || !image || !pixels) ARG_FAIL("null handle or buffer");
     if (e->n_tiles <= 0) { snprintf(g_err, sizeof(g_err), "render before set_atlas"); return BBAI_ERR_STATE; }
-    ON_DEVICE(e->device);
     return render_launch(e, image, pixels, stream);
 }
 
@@ -1321,7 +1340,7 @@ int bbai_set_grid_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = grid_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
-    grid_target_atlas_replaced(e->gt, tile_size);
+    target_atlas_replaced(e->targets.grid, tile_size);
     return atlas_install(e, __func__, e->grid_atlas, e->grid_lut, e->grid_tiles, k, tile_size, GRID_MAX_TILES, GRID_LUT_BYTES, tiles, n_tiles, lut);
 }
 
@@ -1379,16 +1398,10 @@ int bbai_render_grid(bbai_env* e, int tile_size, int highlight, const int64_t* i
     if (k < 0) ARG_FAIL("tile size must be 8, 16 or 32");
     BBAI_TRY(listed_ready(e, __func__, ids, count, out, e->grid_tiles[k] ? 0 : tile_size));
     if (count == 0) return BBAI_OK;
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(3 * e->cfg.W * e->cfg.H * tile_size * tile_size));
-    if (k == 0) render_grid_launch<8>(e, highlight, ids, count, out, s);
-    else if (k == 1) render_grid_launch<16>(e, highlight, ids, count, out, s);
-    else render_grid_launch<32>(e, highlight, ids, count, out, s);
-    HIP_TRY(hipGetLastError());
-    return call.leave();
+    return frame_call(e, stream, WriteRequest{(uintptr_t)out, count * grid_frame_bytes(e->cfg.W * e->cfg.H, tile_size)}, [&](const TargetPlan&, hipStream_t s) {
+        with_tile_size(tile_size, [&](auto ts) { render_grid_launch<ts()>(e, highlight, ids, count, out, s); });
+        return BBAI_OK;
+    });
 }
 
 }  // extern "C"
@@ -1402,7 +1415,7 @@ int bbai_set_view_atlas(bbai_env* e, int tile_size, const uint8_t* tiles, int n_
     const int k = view_ts_index(tile_size);
     if (!e || !tiles || !lut) ARG_FAIL("null handle or pointer");
     if (k < 0) ARG_FAIL("tile size must be 16 or 32 (8: bbai_set_atlas)");
-    target_atlas_replaced(e->rt, tile_size);
+    target_atlas_replaced(e->targets.view, tile_size);
     return atlas_install(e, __func__, e->view_atlas, e->view_lut, e->view_tiles, k, tile_size, VIEWPX_MAX_TILES, VIEWPX_LUT_BYTES, tiles, n_tiles, lut);
 }
 
@@ -1432,11 +1445,11 @@ static void view_delta_launch(bbai_env* e, bool fill, const uint8_t* image, uint
     const int k = view_ts_index(TS);
     if (fill) {
         render_view_launch<TS>(e, image, e->n, nullptr, e->n, out, s);
-        hipLaunchKernelGGL(k_view_ids, dim3(persistent_blocks(e, (e->n * CELLS + 255) / 256, 8)), dim3(256), 0, s, image, e->n, e->view_lut[k], e->rt.shadow);
+        hipLaunchKernelGGL(k_view_ids, dim3(persistent_blocks(e, (e->n * CELLS + 255) / 256, 8)), dim3(256), 0, s, image, e->n, e->view_lut[k], e->targets.view.shadow);
         return;
     }
     ViewDeltaArgs a;
-    a.image = image; a.n = e->n; a.out = out; a.shadow = e->rt.shadow;
+    a.image = image; a.n = e->n; a.out = out; a.shadow = e->targets.view.shadow;
     a.atlas = e->view_atlas[k]; a.lut = e->view_lut[k]; a.n_tiles = e->view_tiles[k];
     const int64_t groups = (e->n + ViewDelta<TS>::G - 1) / ViewDelta<TS>::G;
     hipLaunchKernelGGL((k_view_delta<TS>), dim3(persistent_blocks(e, groups, 2)), dim3(VIEWDELTA_BLOCK), 0, s, a);
@@ -1453,25 +1466,16 @@ int bbai_render_view(bbai_env* e, int tile_size, const uint8_t* image, int64_t r
     BBAI_TRY(frames_ready(__func__, count, out));
     if (!e->view_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_view: no atlas for tile size %d (bbai_set_view_atlas)", tile_size); return BBAI_ERR_STATE; }
     if (count == 0) return BBAI_OK;
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    // plan, launch, commit (bbai_target.hpp): the whole batch into the target registered at this tile size is a delta render (or, while
-    // the shadow is not valid, the whole frames with every tile id behind them); anything else -- ids given, a partial count, another
-    // tile size, a misaligned target, "render_delta" 0 -- draws whole frames, and invalidates where it writes into the registered buffer
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    const TargetPlan tp = plan_target(e->rt, RenderRequest{tile_size, (uintptr_t)out, count * (int64_t)(OBS_BYTES * tile_size * tile_size), 0, count,
-                                                           ids || count != rows || rows != e->n, e->render_delta != 0});
-    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(OBS_BYTES * tile_size * tile_size));
-    const int rc = [&]() -> int {
+    // the whole batch into the target registered at this tile size is a delta render (or, while the shadow is not valid, the whole frames
+    // with every tile id behind them); anything else -- ids given, a partial count, another tile size, a misaligned target,
+    // "render_delta" 0 -- draws whole frames, and invalidates where it writes into a registered buffer
+    const RenderRequest q = {tile_size, (uintptr_t)out, count * view_frame_bytes(tile_size), 0, count, ids || count != rows || rows != e->n, e->render_delta != 0};
+    return frame_call(e, stream, q, [&](const TargetPlan& tp, hipStream_t s) {
         if (tp.kind == TargetPlan::ELSEWHERE) { if (k == 0) render_view_launch<16>(e, image, rows, ids, count, out, s); else render_view_launch<32>(e, image, rows, ids, count, out, s); }
         else if (k == 0) view_delta_launch<16>(e, tp.kind == TargetPlan::FILL, image, out, s);
         else view_delta_launch<32>(e, tp.kind == TargetPlan::FILL, image, out, s);
-        HIP_TRY(hipGetLastError());
-        return call.leave();
-    }();
-    commit_target(e->rt, tp, rc == BBAI_OK);
-    return rc;
+        return BBAI_OK;
+    });
 }
 
 }  // extern "C"
@@ -1487,21 +1491,6 @@ static void view_pixels_launch_vt(bbai_env* e, const uint8_t* image, int64_t row
     a.atlas = e->vpx_atlas[k]; a.lut = e->vpx_lut[k]; a.n_tiles = e->vpx_tiles[k];
     a.envs_per_item = it.envs_per_item; a.slices = it.slices; a.items = it.items;
     hipLaunchKernelGGL((k_view_pixels_n<V, TS>), dim3(persistent_blocks(e, a.items, 2)), dim3(VIEWPXN_BLOCK), 0, s, a);
-}
-template <int V>
-static void view_pixels_launch_v(bbai_env* e, int ts, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
-    if (ts == 8) view_pixels_launch_vt<V, 8>(e, image, rows, ids, count, out, s);
-    else if (ts == 16) view_pixels_launch_vt<V, 16>(e, image, rows, ids, count, out, s);
-    else view_pixels_launch_vt<V, 32>(e, image, rows, ids, count, out, s);
-}
-static void view_pixels_launch(bbai_env* e, int view_size, int ts, const uint8_t* image, int64_t rows, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
-    switch (view_size) {      // (the entry has checked both sizes)
-        case 3: view_pixels_launch_v<3>(e, ts, image, rows, ids, count, out, s); break;
-        case 5: view_pixels_launch_v<5>(e, ts, image, rows, ids, count, out, s); break;
-        case 7: view_pixels_launch_v<7>(e, ts, image, rows, ids, count, out, s); break;
-        case 9: view_pixels_launch_v<9>(e, ts, image, rows, ids, count, out, s); break;
-        default: view_pixels_launch_v<11>(e, ts, image, rows, ids, count, out, s); break;
-    }
 }
 
 extern "C" {
@@ -1525,18 +1514,11 @@ int bbai_render_view_pixels(bbai_env* e, int view_size, int tile_size, const uin
     BBAI_TRY(frames_ready(__func__, count, out));
     if (!e->vpx_tiles[k]) { snprintf(g_err, sizeof(g_err), "render_view_pixels: no atlas for tile size %d (bbai_set_view_pixels_atlas)", tile_size); return BBAI_ERR_STATE; }
     if (count == 0) return BBAI_OK;
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    // never a render of target envs into their own rows: whole frames, and where they land in the registered buffer its history is gone
-    const TargetPlan tp = plan_foreign(e->rt, (uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size));
-    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size));
-    view_pixels_launch(e, view_size, tile_size, image, rows, ids, count, out, s);
-    HIP_TRY(hipGetLastError());
-    const int rc = call.leave();
-    commit_target(e->rt, tp, rc == BBAI_OK);
-    return rc;
+    // never a render of target envs into their own rows: whole frames, and where they land in a registered buffer its history is gone
+    return frame_call(e, stream, WriteRequest{(uintptr_t)out, count * (int64_t)(3 * view_size * view_size * tile_size * tile_size)}, [&](const TargetPlan&, hipStream_t s) {
+        with_view_size(view_size, [&](auto v) { with_tile_size(tile_size, [&](auto ts) { view_pixels_launch_vt<v(), ts()>(e, image, rows, ids, count, out, s); }); });
+        return BBAI_OK;
+    });
 }
 
 }  // extern "C"
@@ -1560,7 +1542,6 @@ static int full_launch(bbai_env* e, const int64_t* ids, int64_t count, uint8_t* 
     a.w_magic = (1ull << 32) / (uint32_t)c.W + 1;
     a.rd_magic = (1ull << 32) / (uint32_t)(c.H * c.ES / 4) + 1;
     hipLaunchKernelGGL(k_full_obs, dim3(persistent_blocks(e, a.items, FULL_BPC)), dim3(FULL_BLOCK), 0, s, a);
-    HIP_TRY(hipGetLastError());
     return BBAI_OK;
 }
 
@@ -1572,43 +1553,28 @@ static void viewn_launch_v(bbai_env* e, const int64_t* ids, int64_t count, uint8
     a.items = (count + ViewN<V>::EPI - 1) / ViewN<V>::EPI;
     hipLaunchKernelGGL((k_view_obs<V>), dim3(persistent_blocks(e, a.items, VIEWN_BPC)), dim3(VIEWN_BLOCK), 0, s, a);
 }
-static int viewn_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
-    switch (view_size) {
-        case 3: viewn_launch_v<3>(e, ids, count, out, s); break;
-        case 5: viewn_launch_v<5>(e, ids, count, out, s); break;
-        case 7: viewn_launch_v<7>(e, ids, count, out, s); break;
-        case 9: viewn_launch_v<9>(e, ids, count, out, s); break;
-        case 11: viewn_launch_v<11>(e, ids, count, out, s); break;
-        default: ARG_FAIL("view size must be 3, 5, 7, 9 or 11");
-    }
-    HIP_TRY(hipGetLastError());
-    return BBAI_OK;
-}
 
-// One observation launch of either kind (view_size 0: the fully observable encoding), and the two calls built on it: the listed envs'
-// frames (the entry point has asked listed_ready), and a step of the whole batch with every env's frame behind it, as one call.
+// One observation launch of either kind (view_size 0: the fully observable encoding; the entry has checked the size) of `count` frames
+// into the WriteRequest's bytes, and the two calls built on it: the listed envs' frames (the entry point has asked listed_ready), and a
+// step of the whole batch with every env's frame behind it, as one call.
+static WriteRequest observe_write(const bbai_env* e, int view_size, int64_t count, const uint8_t* out) {
+    return WriteRequest{(uintptr_t)out, count * (int64_t)(view_size ? 3 * view_size * view_size : 3 * e->cfg.W * e->cfg.H)};
+}
 static int observe_launch(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, hipStream_t s) {
-    return view_size ? viewn_launch(e, view_size, ids, count, out, s) : full_launch(e, ids, count, out, s);
+    if (!view_size) return full_launch(e, ids, count, out, s);
+    with_view_size(view_size, [&](auto v) { viewn_launch_v<v()>(e, ids, count, out, s); });
+    return BBAI_OK;
 }
 static int observe_listed(bbai_env* e, int view_size, const int64_t* ids, int64_t count, uint8_t* out, void* stream) {
     if (count == 0) return BBAI_OK;
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    (void)grid_target_foreign(e->gt, (uintptr_t)out, count * (int64_t)(view_size ? 3 * view_size * view_size : 3 * e->cfg.W * e->cfg.H));
-    BBAI_TRY(observe_launch(e, view_size, ids, count, out, s));
-    return call.leave();
+    return frame_call(e, stream, observe_write(e, view_size, count, out), [&](const TargetPlan&, hipStream_t s) { return observe_launch(e, view_size, ids, count, out, s); });
 }
 static int step_observe(bbai_env* e, const StepIO& io, int view_size, uint8_t* frames, void* stream) {
     BBAI_TRY(step_ready(e, io.auto_reset, "step"));
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    BBAI_TRY(step_launch(e, io, s));
-    BBAI_TRY(observe_launch(e, view_size, nullptr, e->n, frames, s));
-    return call.leave();
+    return frame_call(e, stream, observe_write(e, view_size, e->n, frames), [&](const TargetPlan&, hipStream_t s) -> int {
+        BBAI_TRY(step_launch(e, io, s));
+        return observe_launch(e, view_size, nullptr, e->n, frames, s);
+    });
 }
 
 extern "C" {
@@ -1643,7 +1609,7 @@ int bbai_step_view(bbai_env* e, const uint8_t* actions, uint8_t* image, uint8_t*
 
 }  // extern "C"
 
-// ---- the registered full-grid target (include/bbai_grid_target.h; bbai_gridtarget.hpp: record and planner; bbai_griddelta.hpp: k_grid_delta) ----
+// ---- the registered full-grid target (include/bbai_grid_target.h; bbai_target.hpp: record and planner; bbai_gridtarget.hpp: the pieces; bbai_griddelta.hpp: k_grid_delta) ----
 // The whole batch into the registered buffer.  DELTA: k_grid_delta<TS>, persistent blocks, GRIDDELTA_BPC per CU, over static groups of
 // griddelta_shape's envs (bbai_gridtarget.hpp; option "grid_delta_group").  FILL: the frames whole (k_render_grid<TS>, unchanged) and every
 // tile id behind them (k_grid_ids).
@@ -1651,10 +1617,10 @@ template <int TS>
 static void grid_target_launch(bbai_env* e, bool fill, hipStream_t s) {
     const int k = grid_ts_index(TS);
     const LevelCfg& c = e->cfg;
-    uint8_t* const out = (uint8_t*)e->gt.pixels;
+    uint8_t* const out = (uint8_t*)e->targets.grid.pixels;
     if (fill) {
         render_grid_launch<TS>(e, 0, nullptr, e->n, out, s);
-        hipLaunchKernelGGL(k_grid_ids, dim3(persistent_blocks(e, (e->n * c.W * c.H + 255) / 256, 8)), dim3(256), 0, s, env_list(e, nullptr, e->n, out), e->grid_lut[k], e->gt.shadow);
+        hipLaunchKernelGGL(k_grid_ids, dim3(persistent_blocks(e, (e->n * c.W * c.H + 255) / 256, 8)), dim3(256), 0, s, env_list(e, nullptr, e->n, out), e->grid_lut[k], e->targets.grid.shadow);
         return;
     }
     const int64_t want = cu_count(e) * GRIDDELTA_BPC;
@@ -1666,7 +1632,7 @@ static void grid_target_launch(bbai_env* e, bool fill, hipStream_t s) {
     a.g.frame_magic = (1ull << 32) / a.g.frame16 + 1;
     a.g.ppr = (uint32_t)(c.W * TS * 3 / GridTile<TS>::P);
     a.g.ppr_magic = (1ull << 32) / a.g.ppr + 1;
-    a.shadow = e->gt.shadow;
+    a.shadow = e->targets.grid.shadow;
     a.geom = grid_geom(c.W, c.H, TS);
     const GridDeltaShape shape = griddelta_shape(e->n, want, c.W, c.H, c.ES, e->grid_delta_group);
     a.envs_per_group = shape.envs_per_group;
@@ -1681,31 +1647,19 @@ static_assert(GRID_TARGET_ALIGN == GRID_PIECE, "the registered buffer starts on 
 // What a render into the target asks of the handle first (`func`: "bbai_<who>").
 static int grid_target_ready(const bbai_env* e, const char* func) {
     const char* who = func + 5;
-    if (!e->gt.pixels) { snprintf(g_err, sizeof(g_err), "%s: no grid target (bbai_set_grid_target)", who); return BBAI_ERR_STATE; }
-    if (!e->grid_tiles[grid_ts_index(e->gt.ts)]) { snprintf(g_err, sizeof(g_err), "%s: no atlas for tile size %d (bbai_set_grid_atlas)", who, e->gt.ts); return BBAI_ERR_STATE; }
+    if (!e->targets.grid.pixels) { snprintf(g_err, sizeof(g_err), "%s: no grid target (bbai_set_grid_target)", who); return BBAI_ERR_STATE; }
+    if (!e->grid_tiles[grid_ts_index(e->targets.grid.ts)]) { snprintf(g_err, sizeof(g_err), "%s: no atlas for tile size %d (bbai_set_grid_atlas)", who, e->targets.grid.ts); return BBAI_ERR_STATE; }
     if (!e->live) { snprintf(g_err, sizeof(g_err), "%s before reset", who); return BBAI_ERR_STATE; }
     return BBAI_OK;
 }
-// plan, launch, commit (bbai_gridtarget.hpp) -- behind the step's launches where `io` names a step -- as one call.  Where the registered
-// buffer lies over the 7x7 view's target (bbai_target.hpp) that one's history is gone.
+// The render into the target -- behind the step's launches where `io` names a step -- as one call.  Where the registered buffer lies over
+// the 7x7 view's target that one's history is gone (bbai_target.hpp).
 static int grid_target_call(bbai_env* e, const StepIO* io, void* stream) {
-    ON_DEVICE(e->device);
-    hipStream_t s = (hipStream_t)stream;
-    CallScope call(e, s);
-    BBAI_TRY(call.rc);
-    const GridPlan gp = plan_grid_target(e->gt, e->grid_render_delta != 0);
-    (void)plan_foreign(e->rt, e->gt.pixels, grid_target_bytes(e->gt));
-    const int rc = [&]() -> int {
+    return frame_call(e, stream, GridRenderRequest{e->grid_render_delta != 0}, [&](const TargetPlan& tp, hipStream_t s) -> int {
         if (io) BBAI_TRY(step_launch(e, *io, s));
-        const bool fill = gp.kind == GridPlan::FILL;
-        if (e->gt.ts == 8) grid_target_launch<8>(e, fill, s);
-        else if (e->gt.ts == 16) grid_target_launch<16>(e, fill, s);
-        else grid_target_launch<32>(e, fill, s);
-        HIP_TRY(hipGetLastError());
-        return call.leave();
-    }();
-    commit_grid_target(e->gt, gp, rc == BBAI_OK);
-    return rc;
+        with_tile_size(e->targets.grid.ts, [&](auto ts) { grid_target_launch<ts()>(e, tp.kind == TargetPlan::FILL, s); });
+        return BBAI_OK;
+    });
 }
 
 extern "C" {
@@ -1717,25 +1671,25 @@ int bbai_set_grid_target(bbai_env* e, uint8_t* frames, int tile_size) {
     if (frames && !grid_geom_ok(e->cfg.W, e->cfg.H, tile_size)) ARG_FAIL("grid too narrow for 64-byte pieces");
     ON_DEVICE(e->device);
     // the first registration: the shadow (un-registering keeps it)
-    if (frames && !e->gt.shadow) BBAI_TRY(e->own.alloc({{&e->gt.shadow, (size_t)e->n * e->cfg.W * e->cfg.H}}));
-    register_grid_target(e->gt, (uintptr_t)frames, tile_size, e->n, (int64_t)e->cfg.W * e->cfg.H);
+    if (frames && !e->targets.grid.shadow) BBAI_TRY(e->own.alloc({{&e->targets.grid.shadow, (size_t)e->n * e->cfg.W * e->cfg.H}}));
+    register_target(e->targets.grid, (uintptr_t)frames, tile_size, e->n, grid_frame_bytes((int64_t)e->cfg.W * e->cfg.H, tile_size));
     return BBAI_OK;
 }
 
 int bbai_grid_target_invalidate(bbai_env* e) {
     if (!e) ARG_FAIL("null handle");
-    invalidate_grid_target(e->gt);
+    invalidate_target(e->targets.grid);
     return BBAI_OK;
 }
 
 int bbai_grid_target_shadow(bbai_env* e, uint8_t* out, void* stream) {
     if (!e || !out) ARG_FAIL("null handle or buffer");
-    if (!e->gt.shadow) { snprintf(g_err, sizeof(g_err), "grid_target_shadow before bbai_set_grid_target"); return BBAI_ERR_STATE; }
+    if (!e->targets.grid.shadow) { snprintf(g_err, sizeof(g_err), "grid_target_shadow before bbai_set_grid_target"); return BBAI_ERR_STATE; }
     ON_DEVICE(e->device);
     hipStream_t s = (hipStream_t)stream;
     CallScope call(e, s);
     BBAI_TRY(call.rc);
-    HIP_TRY(hipMemcpyAsync(out, e->gt.shadow, (size_t)e->n * e->cfg.W * e->cfg.H, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out, e->targets.grid.shadow, (size_t)e->n * e->cfg.W * e->cfg.H, hipMemcpyDeviceToDevice, s));
     return call.leave();
 }
 
@@ -1791,7 +1745,7 @@ static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, h
         // cells and updates the shadow (step_dirty), the render only stores (k_render_dstore).  From the step kernel on, the shadow is ahead
         // of the frame until the render has been launched: a failure in between invalidates it (step_render_launch).
         const bool from_step = e->render_delta_from_step < 0 ? e->n >= RENDER_FROM_STEP_MIN_ENVS : e->render_delta_from_step != 0;
-        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !io.auto_reset) && whole_batch_delta(e->rt, (uintptr_t)pixels, e->render_delta != 0);
+        p.dirty = dirty = pixels && from_step && (p.fused || e->inplace || !io.auto_reset) && whole_batch_delta(e->targets.view, (uintptr_t)pixels, e->render_delta != 0);
         const int want = e->step_render_split < 0 ? (STEP_RENDER_SPLIT_DEFAULT && e->n >= STEP_RENDER_SPLIT_MIN) : e->step_render_split;      // (an explicit 1: any size)
         const int64_t nb = step_blocks(e), hb = nb / 2;
         const bool split = want && pixels && (p.fused || !io.auto_reset) && hb > 0;
@@ -1823,7 +1777,7 @@ static int step_render_launch_(bbai_env* e, const StepIO& io, uint8_t* pixels, h
 static int step_render_launch(bbai_env* e, const StepIO& io, uint8_t* pixels, hipStream_t s) {
     bool dirty = false;
     const int rc = step_render_launch_(e, io, pixels, s, dirty);
-    if (rc != BBAI_OK && dirty) invalidate_target(e->rt);       // (a failure before the render's own plan: its commit was never reached)
+    if (rc != BBAI_OK && dirty) invalidate_target(e->targets.view);       // (a failure before the render's own plan: its commit was never reached)
     return rc;
 }
 
@@ -2471,7 +2425,7 @@ int bbai_set_option(bbai_env* e, const char* name, int64_t value) {
         if (k->field == &bbai_env::render_piece_bytes && v != 64 && v != 128) ARG_FAIL("render_piece_bytes: 64 or 128");
         if (k->field == &bbai_env::rt_next_ts && v != 8 && v != 16 && v != 32) ARG_FAIL("render_target_tile_size: 8, 16 or 32");
         e->*k->field = knob_value(*k, v);
-        if (k->field == &bbai_env::render_delta) invalidate_target(e->rt);
+        if (k->field == &bbai_env::render_delta) invalidate_target(e->targets.view);
         if (k->field == &bbai_env::gate_probe) { e->n_probed = 0; e->gate_forced = 0; }      // (forget the verdicts: the next window probes again)
     }
     else {
@@ -2491,8 +2445,8 @@ static int read_flow(bbai_env* e, int word, unsigned long long* out) {
 int bbai_get_option(bbai_env* e, const char* name, int64_t* out) {
     if (!e || !name || !out) ARG_FAIL("null handle, name or output");
     if (const Knob* k = find_knob(name)) *out = e->*k->field;
-    else if (!strcmp(name, "render_delta_valid")) *out = e->rt.valid ? 1 : 0;
-    else if (!strcmp(name, "grid_delta_valid")) *out = e->gt.valid ? 1 : 0;
+    else if (!strcmp(name, "render_delta_valid")) *out = e->targets.view.valid ? 1 : 0;
+    else if (!strcmp(name, "grid_delta_valid")) *out = e->targets.grid.valid ? 1 : 0;
     else if (!strcmp(name, "gate_fault")) *out = e->host_flags ? (int64_t)e->host_flags[0] : 0;     // sticky; no synchronisation
     else if (!strcmp(name, "profile_step_ticks")) *out = e->prof_step_ticks;
     else if (!strcmp(name, "cplane")) *out = e->cplane ? 1 : 0;

@@ -1,15 +1,7 @@
-// bbai_gridtarget.hpp -- the registered full-grid target (bbai_set_grid_target, include/bbai_grid_target.h) as a record and one planner, and the
-// geometry of the 64-byte pieces its delta render stores (k_grid_delta<TS>, bbai_griddelta.hpp).
-// Plain C++: no HIP, no device code (tests/test_grid_delta_host.py compiles it with g++ and drives it with made-up addresses).
-//
-// The caller registers ONE buffer uint8[n][H ts][W ts][3], RGBImgObsWrapper's frames of the whole batch; the handle keeps, in `shadow`, the
-// grid-atlas tile id of every cell of the frame the buffer holds.  While the shadow is valid (and option "grid_render_delta" is on) a
-// render into the target stores only the pieces that hold a changed cell (DELTA); while it is not, the render draws the frames whole and
-// writes every tile id behind them (FILL), after which the shadow is valid.  Any other write of this handle into the registered bytes
-// leaves a frame the shadow does not describe: grid_target_foreign invalidates.  A render is three steps -- plan_grid_target, the
-// launches, commit_grid_target -- and the state moves only when the launches and the call's exit succeeded; a failed call invalidates.
-// This is a second record on the handle, next to bbai_target.hpp's RenderTarget (the 7x7 view's), which it leaves alone.
-// Addresses are integers, as there: the planner compares addresses of unrelated buffers.
+// bbai_gridtarget.hpp -- the geometry of the 64-byte pieces that the registered full-grid target's delta render stores (k_grid_delta<TS>,
+// bbai_griddelta.hpp; bbai_set_grid_target, include/bbai_grid_target.h), and that kernel's launch shape.  The target's record and its
+// planner are bbai_target.hpp's, shared with the 7x7 view's target.
+// Plain C++: no HIP, no device code (tests/test_grid_delta_host.py compiles it with g++).
 #pragma once
 #include <stdint.h>
 #include "bbai_types.hpp"
@@ -17,54 +9,6 @@
 namespace bbai {
 
 constexpr int GRID_PIECE = 64;            // the store unit, as the view's delta renders' (bbai_render.hpp PIECE_BYTES, bbai_viewpx.hpp VIEW_PIECE)
-constexpr int GRID_TARGET_ALIGN = 64;     // the registered buffer starts on a piece
-
-struct GridTarget {
-    uintptr_t pixels = 0;         // the registered caller-owned uint8[n][H ts][W ts][3] buffer (0: none)
-    int ts = 8;                   // the tile size of that registration
-    uint8_t* shadow = nullptr;    // [n][W H] tile id of every cell of the frame in `pixels`, row-major y W + x, in the grid atlas of `ts` (allocated at the first registration)
-    bool valid = false;           // `shadow` describes `pixels`
-    int64_t n = 0;                // envs of the batch
-    int64_t cells = 0;            // W H: a frame is 3 cells ts ts bytes
-};
-
-inline int64_t grid_target_bytes(const GridTarget& t) { return t.n * 3 * t.cells * (int64_t)t.ts * t.ts; }
-
-// The one place that writes the flag.
-inline void invalidate_grid_target(GridTarget& t) { t.valid = false; }
-
-// bbai_set_grid_target (pixels 0: un-register; the shadow stays allocated).  The history starts invalid.
-inline void register_grid_target(GridTarget& t, uintptr_t pixels, int ts, int64_t n, int64_t cells) {
-    t.pixels = pixels; t.ts = ts; t.n = n; t.cells = cells;
-    invalidate_grid_target(t);
-}
-
-// The grid atlas of tile size `ts` was replaced: a frame registered at that size was drawn with the old one.
-inline void grid_target_atlas_replaced(GridTarget& t, int ts) { if (t.pixels && t.ts == ts) invalidate_grid_target(t); }
-
-// Do the `bytes` bytes at `out` overlap the registered buffer?  (A range that ends where the buffer starts, or starts where it ends, does not.)
-inline bool overlaps_grid_target(const GridTarget& t, uintptr_t out, int64_t bytes) {
-    return t.pixels && bytes > 0 && out < t.pixels + (uintptr_t)grid_target_bytes(t) && out + (uintptr_t)bytes > t.pixels;
-}
-
-// Another entry of the handle writes `bytes` bytes at `out` (frames or observations into a per-call caller buffer): where they land in
-// the registered buffer its history is gone, here and now.  Returns whether it was.
-inline bool grid_target_foreign(GridTarget& t, uintptr_t out, int64_t bytes) {
-    const bool hit = overlaps_grid_target(t, out, bytes);
-    if (hit) invalidate_grid_target(t);
-    return hit;
-}
-
-struct GridPlan { enum Kind { FILL, DELTA } kind; };
-
-// What a render into the target does: DELTA while the history is valid and option "grid_render_delta" is on, else whole frames with every
-// tile id behind them.  Changes nothing until commit_grid_target.
-inline GridPlan plan_grid_target(const GridTarget& t, bool delta) {
-    return GridPlan{t.valid && delta ? GridPlan::DELTA : GridPlan::FILL};
-}
-
-// Behind the launches and the call's exit.  ok: the shadow describes the buffer.  Not ok: either may hold part of a frame.
-inline void commit_grid_target(GridTarget& t, const GridPlan&, bool ok) { t.valid = ok; }
 
 // ---- the pieces of a frame ---------------------------------------------------------------------------------------------------------
 // A frame is H ts pixel rows of RB = 3 W ts bytes; F = 3 W H ts^2 bytes.  RB is no multiple of 64 for most W (96 B at W = 4 / ts 8,

@@ -135,9 +135,16 @@ int bbai_step_render(bbai_env* env, const uint8_t* actions_dev, uint8_t* image_d
  * Option "render_target_tile_size" (8 by default; 16 or 32) states the frame size of the NEXT registration: uint8[N][7 ts][7 ts][3].  A
  * handle has one target at a time; registering replaces it and invalidates the history.  A target of 16 / 32 is bbai_render_view's (below):
  * the tile ids are those of that size's view atlas, bbai_set_view_atlas of that size invalidates (bbai_set_atlas does not), and
- * bbai_render, bbai_step_render and bbai_rollout treat the handle as one without a target -- but for this: whatever they, or any other
- * render of the handle, write into the registered buffer's bytes invalidates its history.  bbai_render_shadow, bbai_render_invalidate and
- * the options "render_delta" / "render_delta_valid" work alike at every size. */
+ * bbai_render, bbai_step_render and bbai_rollout treat the handle as one without a target -- but for the one rule below.
+ * bbai_render_shadow, bbai_render_invalidate and the options "render_delta" / "render_delta_valid" work alike at every size.
+ * What drops the history -- one list, for this target and for the full-grid target (bbai_grid_target.h) alike: a registration; the
+ * target's atlas of the registered tile size installed again; its invalidate entry; a set of "render_delta" (this target only); a
+ * render that failed; and EVERY entry of this handle that writes frames or observations into a buffer whose bytes overlap the
+ * registered ones without being a planned render of that target's envs into their own rows -- bbai_render, bbai_step_render,
+ * bbai_rollout's pixels, bbai_render_view, bbai_render_view_pixels, bbai_render_grid, bbai_observe_full, bbai_observe_view, the `full` /
+ * `view` frames of bbai_step_full / bbai_step_view, and a render into the other target where the two buffers overlap.  A write that
+ * overlaps neither buffer changes nothing.  (The encoded `image`, `dir` and reward outputs of the step entries, rollout and tap rows and
+ * the demo entries are not frames and are not looked at: do not point them into a registered buffer.) */
 int bbai_set_render_target(bbai_env* env, uint8_t* pixels_dev);
 int bbai_render_invalidate(bbai_env* env);
 /* A copy of the registered buffer's tile ids, uint8[N][49] (cell = 7 x + y of the encoded view), into a device buffer, on `stream`:
@@ -153,7 +160,7 @@ int bbai_render_shadow(bbai_env* env, uint8_t* out_dev, void* stream);
  * bbai_render_grid writes frame k = the picture of env ids_dev[k] (int64 device array; NULL = envs 0 .. count - 1) into
  * out_dev + k * H*ts * W*ts * 3 (16-byte aligned), pixel [row y][column x][rgb] as Grid.render lays it out: the grid's cells, the
  * agent's triangle on its cell, and -- highlight != 0 -- the cells the agent sees lightened (the carried object is not drawn).  It
- * reads the current state and writes nothing but out_dev (not the pixel observations, not the registered render target, no state);
+ * reads the current state and writes nothing but out_dev (no state; where out_dev overlaps a registered target: the list above);
  * asynchronous on `stream`, ordered behind the handle's previous calls like every state-reading call.  An id outside [0, n) yields an
  * all-zero frame, never an out-of-bounds read.  BBAI_ERR_STATE without an atlas of that tile size or before the first reset;
  * BBAI_ERR_ARG for a tile size other than 8 / 16 / 32, count < 0, count > n without ids, or a missing / misaligned out_dev. */

@@ -32,12 +32,14 @@ extern "C" {
  * bbai_step_grid_target is bbai_step -- the same arguments, the same launches -- with that render behind it, as one call:
  * RGBImgObsWrapper's step.  BBAI_ERR_ARG for a null handle or buffer; BBAI_ERR_STATE as the render's and the step's.
  *
- * What drops the history: a registration, bbai_set_grid_atlas at the registered tile size, bbai_grid_target_invalidate (call it after
- * writing into the buffer yourself), a render that failed, and every entry of this handle that writes frames or observations into a
- * per-call buffer whose bytes overlap the registered ones (bbai_render, bbai_render_view, bbai_render_view_pixels, bbai_render_grid,
- * bbai_observe_full, bbai_observe_view).  Likewise a grid target laid over the buffer registered with bbai_set_render_target drops
- * that one's history with every render.  State changes that never touch the buffer (bbai_load_state, bbai_reseed, bbai_import_state,
- * bbai_checkpoint_load) need nothing: the shadow describes the buffer, not the state, and the next render compares.
+ * What drops the history: the one list of bbai.h (bbai_set_render_target), which holds for both registered buffers -- a registration,
+ * bbai_set_grid_atlas at the registered tile size, bbai_grid_target_invalidate (call it after writing into the buffer yourself), a
+ * render that failed, and every entry of this handle that writes frames or observations into a per-call buffer whose bytes overlap the
+ * registered ones (bbai_render, bbai_step_render, bbai_render_view, bbai_render_view_pixels, bbai_render_grid, bbai_observe_full,
+ * bbai_observe_view, the frames of bbai_step_full / bbai_step_view).  Likewise a grid target laid over the buffer registered with
+ * bbai_set_render_target drops that one's history with every render.  State changes that never touch the buffer (bbai_load_state,
+ * bbai_reseed, bbai_import_state, bbai_checkpoint_load) need nothing: the shadow describes the buffer, not the state, and the next
+ * render compares.
  *
  * Option "grid_delta_group" (default 0): envs a block of the delta render works on at a time; 0 = chosen by batch size, a value above
  * what the kernel's planes hold for the grid is clamped.  Never semantics: every setting stores the same bytes (the tests run them all).

@@ -30,9 +30,9 @@ extern "C" {
  * bbai_render_view_pixels draws frame k = row ids_dev[k] (int64 device array; NULL = rows 0 .. count - 1) of the encoded buffer
  * image_dev[rows][V][V][3] into out_dev + k * 3 V V ts ts (16-byte aligned; a frame is a multiple of 64 bytes at every size).  It writes
  * nothing but out_dev; asynchronous on `stream`, ordered behind the handle's previous calls.  A row id outside [0, rows) yields an
- * all-zero frame and no read outside the buffer; an id may be listed more than once.  Where the frames overlap the buffer registered
- * with bbai_set_render_target they are a foreign whole-frame write: the target's history is invalidated, as by a bbai_render_view with
- * ids; a write elsewhere leaves it alone.  BBAI_ERR_ARG for a null handle, a view size or tile size outside the sets, rows < 0,
+ * all-zero frame and no read outside the buffer; an id may be listed more than once.  Where the frames overlap a registered buffer
+ * (bbai_set_render_target, bbai_set_grid_target) they are a foreign whole-frame write: that target's history is invalidated, as by a
+ * bbai_render_view with ids (the one list: bbai.h, bbai_set_render_target); a write elsewhere leaves both alone.  BBAI_ERR_ARG for a null handle, a view size or tile size outside the sets, rows < 0,
  * count < 0, count > rows without ids, a missing or misaligned out_dev, or a missing image_dev with work to do; BBAI_ERR_STATE while no
  * atlas of that tile size is installed; count == 0 is BBAI_OK.  A refused call writes nothing. */
 int bbai_set_view_pixels_atlas(bbai_env* env, int tile_size /* 8|16|32 */, const uint8_t* tiles_host, int n_tiles /* <= 64 */,

@@ -439,6 +439,97 @@ def test_grid_target_and_view_target_side_by_side(gpu):
     assert env.get_option("render_delta_valid") == 1
 
 
+POISON = 0x5A
+
+
+def view_restored(env, acts, what):
+    """The 7x7 target's history is gone: the next step() draws every frame whole (every byte of poisoned `pixels` rewritten) and restores it."""
+    import torch
+    assert env.get_option("render_delta_valid") == 0, what
+    env.pixels.fill_(POISON)
+    env.step(acts)
+    assert torch.equal(env.pixels, env.render_encoding(out=torch.empty_like(env.pixels))), what
+    assert env.get_option("render_delta_valid") == 1, what
+
+
+@pytest.mark.gpu
+def test_listed_frames_into_the_view_target_drop_its_history(gpu):
+    """bbai_render_grid, bbai_observe_view and bbai_observe_full write listed envs' frames wherever the caller says: into the bytes of the
+    registered 7x7 target they drop its history, as into the grid target's (test_what_drops_the_history); elsewhere they leave it."""
+    import torch
+    n, ts = 6, 8
+    env = make_env(gpu, SMALL, n, ts, full_obs=False)
+    env._install_atlas("grid", ts)
+    acts = torch.full((n,), LEFT, dtype=torch.uint8, device=gpu)
+    env.reset()
+    env.step(acts)
+    assert env.get_option("render_delta_valid") == 1
+    flat = env.pixels.view(-1)
+    assert flat.data_ptr() % 16 == 0 and flat.numel() == n * 9408
+
+    def kept(what):
+        assert env.get_option("render_delta_valid") == 1, what
+        env.step(acts)                                    # a delta render
+        assert env.get_option("render_delta_valid") == 1 and torch.equal(env.pixels, env.render_encoding(out=torch.empty_like(env.pixels))), what
+
+    env.render_grid([0], tile_size=ts, out=flat[9408:9408 + 3072].view(1, 32, 32, 3))             # the second frame's first bytes
+    view_restored(env, acts, "render_grid into the registered buffer")
+    env.observe_view([0, 1], view_size=5, out=flat[64:64 + 2 * 75].view(2, 5, 5, 3))
+    view_restored(env, acts, "observe_view into the registered buffer")
+    env.observe_full([2], out=flat[n * 9408 - 48:].view(1, 4, 4, 3))                             # the buffer's last 48 bytes
+    view_restored(env, acts, "observe_full into the registered buffer")
+    env.render_grid([0], tile_size=ts)
+    kept("render_grid into a buffer of its own")
+    env.observe_view([0, 1], view_size=5)
+    kept("observe_view into a buffer of its own")
+    env.observe_full([2])
+    kept("observe_full into a buffer of its own")
+
+
+@pytest.mark.gpu
+def test_step_full_and_step_view_tell_both_targets(gpu):
+    """bbai_step_view / bbai_step_full write n frames to a buffer the caller names: inside a registered buffer they drop that target's
+    history and leave the other's, and the next render of the dropped one rewrites every byte."""
+    import torch
+    n, ts = 6, 8
+    env = make_env(gpu, SMALL, n, ts, full_obs=False)
+    env._install_atlas("grid", ts)
+    F = gdu.frame_bytes(4, 4, ts)
+    buf = torch.zeros((n * F,), dtype=torch.uint8, device=gpu)
+    lib, h = env.lib, env.handle
+    assert lib.bbai_set_grid_target(h, ctypes.c_void_p(buf.data_ptr()), ts) == 0
+    acts = torch.full((n,), LEFT, dtype=torch.uint8, device=gpu)
+    valid = lambda: (env.get_option("render_delta_valid"), env.get_option("grid_delta_valid"))
+    grid_frames = lambda: buf.view(n, 4 * ts, 4 * ts, 3)
+    env.reset()
+    env.step(acts)
+    assert lib.bbai_render_grid_target(h, env._stream()) == 0
+    assert valid() == (1, 1)
+    # the 5x5 views of a step into the grid target's buffer
+    view = buf[64:64 + n * 75]
+    assert view.data_ptr() % 16 == 0
+    assert lib.bbai_step_view(h, acts.data_ptr(), *env._step_out(), 5, view.data_ptr(), env._stream()) == 0
+    assert valid() == (1, 0)
+    buf.fill_(POISON)
+    assert lib.bbai_render_grid_target(h, env._stream()) == 0
+    assert valid() == (1, 1) and torch.equal(grid_frames(), whole(env, ts))
+    env.step(acts)                                        # the untouched 7x7 target: a delta render, of two steps' changes
+    assert valid() == (1, 1) and torch.equal(env.pixels, env.render_encoding(out=torch.empty_like(env.pixels)))
+    # a step's full observations into the 7x7 target's buffer
+    full = env.pixels.view(-1)[128:128 + n * 48]
+    assert full.data_ptr() % 16 == 0
+    assert lib.bbai_step_full(h, acts.data_ptr(), *env._step_out(), full.data_ptr(), env._stream()) == 0
+    assert valid() == (0, 1)
+    view_restored(env, acts, "bbai_step_full into the registered buffer")
+    assert lib.bbai_render_grid_target(h, env._stream()) == 0                # the untouched grid target: a delta render
+    assert valid() == (1, 1) and torch.equal(grid_frames(), whole(env, ts))
+    # buffers of their own: both histories stay
+    own = torch.empty((n * 75,), dtype=torch.uint8, device=gpu)
+    assert lib.bbai_step_view(h, acts.data_ptr(), *env._step_out(), 5, own.data_ptr(), env._stream()) == 0
+    assert lib.bbai_step_full(h, acts.data_ptr(), *env._step_out(), own.data_ptr(), env._stream()) == 0
+    assert valid() == (1, 1)
+
+
 # ---- 4. errors ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_refusals(gpu):

@@ -1,4 +1,4 @@
-"""The registered full-grid target on the host (include/bbai_grid_target.h; babyai_amd/csrc/bbai_gridtarget.hpp, compiled here with g++):
+"""The registered full-grid target on the host (include/bbai_grid_target.h; babyai_amd/csrc/bbai_gridtarget.hpp and bbai_target.hpp, compiled here with g++):
 the geometry of a frame's 64-byte pieces against grid_delta_util's, which is written from the picture alone; the planner's state machine
 with made-up addresses; and the C ABI of the five entries against engine.ABI_GRID_TARGET.  No GPU."""
 import ctypes
@@ -18,6 +18,7 @@ GRIDS = sorted(gdu.level_grids())
 
 _SRC = r"""
 #include "bbai_gridtarget.hpp"
+#include "bbai_target.hpp"
 using namespace bbai;
 extern "C" int gd_ok(int W, int H, int ts) { return grid_geom_ok(W, H, ts) ? 1 : 0; }
 extern "C" uint32_t gd_pieces(int W, int H, int ts) { return grid_geom(W, H, ts).NP; }
@@ -55,19 +56,20 @@ extern "C" void gd_shape_constants(int* c) {
     c[0] = GRIDDELTA_BLOCK; c[1] = GRIDDELTA_MAX_ENVS; c[2] = GRIDDELTA_APP; c[3] = GRIDDELTA_IDS; c[4] = GRIDDELTA_BPC; c[5] = MAX_W;
 }
 // the planner, on one record
-static GridTarget T;
+static Targets BOTH;                      // (the view target stays un-registered)
+static GridTarget& T = BOTH.grid;
 static uint8_t SHADOW[4];
-extern "C" void gt_register(uint64_t pixels, int ts, int64_t n, int64_t cells) { if (pixels) T.shadow = SHADOW; register_grid_target(T, (uintptr_t)pixels, ts, n, cells); }
-extern "C" int gt_render(int delta, int ok) { const GridPlan p = plan_grid_target(T, delta != 0); const int k = (int)p.kind; commit_grid_target(T, p, ok != 0); return k; }
-extern "C" int gt_plan(int delta) { return (int)plan_grid_target(T, delta != 0).kind; }
-extern "C" int gt_foreign(uint64_t out, int64_t bytes) { return grid_target_foreign(T, (uintptr_t)out, bytes) ? 1 : 0; }
-extern "C" void gt_atlas(int ts) { grid_target_atlas_replaced(T, ts); }
-extern "C" void gt_invalidate() { invalidate_grid_target(T); }
+extern "C" void gt_register(uint64_t pixels, int ts, int64_t n, int64_t cells) { if (pixels) T.shadow = SHADOW; register_target(T, (uintptr_t)pixels, ts, n, grid_frame_bytes(cells, ts)); }
+extern "C" int gt_render(int delta, int ok) { const TargetPlan p = plan_target(BOTH, GridRenderRequest{delta != 0}); const int k = (int)p.kind; commit_target(BOTH, p, ok != 0); return k; }
+extern "C" int gt_plan(int delta) { return (int)plan_target(BOTH, GridRenderRequest{delta != 0}).kind; }
+extern "C" int gt_foreign(uint64_t out, int64_t bytes) { const bool hit = overlaps_target(T, (uintptr_t)out, bytes); (void)plan_target(BOTH, WriteRequest{(uintptr_t)out, bytes}); return hit ? 1 : 0; }
+extern "C" void gt_atlas(int ts) { target_atlas_replaced(T, ts); }
+extern "C" void gt_invalidate() { invalidate_target(T); }
 extern "C" int gt_valid() { return T.valid ? 1 : 0; }
 extern "C" uint64_t gt_pixels() { return (uint64_t)T.pixels; }
-extern "C" int64_t gt_bytes() { return grid_target_bytes(T); }
+extern "C" int64_t gt_bytes() { return target_bytes(T); }
 extern "C" int gt_has_shadow() { return T.shadow ? 1 : 0; }
-extern "C" int gt_constants(int k) { return k == 0 ? GRID_PIECE : k == 1 ? GRID_TARGET_ALIGN : (int)GridPlan::FILL * 10 + (int)GridPlan::DELTA; }
+extern "C" int gt_constants(int k) { return k == 0 ? GRID_PIECE : k == 1 ? GRID_TARGET_ALIGN : (int)TargetPlan::FILL * 10 + (int)TargetPlan::DELTA; }
 """
 
 
@@ -284,7 +286,7 @@ def test_planner_state_machine(lib):
 
 def test_planner_with_extents_and_addresses_beyond_4_gib(lib):
     """Targets of 2^32 + 2^24 bytes (tests/test_gpu_large_outputs.py's) up to 2^40 bytes, at bases just above 2^32, far above it and below
-    it with the buffer running across it: grid_target_bytes and the overlap test against Python's integers, which do not wrap."""
+    it with the buffer running across it: target_bytes and the overlap test against Python's integers, which do not wrap."""
     FILL, DELTA = divmod(lib.gt_constants(2), 10)
     cases = 0
     for (W, H), ts in [((22, 22), 32), ((22, 22), 8), ((8, 8), 16), ((4, 4), 8), ((25, 25), 32)]:

@@ -1,4 +1,4 @@
-"""The registered render target's bookkeeping (babyai_amd/csrc/bbai_target.hpp: RenderTarget, plan_target, commit_target) without a GPU:
+"""The registered render target's bookkeeping (babyai_amd/csrc/bbai_target.hpp: RenderTarget, plan_target, commit_target -- the view render's and the other write's entries) without a GPU:
 the header compiled with g++ from a wrapper this test writes, driven with made-up addresses.  What a render means for the target --
 ELSEWHERE, FILL or DELTA --, what invalidates the shadow and when it becomes valid again are checked against a model written here from
 the contract in include/bbai.h (bbai_set_render_target, bbai_render_view), over an enumerated grid of targets and requests; then the call
@@ -20,26 +20,27 @@ FAR = 0x100000000000          # buffers that are not the registered one
 WRAPPER = """
 #include "bbai_target.hpp"
 using namespace bbai;
-static RenderTarget g;
+static Targets g_both;                    // (the grid target stays un-registered: these tests are about the view's)
+static RenderTarget& g = g_both.view;
 static TargetPlan g_plan;
 extern "C" {
-void tg_new() { g = RenderTarget(); }
+void tg_new() { g_both = Targets(); }
 // bbai_set_render_target: the shadow and the masks come with the first registration (addresses nobody reads)
 void tg_register(unsigned long long pixels, int ts, long long n) {
     if (pixels && !g.shadow) { g.shadow = reinterpret_cast<uint8_t*>(uintptr_t(1) << 20); g.dmask = reinterpret_cast<uint64_t*>(uintptr_t(1) << 21); }
-    register_target(g, (uintptr_t)pixels, ts, n);
+    register_target(g, (uintptr_t)pixels, ts, n, view_frame_bytes(ts));
 }
 void tg_invalidate() { invalidate_target(g); }
 void tg_atlas_replaced(int ts) { target_atlas_replaced(g, ts); }
 void tg_force(int valid, long long filled) { g.valid = valid != 0; g.filled = filled; }      // (the grid's "state beforehand")
 int tg_plan(int ts, unsigned long long out, long long bytes, long long env_off, long long nr, int partial, int delta) {
-    g_plan = plan_target(g, RenderRequest{ts, (uintptr_t)out, bytes, env_off, nr, partial != 0, delta != 0});
+    g_plan = plan_target(g_both, RenderRequest{ts, (uintptr_t)out, bytes, env_off, nr, partial != 0, delta != 0});
     return g_plan.kind == TargetPlan::ELSEWHERE ? 0 : g_plan.kind == TargetPlan::FILL ? 1 : 2;
 }
 long long tg_shadow_off() { return g_plan.shadow_off; }
-void tg_commit(int ok) { commit_target(g, g_plan, ok != 0); }
+void tg_commit(int ok) { commit_target(g_both, g_plan, ok != 0); }
 int tg_query(unsigned long long pixels, int delta) { const RenderTarget& c = g; return whole_batch_delta(c, (uintptr_t)pixels, delta != 0) ? 1 : 0; }
-int tg_foreign(unsigned long long out, long long bytes) { g_plan = plan_foreign(g, (uintptr_t)out, bytes); return g_plan.kind == TargetPlan::ELSEWHERE ? 0 : 1; }
+int tg_foreign(unsigned long long out, long long bytes) { g_plan = plan_target(g_both, WriteRequest{(uintptr_t)out, bytes}); return g_plan.kind == TargetPlan::ELSEWHERE ? 0 : 1; }
 int tg_valid() { return g.valid ? 1 : 0; }
 long long tg_filled() { return g.filled; }
 void tg_state(unsigned long long* s) {
@@ -309,7 +310,7 @@ def test_foreign_writes_into_targets_beyond_4_gib(lib):
                     kind = lib.tg_plan({8: 16, 16: 32, 32: 8}[ts], out, nbytes, 0, 1, 1, 1)
                 else:
                     kind = lib.tg_plan(ts, out, nbytes, 0, 1, 1, 1)
-                hit = out < base + size and out + nbytes > base                        # Python integers
+                hit = nbytes > 0 and out < base + size and out + nbytes > base         # Python integers (an empty range overlaps nothing)
                 if entry == "listed rows" and ts == 8 and out == base:
                     continue                                                            # (at 8 a range from env 0 on is on target)
                 assert kind == ELSEWHERE, (ts, n, hex(base), hex(out), nbytes, entry)
